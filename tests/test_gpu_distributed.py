@@ -128,7 +128,7 @@ def test_bench_two_ranks_with_gather_in_the_timed_region():
         env.pop(k, None)
     env.update(LZ_BENCH_BACKEND="gloo", LZ_BENCH_SHARE_GPU="1", LZ_BENCH_PORT=str(_free_port()))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-                        "--games", "256", "--sims", "16", "--model", "b6c64", "--soak-seconds", "0",
+                        "--games", "256", "--sims", "16", "--model", "b6c64", "--soak-steps", "0",
                         "--reuse-factor", "2", "--no-probe"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -556,3 +556,41 @@ def test_tree_runner_switches_to_compact_lists_in_the_drain_and_plays_the_same_g
     assert c1["leaf_eval_count"] <= ca["leaf_eval_count"] <= c0["leaf_eval_count"]
     print(f"{plies} plies: lists in {ca['list_searches']} of them; launched evaluations dense {c0['leaf_eval_count']}, "
           f"auto {ca['leaf_eval_count']}, lists always {c1['leaf_eval_count']}")
+
+
+def test_bench_dump_outputs_are_the_same_in_every_run(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's trajectory rows (one per game) as float32 .npy files, and the
+    same numbers from two runs with the same arguments (a fixed count of soak steps, seeded weights and population), so
+    that two builds can be compared output for output."""
+    import json
+    import os
+    import subprocess
+    import sys
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    fields = ("state_tensors", "legal_masks", "policy_targets")
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--games", "256", "--sims", "16", "--model", "b6c64", "--soak-steps", "1", "--reuse-factor", "2",
+                            "--no-probe", "--no-smi", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["soak"]["steps"] == 1 and "also" not in out
+        assert abs(out["value"] - 256 * 3 / (out["ms_per_step"] * 3e-3)) < 2e-3 * out["value"]      # ms_per_step is rounded
+        d = out["dump_outputs"]
+        assert d["rows"] == d["rows_of_step"] == 256 and d["files"] == sorted(f + ".npy" for f in fields)
+        arrays = {f: np.load(tmp_path / run / (f + ".npy")) for f in fields}
+        assert all(a.dtype == np.float32 and a.shape[0] == 256 for a in arrays.values())
+        assert arrays["state_tensors"].shape == (256, 11, 6, 6) and arrays["policy_targets"].shape == (256, 220)
+        legal = arrays["legal_masks"]
+        assert set(np.unique(legal).tolist()) <= {0.0, 1.0} and float(legal.sum()) > 0
+        pol = arrays["policy_targets"]
+        assert float(pol.min()) >= 0.0 and float((pol * (1 - legal)).max()) == 0.0 and float(pol.sum()) > 0
+        got.append(arrays)
+    for f in fields:
+        assert np.array_equal(got[0][f], got[1][f]), f
