@@ -396,7 +396,8 @@ typedef struct LzTreeDesc {
     int32_t* path;                 /* [B*path_cap] edge index | bit 31: the mover changes from parent to child */
     int32_t* path_len;             /* [B] */
     int32_t* leaf_kind;            /* [B] 0 inactive, 1 needs evaluation, 2 terminal (value in leaf_value),
-                                      3 root kept by lz_tree_advance (no evaluation, noise mix only) */
+                                      3 root kept by lz_tree_advance (no evaluation, noise mix only),
+                                      4 shared: a transposed twin's evaluation is reused (pos_index) */
     void*    leaf_state;           /* packed [B]: state awaiting evaluation */
     float*   leaf_value;           /* [B] */
     uint8_t* root_terminal;        /* [B] */
@@ -431,7 +432,16 @@ typedef struct LzTreeDesc {
     int32_t* live_row;             /* [num_games] */
     int64_t* live_count;           /* [live_count_cap] */
     int64_t  live_count_cap;
+    /* Optional position index (all four arrays and pos_slots, or none): a leaf whose 32-byte state another node (not
+     * the root) of the same tree holds is not evaluated (leaf_kind 4, shared) -- it takes that node's priors and raw
+     * network value, bit for bit, and is left out of the compact lists.  Env LZ_TREE_SHARE=0 turns the look-ups off. */
+    int32_t* pos_index;            /* [B*pos_slots] node index or -1 (open addressing; lz_tree_begin / lz_tree_advance reset it) */
+    float*   node_value;           /* [B*node_cap] raw network value each node was expanded with */
+    int32_t* leaf_src;             /* [B] source node of a shared leaf (select -> expand hand-off) */
+    int32_t* share_count;          /* optional [B]: += 1 for every shared leaf a game's expand step took (NULL: off) */
+    int64_t  pos_slots;            /* slots per game: a power of two >= 64 */
 } LzTreeDesc;
+LZ_API int64_t lz_tree_desc_bytes(void);
 
 /* SoA batch -> packed records; packed records -> float32[B,11,6,6] model input (src/neural_network.py:15-65) */
 /* Wave-batched leaves: the legacy search of src/mcts.py:280-497 (`batch_K` distinct leaves per tree and wave, no

@@ -75,6 +75,12 @@ __global__ __launch_bounds__(kBlock) void tree_begin_kernel(Tree t) {
 }
 
 
+// every slot of the position index -> -1 (fresh trees)
+__global__ __launch_bounds__(kBlock) void pos_clear_kernel(int* __restrict__ tab, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * kBlock)
+        reinterpret_cast<int4*>(tab)[i] = make_int4(-1, -1, -1, -1);
+}
+
 __global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t) {
     const int g = wave_game();
     if (g >= t.B) return;
@@ -520,6 +526,23 @@ constexpr int kMarkWordsMax = 1024;        // four waves per workgroup: node_cap
 constexpr int kMarkWordsBig = 8192;        // ONE wave per workgroup (round 6): node_cap <= 524 288 (96 KB) -- the arenas of a
                                            // long single-game search (MCTSCore with tens of thousands of simulations)
 
+// game g's position index after an advance: cleared, then the kept nodes 1 .. kept-1 inserted (lanes in parallel; which
+// slot a node lands in depends on the order of the CAS, not which nodes are found: any node holding a state is a valid
+// source, twins hold bit-identical priors and values)
+__device__ __forceinline__ void pos_rebuild(const Tree& t, int g, int lane, int kept) {
+    if (t.pos_index == nullptr) return;
+    int* tab = t.pos_index + (size_t)g * t.pos_slots;
+    for (int i = lane; i < t.pos_slots / 4; i += kWave) reinterpret_cast<int4*>(tab)[i] = make_int4(-1, -1, -1, -1);
+    __threadfence_block();
+    const uint32_t mask = (uint32_t)t.pos_slots - 1u;
+    const Node* nodes = t.nodes + (size_t)g * t.node_cap;
+    for (int id = 1 + lane; id < kept; id += kWave) {
+        const uint32_t h = pos_hash(load_state(&nodes[id].state));
+        for (int p = 0; p < kWave; ++p)
+            if (atomicCAS(&tab[(h + (uint32_t)p) & mask], -1, id) == -1) break;
+    }
+}
+
 template <int WPB>
 __global__ __launch_bounds__(WPB * kWave) void tree_advance_kernel(Tree t, const int* __restrict__ played_action,
                                                               const uint8_t* __restrict__ reset, int reserve_nodes,
@@ -626,6 +649,7 @@ __global__ __launch_bounds__(WPB * kWave) void tree_advance_kernel(Tree t, const
     }
     if (c <= 0) {
         release_chunks_wave(t, g, 0, lane);
+        pos_rebuild(t, g, lane, 0);
         if (lane == 0) begin_game(t, g, /*release=*/false);
         return;
     }
@@ -642,15 +666,18 @@ __global__ __launch_bounds__(WPB * kWave) void tree_advance_kernel(Tree t, const
     for (int w0 = 0; w0 < words; w0 += 2) {
         // a node record as three 16-byte parts: the packed state (2 parts), then {edge_begin, nedges, parent, old_begin}
         u32x4 na[2], nb2[2], nc2[2];
+        float nv[2];                                             // the node's raw network value (position index)
         uint64_t ms[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int w = w0 + u;
             ms[u] = w < words ? mark[w] : 0ull;
             na[u] = nb2[u] = nc2[u] = (u32x4){0u, 0u, 0u, 0u};
+            nv[u] = 0.f;
             if ((ms[u] >> lane) & 1ull) {
                 const u32x4* q = reinterpret_cast<const u32x4*>(&nodes[w * kWave + lane]);
                 na[u] = q[0]; nb2[u] = q[1]; nc2[u] = q[2];
+                if (t.node_value != nullptr) nv[u] = t.node_value[(size_t)g * t.node_cap + w * kWave + lane];
             }
         }
 #pragma unroll
@@ -684,8 +711,10 @@ __global__ __launch_bounds__(WPB * kWave) void tree_advance_kernel(Tree t, const
                 meta.w = meta.x;                                 // old_begin = edge_begin
                 meta.x = (uint32_t)begin;
                 meta.z = id == c ? 0xFFFFFFFFu : (uint32_t)rank_of((int)meta.z);
-                u32x4* q = reinterpret_cast<u32x4*>(&nodes[nprefix[w] + __popcll(m & lt)]);
+                const int to = nprefix[w] + __popcll(m & lt);
+                u32x4* q = reinterpret_cast<u32x4*>(&nodes[to]);
                 q[0] = na[u]; q[1] = nb2[u]; q[2] = meta;
+                if (t.node_value != nullptr) t.node_value[(size_t)g * t.node_cap + to] = nv[u];
             }
         }
     }
@@ -696,6 +725,7 @@ __global__ __launch_bounds__(WPB * kWave) void tree_advance_kernel(Tree t, const
         // every run was laid out by the same greedy rule (header comment).  Should a future change of the allocation rule
         // break that, the kept subtree is DROPPED and counted instead of being packed over live records
         release_chunks_wave(t, g, 0, lane);
+        pos_rebuild(t, g, lane, 0);
         if (lane == 0) {
             if (dropped != nullptr) atomicAdd(dropped, 1);
             begin_game(t, g, /*release=*/false);
@@ -774,6 +804,7 @@ __global__ __launch_bounds__(WPB * kWave) void tree_advance_kernel(Tree t, const
     }
     if (ticks != nullptr && lane == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); ticks[(size_t)g * 8 + 3] = (long long)wall_clock64(); }
     release_chunks_wave(t, g, ci + 1, lane);
+    pos_rebuild(t, g, lane, kept_nodes);
     if (lane == 0) {
         t.n_nodes[g] = kept_nodes;
         t.n_edges[g] = cbase + off;          // off == chunk: "no open chunk" (the next run takes a new one)
@@ -1226,14 +1257,18 @@ int lz_packed_to_model_input(const void* packed, int64_t B, float* out, void* st
 int lz_tree_begin(const LzTreeDesc* d, void* stream) {
     if (!tree_ok(d)) return LZ_ERR_ARG;
     if (d->num_games == 0) return LZ_OK;
-    hipLaunchKernelGGL(tree_begin_kernel, dim3(gt(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d));
+    const Tree t = make_tree(d);
+    if (t.pos_index != nullptr)
+        hipLaunchKernelGGL(pos_clear_kernel, dim3(1024), dim3(kBlock), 0, as_stream(stream), t.pos_index,
+                           (int64_t)t.B * t.pos_slots);
+    hipLaunchKernelGGL(tree_begin_kernel, dim3(gt(d->num_games)), dim3(kBlock), 0, as_stream(stream), t);
     return st();
 }
 
 int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (!tree_ok(d)) return LZ_ERR_ARG;
     if (d->num_games == 0) return LZ_OK;
-    hipLaunchKernelGGL(tree_select_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d));
+    hipLaunchKernelGGL(tree_select_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), no_share(make_tree(d)));
     return st();
 }
 
@@ -1243,7 +1278,7 @@ int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const flo
     if (!tree_ok(d) || !values) return LZ_ERR_ARG;
     if (!priors220 && (!lp1 || !lp2 || !lpmc)) return LZ_ERR_ARG;
     if (d->num_games == 0) return LZ_OK;
-    const Tree t = make_tree(d);
+    const Tree t = no_share(make_tree(d));
     if (is_root)
         hipLaunchKernelGGL(tree_expand_kernel<true>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
                            lpmc, priors220, values, noise, (int)noise_stride, epsilon, -1);
@@ -1330,7 +1365,10 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
     if (rc) return rc;
     (void)planes;   // the network kernel stages its input straight from the 32-byte packed leaf states
-    const Tree t = make_tree(d);
+    // Shared leaves (position index) only in the one-wave step, whose evaluator is this network: its outputs are a
+    // function of the packed state alone.  The step-by-step entry points (external evaluators) and the two-wave split
+    // step (where the descent runs beside the expansion that inserts into the index) keep the index but do not look it up.
+    const Tree t = split_step(B) ? no_share(make_tree(d)) : make_tree(d);
     if (t.live_count != nullptr) {
         // compact evaluation lists: simulation s evaluates live_count[s] leaves (see LzTreeDesc.live_*)
         if (d->live_count_cap < sims + 2) return LZ_ERR_ARG;
@@ -1402,6 +1440,8 @@ LZ_API int lz_exp_tree_stamps(unsigned long long* out32, int reset) {
     return LZ_OK;
 }
 #endif
+
+int64_t lz_tree_desc_bytes(void) { return (int64_t)sizeof(LzTreeDesc); }
 
 int lz_root_prepare(const void* root_states, int64_t B, const float* lp1, const float* lp2, const float* lpmc,
                     const float* noise, float epsilon, int64_t* legal_index_mat, float* priors_mat,

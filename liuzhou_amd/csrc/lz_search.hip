@@ -199,7 +199,7 @@ int lz_tree_search_persistent(const LzTreeDesc* d, const LzNetDesc* net, int64_t
     const unsigned grid = (unsigned)((B + 8 - 1) / 8);
     (void)lz_prof_mark_begin(stream);
     hipLaunchKernelGGL((tree_search_persistent_kernel<64, 8, 4>), dim3(grid), dim3(K::THREADS), K::LDS_BYTES, stm, P,
-                       make_tree(d), a, lp1, lp2, lpmc, values);
+                       no_share(make_tree(d)), a, lp1, lp2, lpmc, values);
     (void)lz_prof_mark_end(stream, B * (sims + 1));
     return st();
 }

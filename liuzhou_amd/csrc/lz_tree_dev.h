@@ -21,7 +21,9 @@ constexpr int kWavesPerBlock = 4;
 constexpr int kMaxChildren = 72;
 
 // kLeafReusedRoot: the root survived an advance (a21) -- no evaluation needed, only the fresh noise mix
-enum LeafKind : int { kLeafInactive = 0, kLeafExpand = 1, kLeafTerminal = 2, kLeafReusedRoot = 3 };
+// kLeafShared: a leaf whose position another node of the same tree already holds (position index, LzTreeDesc.pos_*): it
+// takes that node's priors and network value instead of an evaluation of its own
+enum LeafKind : int { kLeafInactive = 0, kLeafExpand = 1, kLeafTerminal = 2, kLeafReusedRoot = 3, kLeafShared = 4 };
 // edge info bits
 constexpr uint8_t kInfoWhite = 1;       // child mover is white
 constexpr uint8_t kInfoTerminal = 2;    // child is terminal (game over, or found to have no legal move)
@@ -79,6 +81,12 @@ struct Tree {
     // step by an ordered one-workgroup scan (tree_live_scan_kernel), so that a network launch runs
     // ceil(live / samples-per-pass) passes instead of one per slot of the batch
     Packed* live_state; int* live_row; unsigned long long* live_count;
+    // optional position index (LzTreeDesc.pos_*): per game an open-addressed table [pos_slots] of node indices (-1: empty)
+    // over the nodes expanded from a network result, the raw value of every node (node_value [B*node_cap]), the source
+    // node of a shared leaf (leaf_src [B]) and the per-game count of shared leaves.  Maintained whenever the arrays are
+    // there; `share` (LZ_TREE_SHARE, on by default) turns the look-ups of the descent on.
+    int* pos_index; float* node_value; int* leaf_src; int* share_count;
+    int pos_slots, share;
 };
 
 // Edge / node records are read with plain (L1 + L2 cached, normal retention) 16-byte loads.  This is safe next to the
@@ -105,6 +113,41 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_game() {
     return blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
+// ---- position index: one wave per game owns its table, so no atomics except in the parallel rebuild of lz_tree_advance.
+// Linear probing over a window of 64 slots (one 256-byte load): a key lives in the window of its hash, before the
+// window's first empty slot; a window without room means the position is not indexed (plain evaluation, never a failure).
+__device__ __forceinline__ bool same_state(const Packed& a, const Packed& b) {
+    return a.w0 == b.w0 && a.w1 == b.w1 && a.w2 == b.w2 && a.w3 == b.w3;
+}
+__device__ __forceinline__ uint32_t pos_hash(const Packed& s) {
+    uint64_t h = s.w0 * 0x9E3779B97F4A7C15ull;
+    h = (h ^ (h >> 29) ^ s.w1) * 0xBF58476D1CE4E5B9ull;
+    h = (h ^ (h >> 31) ^ s.w2) * 0x94D049BB133111EBull;
+    h = (h ^ (h >> 27) ^ s.w3) * 0x9E3779B97F4A7C15ull;
+    return (uint32_t)(h >> 32);
+}
+// The window of `s` in game g's table: the slot entry of this lane (entries outside [1, nn) count as empty -- node 0, the
+// root, is never a source: its priors carry the noise mix) and the first empty lane (kWave: none).
+struct PosWindow { int entry; int first_empty; uint32_t base; };
+__device__ __forceinline__ PosWindow pos_window(const Tree& t, int g, const Packed& s, int nn, int lane) {
+    const int* tab = t.pos_index + (size_t)g * t.pos_slots;
+    const uint32_t mask = (uint32_t)t.pos_slots - 1u;
+    PosWindow w;
+    w.base = pos_hash(s) & mask;
+    w.entry = tab[(w.base + (uint32_t)lane) & mask];
+    const uint64_t em = __ballot(w.entry < 1 || w.entry >= nn);
+    w.first_empty = em ? __ffsll((unsigned long long)em) - 1 : kWave;
+    return w;
+}
+// node of game g that holds state s (>= 1), or -1
+__device__ __forceinline__ int pos_find(const Tree& t, int g, const Packed& s, int nn, int lane) {
+    const PosWindow w = pos_window(t, g, s, nn, lane);
+    bool hit = false;
+    if (lane < w.first_empty) hit = same_state(load_state(&t.nodes[(size_t)g * t.node_cap + w.entry].state), s);
+    const uint64_t hm = __ballot(hit);
+    return hm ? lzw::lane_bcast(w.entry, __ffsll((unsigned long long)hm) - 1) : -1;
+}
+
 #ifdef LZ_EXP_TREE_STAMPS   /* timing experiment (scripts/exp_tree_stamps.py): absolute clocks summed per stamp by ONE game's wave */
 __device__ unsigned long long g_tree_stamps[32];
 #define LZ_TSTAMP_ON(g) ((g) == 5)
@@ -375,19 +418,27 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
         if (depth >= t.path_cap - 1) break;
     }
     LZ_TSTAMP(g, 8)                                            // descent done
+    Packed leaf_packed{};
+    int src = -1;
+    if (kind == kLeafExpand) {                                 // wave-uniform: every lane derives the leaf state
+        State leaf = unpack(node_state);
+        int kd, p, q2, ex;
+        index_to_code(leaf.phase, leaf_action, kd, p, q2, ex);
+        apply_legal(leaf, kd, p, q2);                       // an action this engine enumerated: no re-validation
+        leaf_packed = pack(leaf);
+        if (t.share) {                                         // a position this tree already evaluated: no network row
+            src = pos_find(t, g, leaf_packed, t.n_nodes[g], lane);
+            if (src > 0) kind = kLeafShared;
+        }
+    }
     if (lane == 0) {
         t.path_len[g] = depth;
         t.leaf_kind[g] = kind;
         t.leaf_value[g] = term_value;
         t.leaf_edge[g] = leaf_edge;
         t.leaf_parent[g] = node;
-        if (kind == kLeafExpand) {
-            State leaf = unpack(node_state);
-            int kd, p, q2, ex;
-            index_to_code(leaf.phase, leaf_action, kd, p, q2, ex);
-            apply_legal(leaf, kd, p, q2);                   // an action this engine enumerated: no re-validation
-            t.leaf_state[g] = pack(leaf);
-        }
+        if (kind == kLeafExpand || kind == kLeafShared) t.leaf_state[g] = leaf_packed;
+        if (kind == kLeafShared) t.leaf_src[g] = src;
     }
     LZ_TSTAMP(g, 9)                                            // leaf state written
 }
@@ -442,7 +493,19 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
     }
     nn_ld = t.n_nodes[g];
     ne_ld = t.n_edges[g];
-    value_ld = values[g];
+    const bool shared = !IS_ROOT && ROLE == 0 && kind == kLeafShared;
+    value_ld = shared ? 0.f : values[g];
+    // position index: the window a new node of this leaf goes into (speculative: most leaves are expanded)
+    const bool indexed = !IS_ROOT && ROLE != 2 && t.pos_index != nullptr;
+    PosWindow pw{0, kWave, 0u};
+    if (indexed) pw = pos_window(t, g, leaf_packed, nn_ld, lane);
+    // a shared leaf: the source node's raw value and its edge run (same state => same legal actions in the same order)
+    int src_begin = 0;
+    if (shared) {
+        const int src = t.leaf_src[g];
+        value_ld = t.node_value[(size_t)g * t.node_cap + src];
+        src_begin = nodes[src].edge_begin;
+    }
     if (root_after != nullptr) *root_after = root;
     if (ROLE == 1) {                                           // the partner may now overwrite the leaf record (next leaf)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -496,7 +559,8 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
     if (kind == kLeafTerminal) {
         backup_value = (double)leaf_value_ld;
     } else {
-        if (ROLE != 2 && t.eval_count != nullptr && lane == 0) t.eval_count[g] += 1;     // this game's wave is the only writer
+        if (shared) { if (t.share_count != nullptr && lane == 0) t.share_count[g] += 1; }
+        else if (ROLE != 2 && t.eval_count != nullptr && lane == 0) t.eval_count[g] += 1;     // this game's wave is the only writer
         const State s = unpack(leaf_packed);
         const Legal L = legal_actions(s, /*fallback_forced=*/0);     // python semantics (move_generator.py:24-70)
         const int n = legal_count(L);
@@ -518,7 +582,7 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
             // gather per-lane logits / priors of the legal actions in ascending index order
             float h1 = 0.f, h2 = 0.f, hm = 0.f;
             const bool heads = priors220 == nullptr;
-            if (heads && lane < kCells) {
+            if (heads && lane < kCells && !shared) {
                 h1 = lp1[(size_t)g * 36 + lane]; h2 = lp2[(size_t)g * 36 + lane]; hm = lpm[(size_t)g * 36 + lane];
                 if (tracing) {
                     float* th = t.trace_heads + tslot * 108;
@@ -594,8 +658,17 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
             // renormalise with a sequential fp32 sum in ascending action order (== the oracle's order): scalar loop
             // of v_readlane + add, no further LDS round trip
             float psum = 0.f;
+            if (shared) {                                      // the source's priors, bit for bit
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const int k = r * kWave + lane;
+                    cval[r] = k < n ? edges[(size_t)(src_begin + k)].P : 0.f;
+                }
+                psum = 1.f;
+            } else {
 #pragma unroll 4
-            for (int k = 0; k < n; ++k) psum += lzw::lane_bcast(k < kWave ? cval[0] : cval[1], k & 63);
+                for (int k = 0; k < n; ++k) psum += lzw::lane_bcast(k < kWave ? cval[0] : cval[1], k & 63);
+            }
             const bool bad = !(psum > 0.f) || !isfinite(psum);
             LZ_TSTAMP(g, 3)                                    // compaction + sequential renormalisation sum
             // node + edge allocation: the node from the game's bump counter, the run of n edges from the game's open
@@ -614,6 +687,9 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
                         in.child = node_id; in.cbegin = e0; in.cn = (uint8_t)n;
                         nodes[node_id].state = leaf_packed;
                         nodes[node_id].parent = leaf_parent;
+                        if (t.node_value != nullptr) t.node_value[(size_t)g * t.node_cap + node_id] = value_ld;
+                        if (indexed && !shared && pw.first_empty < kWave)      // full window: not indexed
+                            t.pos_index[(size_t)g * t.pos_slots + ((pw.base + (uint32_t)pw.first_empty) & ((uint32_t)t.pos_slots - 1u))] = node_id;
                     }
                     nodes[node_id].edge_begin = e0;
                     nodes[node_id].nedges = n;
@@ -643,7 +719,7 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
                 }
                 Edge rec;
                 rec.W = 0.0;
-                rec.P = bad ? (1.0f / (float)n) : ((r == 0 ? cval[0] : cval[1]) / psum);
+                rec.P = shared ? (r == 0 ? cval[0] : cval[1]) : bad ? (1.0f / (float)n) : ((r == 0 ? cval[0] : cval[1]) / psum);
                 rec.n_info = (uint32_t)info << 24;
                 rec.child = -1;
                 rec.cbegin = 0;
@@ -720,8 +796,18 @@ Tree make_tree(const LzTreeDesc* d) {
     t.live_state = live ? reinterpret_cast<Packed*>(d->live_state) : nullptr;
     t.live_row = live ? d->live_row : nullptr;
     t.live_count = live ? reinterpret_cast<unsigned long long*>(d->live_count) : nullptr;
+    const bool pos = d->pos_index && d->node_value && d->leaf_src && d->pos_slots >= kWave &&
+                     (d->pos_slots & (d->pos_slots - 1)) == 0;
+    t.pos_index = pos ? d->pos_index : nullptr;
+    t.node_value = pos ? d->node_value : nullptr;
+    t.leaf_src = pos ? d->leaf_src : nullptr;
+    t.pos_slots = pos ? (int)d->pos_slots : 0;
+    t.share_count = d->share_count;
+    // look-ups ON unless LZ_TREE_SHARE=0 (A/B runs on one build); off while a parity trace records what the network gave
+    { const char* e = getenv("LZ_TREE_SHARE"); t.share = pos && !tr && !(e && e[0] == '0') ? 1 : 0; }
     return t;
 }
+inline Tree no_share(Tree t) { t.share = 0; return t; }     // paths that keep the index but do not look it up
 bool tree_ok(const LzTreeDesc* d) {
     return d && d->num_games >= 0 && d->node_cap >= 2 && d->path_cap >= 3 &&
            d->edge_chunk >= 128 && (d->edge_chunk & (d->edge_chunk - 1)) == 0 && d->chunk_cap >= 1 &&

@@ -46,7 +46,8 @@ class LzTreeDesc(C.Structure):
                [("trace_cap", C.c_int64), ("eval_count", C.c_void_p)] + \
                [(n, C.c_void_p) for n in ("chunk_list", "n_chunks", "free_chunks", "pool_top", "pool_stats")] + \
                [("pool_chunks", C.c_int64)] + \
-               [(n, C.c_void_p) for n in ("live_state", "live_row", "live_count")] + [("live_count_cap", C.c_int64)]
+               [(n, C.c_void_p) for n in ("live_state", "live_row", "live_count")] + [("live_count_cap", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("pos_index", "node_value", "leaf_src", "share_count")] + [("pos_slots", C.c_int64)]
 
 
 class LzTreeWaveDesc(C.Structure):
@@ -69,6 +70,27 @@ MAX_NODE_CAP = 524288          # lz_tree_advance marks a game's nodes in LDS: 8 
 AUTO_NODE_CAP = 65536          # arenas sized automatically (auto_reuse_factor) stay within the four-wave form
 PATH_CAP = 192                 # a game lasts <= 144 plies (game_state.py:87-89), so no descent is deeper than that
 REUSE_FACTOR_CAP = 40.0
+POS_SLOTS_MAX = 8192           # position index: slots per game (a window that finds no room just leaves a node unindexed)
+SPLIT_MAX_GAMES = 8192         # lz_engine.hip kSplitMaxGames: larger launches take the one-wave tree step
+
+
+def pos_slots_for(node_cap: int) -> int:
+    """Slots of a game's position index: a power of two >= 2 x node_cap (load <= 1/2), 64 .. POS_SLOTS_MAX."""
+    n = 64
+    while n < 2 * int(node_cap) and n < POS_SLOTS_MAX:
+        n *= 2
+    return n
+
+
+def shares_leaves(num_games: int) -> bool:
+    """Does the fused search of an engine of `num_games` games look transposed leaves up in its position index?  Only
+    the one-wave tree step does (LZ_TREE_SHARE=0: never); mirrors lz_engine.hip split_step."""
+    if os.environ.get("LZ_TREE_SHARE", "1").strip().startswith("0"):
+        return False
+    if os.environ.get("LZ_TREE_SPLIT", "").strip().startswith("0"):
+        return True
+    limit = int(os.environ.get("LZ_TREE_SPLIT_MAX", "0") or 0) or SPLIT_MAX_GAMES
+    return int(num_games) > limit
 
 
 def auto_reuse_factor(num_games: int, sims: int, device, memory_fraction: float = 0.10, cap: float = REUSE_FACTOR_CAP) -> float:
@@ -166,10 +188,17 @@ class TreeEngine:
             # [0] expansions refused because the pool was empty (0 in a correctly sized engine), [1] fewest free chunks seen
             # + [2] fresh roots that still have to take the chunk of their first expansion (reserved for them)
             "pool_stats": torch.tensor([0, self.pool_chunks, 0], dtype=torch.int32, device=dev),
+            # position index (LzTreeDesc.pos_*): table of node indices per game, raw value per node, source of a shared leaf
+            "pos_index": torch.full((B * pos_slots_for(self.node_cap),), -1, dtype=torch.int32, device=dev),
+            "node_value": z((B * self.node_cap,), torch.float32), "leaf_src": z((B,), torch.int32),
         }
         d = LzTreeDesc()
         d.num_games, d.node_cap, d.edge_chunk, d.path_cap = B, self.node_cap, self.edge_chunk, self.path_cap
         d.chunk_cap, d.pool_chunks = self.chunk_cap, self.pool_chunks
+        d.pos_slots = pos_slots_for(self.node_cap)
+        if int(L.lib().lz_tree_desc_bytes()) != C.sizeof(LzTreeDesc):
+            raise RuntimeError(f"LzTreeDesc layout mismatch: library {int(L.lib().lz_tree_desc_bytes())} B, "
+                               f"Python {C.sizeof(LzTreeDesc)} B")
         d.exploration_weight = float(exploration_weight)
         for name, t in self.buf.items():
             setattr(d, name, t.data_ptr())
@@ -214,6 +243,8 @@ class TreeEngine:
         self.reuse_dropped = z((2,), torch.int32)      # [0] kept subtrees dropped whole (defensive), [1] pruned to fit
         self.eval_count = z((B,), torch.int32)          # evaluations the games' expand steps consumed (LzTreeDesc.eval_count)
         self.desc.eval_count = self.eval_count.data_ptr()
+        self.share_count = z((B,), torch.int32)         # leaves that took a transposed twin's evaluation (LzTreeDesc.share_count)
+        self.desc.share_count = self.share_count.data_ptr()
         self.compact_evals = bool(compact_evals) and self.batch_k == 1
         self.live_total = z((1,), torch.int64)          # compact_evals: evaluations launched so far (sum of the per-simulation counts)
         if self.compact_evals:
@@ -525,9 +556,11 @@ class PortableTreeMCTS:
         # asked for explicitly: every search uses the lists.  Chosen automatically: the engine can do both and launches
         # every slot unless a search is told otherwise (`compact=` of search_batch: the runner's hint that the wave is
         # draining) -- while nearly all games are live the lists shorten nothing and cost a scan kernel per simulation
+        # (a search that shares transposed leaves takes them out of the lists, so it uses the lists throughout)
         self.compact_default = compact_evals is True
         if compact_evals is None:
             compact_evals = self.fused and int(num_games) >= 2 * samples_per_launch_pass(net)
+            self.compact_default = compact_evals and self.batch_k == 1 and shares_leaves(num_games)
         self.engine = TreeEngine(num_games, num_simulations, device, exploration_weight,
                                  reuse_factor=float(reuse_factor) if self.reuse_tree else 0.0, batch_k=self.batch_k,
                                  compact_evals=bool(compact_evals) and self.fused and self.batch_k == 1)
@@ -651,10 +684,10 @@ class PortableTreeMCTS:
                 # after a fresh one
                 # (an engine with compact lists warms up both launch forms: the other one may be captured later inside a
                 #  continued search, which cannot be preceded by a warm-up of its own)
-                counted = (e.live_total.clone(), e.eval_count.clone())     # warm-ups are not searches: not counted
+                counted = (e.live_total.clone(), e.eval_count.clone(), e.share_count.clone())   # warm-ups are not searches
                 for form in ((lists, not lists) if e.compact_evals else (lists,)):
                     e.search(self.net, min(self.sims, 2), noise, self.eps, False, compact=form)
-                e.live_total.copy_(counted[0]); e.eval_count.copy_(counted[1])
+                e.live_total.copy_(counted[0]); e.eval_count.copy_(counted[1]); e.share_count.copy_(counted[2])
             torch.cuda.synchronize(e.device)
             try:
                 g = torch.cuda.CUDAGraph()
@@ -737,6 +770,7 @@ class PortableTreeMCTS:
         self._root_evals = 0
         self.extra_rounds = 0
         self.engine.eval_count.zero_()
+        self.engine.share_count.zero_()
         self.engine.live_total.zero_()
         self.engine.reuse_dropped.zero_()
         # refused expansions / fewest free chunks are per run too (a cached engine must not report an earlier run's)
@@ -759,6 +793,7 @@ class PortableTreeMCTS:
         self._root_evals = 0
         self.extra_rounds = 0
         self.engine.eval_count.zero_()
+        self.engine.share_count.zero_()
         self.engine.live_total.zero_()
         self.get_timing(reset=True)
         if self.batch_k > 1:
