@@ -440,6 +440,20 @@ typedef struct LzTreeDesc {
     int32_t* leaf_src;             /* [B] source node of a shared leaf (select -> expand hand-off) */
     int32_t* share_count;          /* optional [B]: += 1 for every shared leaf a game's expand step took (NULL: off) */
     int64_t  pos_slots;            /* slots per game: a power of two >= 64 */
+    /* Optional symmetric leaf evaluation (csrc/lz_symmetry.h; sym_mode 0 = off, every array unused): each evaluation of
+     * game g is of sigma_k(leaf) -- leaf_state holds the transformed record, leaf_sym[g] = k -- and the expand step
+     * builds the node from the true leaf, reading the heads as head[sigma_k(p)] for cell p and priors220 through the
+     * action permutation.  sym_mode 1: k = sym_fixed for every evaluation; 2: k from Philox keyed by sym_seed, the
+     * game's key sym_game[g], its ply sym_ply[g], a per-run salt sym_salt[g] (device memory, read at every launch: not
+     * frozen into a captured graph) and the hash of the true leaf state -- the same id in every launch form.  Shared
+     * leaves are not evaluated: k = 0. */
+    int32_t* leaf_sym;             /* [B] */
+    int32_t* trace_sym;            /* optional [trace_cap][B]: the k of every traced step (with trace_*) */
+    const int32_t* sym_salt;       /* [B] (mode 2) */
+    const int64_t* sym_game;       /* [B] (mode 2) */
+    const int64_t* sym_ply;        /* [B] (mode 2) */
+    uint64_t sym_seed;
+    int32_t  sym_mode, sym_fixed;
 } LzTreeDesc;
 LZ_API int64_t lz_tree_desc_bytes(void);
 
@@ -647,6 +661,34 @@ LZ_API int lz_pack_trajectory_rows(const float* state_tensors, const uint8_t* le
 LZ_API int lz_unpack_trajectory_rows(const void* records, int64_t rows, float* state_tensors, uint8_t* legal_masks,
                                      float* policy_targets, float* value_targets, float* soft_value_targets,
                                      void* stream);
+
+/* ---- board symmetries (the dihedral group D4 of the 6x6 square; csrc/lz_symmetry.h) --------------------------------
+ * Element ids 0..7: identity, rotate 90 (r,c)->(c,5-r), rotate 180, rotate 270 (r,c)->(5-c,r), flip left-right
+ * (r,c)->(r,5-c), flip up-down (r,c)->(5-r,c), transpose (r,c)->(c,r), anti-transpose (r,c)->(5-c,5-r).  A transformed
+ * row holds at cell sigma(x) what the source held at x, and at action P_sigma(a) what it held at a (placement and
+ * selection cells mapped, movement 36+4*from+d -> 36+4*sigma(from)+sigma_d(d), indices 216..219 kept).
+ * `sym` is int8 (sym_width 1) or int32 (sym_width 4).  A row whose id is outside 0..7, or whose source index is
+ * outside [0, n_src), is zeroed (gather_samples) or left untouched (the two transforms).  Both builds export all four entry points (the host build for CPU tensors). */
+
+/* The tables, written to HOST memory in both builds (no launch): cells int32[8,36], actions int32[8,220],
+ * inverse int32[8], compose int32[8,8] with compose[a][b] = sigma_a o sigma_b ("b first"), directions int32[8,4]. */
+LZ_API int lz_symmetry_tables(int32_t* cells, int32_t* actions, int32_t* inverse, int32_t* compose, int32_t* directions);
+
+/* Training rows: row j of each output = sigma_{sym[j]} of source row idx[j] (idx NULL: row j), in one pass over
+ * planes float32[n_src,11,36] (a spatial permutation of every plane), masks uint8[n_src,220] and policy
+ * float32[n_src,220] (exact bit copies).  masks / policy may be NULL together with their outputs.  One wave per row. */
+LZ_API int lz_symmetry_gather_samples(const float* planes, const uint8_t* masks, const float* policy, int64_t n_src,
+                                      const int64_t* idx, const void* sym, int32_t sym_width, float* out_planes,
+                                      uint8_t* out_masks, float* out_policy, int64_t m, void* stream);
+
+/* State batch: board and marks permuted, every scalar field copied.  `in` and `out` must not overlap. */
+LZ_API int lz_symmetry_transform_states(const LzStateSoA* in, const void* sym, int32_t sym_width,
+                                        const LzStateSoA* out, int64_t batch, void* stream);
+
+/* Packed 32-byte records (csrc/lz_rules.h:pack): the four boards permuted, the metadata bits of word 0 above bit 35
+ * kept.  The device build runs the wave function of the tree search's symmetric leaf evaluation. */
+LZ_API int lz_symmetry_transform_packed(const int64_t* in /*[B,4]*/, const void* sym, int32_t sym_width,
+                                        int64_t* out /*[B,4]*/, int64_t batch, void* stream);
 
 #ifdef __cplusplus
 }

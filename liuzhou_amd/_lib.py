@@ -105,7 +105,9 @@ _host: Optional[C.CDLL] = None
 HOST_SYMBOLS = ("lz_version", "lz_status_string", "lz_encode_actions_fast", "lz_batch_apply_moves",
                 "lz_batch_apply_moves_inplace", "lz_states_to_model_input", "lz_project_policy_logits_fast",
                 "lz_root_pack_rows", "lz_root_pack_plan", "lz_root_pack_fill", "lz_root_puct_allocate_visits",
-                "lz_root_finalize_from_visits", "lz_self_play_step_inplace", "lz_finalize_trajectory_inplace")
+                "lz_root_finalize_from_visits", "lz_self_play_step_inplace", "lz_finalize_trajectory_inplace",
+                "lz_symmetry_tables", "lz_symmetry_gather_samples", "lz_symmetry_transform_states",
+                "lz_symmetry_transform_packed")
 _STATUS = {0: "ok", -1: "invalid argument", -2: "unsupported dimensions", -3: "kernel launch failed",
            -4: "misaligned pointer", -5: "illegal action for the state"}
 

@@ -8,7 +8,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "lz_rng.h"
 #include "lz_soa.h"
+#include "lz_symmetry.h"
 #include "lz_wave.h"
 
 using namespace lz;
@@ -87,6 +89,9 @@ struct Tree {
     // there; `share` (LZ_TREE_SHARE, on by default) turns the look-ups of the descent on.
     int* pos_index; float* node_value; int* leaf_src; int* share_count;
     int pos_slots, share;
+    // optional symmetric leaf evaluation (LzTreeDesc.leaf_sym ..; sym_mode 0: off)
+    int* leaf_sym; int* trace_sym; const int* sym_salt; const int64_t* sym_game; const int64_t* sym_ply;
+    uint64_t sym_seed; int sym_mode, sym_fixed;
 };
 
 // Edge / node records are read with plain (L1 + L2 cached, normal retention) 16-byte loads.  This is safe next to the
@@ -165,6 +170,17 @@ __device__ unsigned long long g_tree_stamps[32];
 #define LZ_TSTAMP_ARG
 #define LZ_TSTAMP_PASS
 #endif
+
+// element under which game g evaluates `leaf` (the true state): a pure function of device memory and of the leaf, so every
+// lane computes the same value and every launch form (one-wave / split step, dense / list, graph / direct) the same id
+constexpr uint32_t kPurposeSymmetry = 3;
+__device__ __forceinline__ int leaf_sym_for(const Tree& t, int g, const Packed& leaf) {
+    if (t.sym_mode == 1) return t.sym_fixed & 7;
+    const uint64_t game = (uint64_t)t.sym_game[g];
+    const lzrng::U4 c = {(uint32_t)game, (uint32_t)(game >> 32) ^ (uint32_t)t.sym_salt[g],
+                         (uint32_t)t.sym_ply[g] ^ (kPurposeSymmetry << 30), pos_hash(leaf)};
+    return (int)(lzrng::philox4x32_10(c, (uint32_t)t.sym_seed, (uint32_t)(t.sym_seed >> 32)).x >> 29);
+}
 
 __device__ __forceinline__ double terminal_value_for_mover(const State& s) {   // portable_mcts.py:141-147
     const int st = game_status(s);
@@ -248,6 +264,11 @@ __device__ __forceinline__ void begin_game(const Tree& t, int g, bool release = 
     if (pending != was_pending) atomicAdd(t.pool_stats + 2, pending ? 1 : -1);
     t.leaf_state[g] = rs;                                  // the root is the first pending evaluation
     t.leaf_value[g] = 0.f;
+    if (t.sym_mode != 0) {                                 // symmetric evaluation: the record the network reads is sigma_k(root)
+        const int k = pending ? leaf_sym_for(t, g, rs) : 0;
+        t.leaf_sym[g] = k;
+        if (k != 0) t.leaf_state[g] = sym_packed(k, rs);
+    }
 }
 
 // ---- select: one wave per game ---------------------------------------------------------------------------
@@ -431,6 +452,11 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
             if (src > 0) kind = kLeafShared;
         }
     }
+    int sym = 0;
+    if (t.sym_mode != 0 && kind == kLeafExpand) {            // symmetric evaluation: the network reads sigma_k(leaf)
+        sym = __builtin_amdgcn_readfirstlane(leaf_sym_for(t, g, leaf_packed));
+        leaf_packed = sym_packed_wave(sym, leaf_packed, lane);
+    }
     if (lane == 0) {
         t.path_len[g] = depth;
         t.leaf_kind[g] = kind;
@@ -439,6 +465,7 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
         t.leaf_parent[g] = node;
         if (kind == kLeafExpand || kind == kLeafShared) t.leaf_state[g] = leaf_packed;
         if (kind == kLeafShared) t.leaf_src[g] = src;
+        if (t.sym_mode != 0) t.leaf_sym[g] = sym;
     }
     LZ_TSTAMP(g, 9)                                            // leaf state written
 }
@@ -482,6 +509,8 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
     double root_w = 0.0;
     float leaf_value_ld = 0.f, value_ld = 0.f;
     Packed leaf_packed = t.leaf_state[g];
+    // symmetric evaluation: the evaluator saw sigma_k(leaf); the step works on the true leaf
+    const int sym = (t.sym_mode != 0 && kind == kLeafExpand) ? (__builtin_amdgcn_readfirstlane(t.leaf_sym[g]) & 7) : 0;
     if (!IS_ROOT) {
         root = load_root_info(t, g);
         plen_ld = t.path_len[g];
@@ -493,6 +522,8 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
     }
     nn_ld = t.n_nodes[g];
     ne_ld = t.n_edges[g];
+    const Packed eval_packed = leaf_packed;
+    if (sym != 0) leaf_packed = sym_packed_wave(sym_inverse(sym), eval_packed, lane);
     const bool shared = !IS_ROOT && ROLE == 0 && kind == kLeafShared;
     value_ld = shared ? 0.f : values[g];
     // position index: the window a new node of this leaf goes into (speculative: most leaves are expanded)
@@ -517,7 +548,10 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
     const bool tracing = ROLE != 2 && t.trace_kind != nullptr && step >= 0 && step < t.trace_cap;
     const size_t tslot = tracing ? (size_t)step * (size_t)t.B + (size_t)g : 0;
     if (tracing) {
-        if (lane == 0) { t.trace_kind[tslot] = kind; t.trace_leaf[tslot] = leaf_packed; t.trace_value[tslot] = value_ld; }
+        if (lane == 0) {
+            t.trace_kind[tslot] = kind; t.trace_leaf[tslot] = eval_packed; t.trace_value[tslot] = value_ld;
+            if (t.trace_sym != nullptr) t.trace_sym[tslot] = sym;
+        }
         for (int a = lane; a < 220; a += kWave) t.trace_priors[tslot * 220 + a] = 0.f;
     }
     if (kind == kLeafInactive) return;
@@ -583,10 +617,12 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
             float h1 = 0.f, h2 = 0.f, hm = 0.f;
             const bool heads = priors220 == nullptr;
             if (heads && lane < kCells && !shared) {
-                h1 = lp1[(size_t)g * 36 + lane]; h2 = lp2[(size_t)g * 36 + lane]; hm = lpm[(size_t)g * 36 + lane];
-                if (tracing) {
+                // cell p of the true leaf is cell sigma_k(p) of the evaluated record
+                const int hc = sym != 0 ? sym_cell(sym, lane) : lane;
+                h1 = lp1[(size_t)g * 36 + hc]; h2 = lp2[(size_t)g * 36 + hc]; hm = lpm[(size_t)g * 36 + hc];
+                if (tracing) {                                 // the rows as the evaluator wrote them
                     float* th = t.trace_heads + tslot * 108;
-                    th[lane] = h1; th[36 + lane] = h2; th[72 + lane] = hm;
+                    th[hc] = h1; th[36 + hc] = h2; th[72 + hc] = hm;
                 }
             }
             // Phase A, per 64 action indices (skipped when none of them is legal): legality, compact slot, logit.
@@ -613,7 +649,7 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
                     const float p1d = __shfl(h1, dest), p2f = __shfl(h2, from), p1c = __shfl(h1, cell), pmc = __shfl(hm, cell);
                     x = a < 36 ? p1c : a < 180 ? (p2f + p1d) : a < 216 ? pmc : 0.f;
                 } else {
-                    x = lg[it] ? priors220[(size_t)g * 220 + a] : 0.f;
+                    x = lg[it] ? priors220[(size_t)g * 220 + (sym != 0 ? (int)kSym.action[sym][a] : a)] : 0.f;
                 }
                 val[it] = x;
                 if (heads && lg[it]) mx = fmaxf(mx, x);
@@ -805,6 +841,16 @@ Tree make_tree(const LzTreeDesc* d) {
     t.share_count = d->share_count;
     // look-ups ON unless LZ_TREE_SHARE=0 (A/B runs on one build); off while a parity trace records what the network gave
     { const char* e = getenv("LZ_TREE_SHARE"); t.share = pos && !tr && !(e && e[0] == '0') ? 1 : 0; }
+    const bool sym = d->leaf_sym && ((d->sym_mode == 1 && d->sym_fixed >= 0 && d->sym_fixed < 8) ||
+                                     (d->sym_mode == 2 && d->sym_salt && d->sym_game && d->sym_ply));
+    t.sym_mode = sym ? d->sym_mode : 0;
+    t.sym_fixed = sym ? d->sym_fixed : 0;
+    t.leaf_sym = sym ? d->leaf_sym : nullptr;
+    t.trace_sym = sym && tr ? d->trace_sym : nullptr;
+    t.sym_salt = sym ? d->sym_salt : nullptr;
+    t.sym_game = sym ? d->sym_game : nullptr;
+    t.sym_ply = sym ? d->sym_ply : nullptr;
+    t.sym_seed = d->sym_seed;
     return t;
 }
 inline Tree no_share(Tree t) { t.share = 0; return t; }     // paths that keep the index but do not look it up

@@ -126,11 +126,12 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         search_backend: str = "cuda_root", portable_mcts_backend: str = "python",
                         portable_cpp_threads: int = 1, policy_target_temperature: Optional[float] = None,
                         policy_target_prior_pseudocount: float = 0.0, sample_moves: bool = True,
-                        worker_fn: Optional[Callable[..., Dict[str, Any]]] = None,
+                        eval_symmetry: Any = "none", worker_fn: Optional[Callable[..., Dict[str, Any]]] = None,
                         in_process: bool = False) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
-    `worker_fn` / `in_process` exist for tests (a stub worker, no process pool)."""
+    `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
+    "random" or a fixed id 0..7) reaches the workers only when it is not "none"."""
     if worker_fn is None:
         from .self_play_worker import run_self_play_worker as worker_fn
     shards = split_games(int(num_games), len(devices))
@@ -163,7 +164,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             policy_target_temperature=policy_target_temperature,
             policy_target_prior_pseudocount=float(policy_target_prior_pseudocount), sample_moves=bool(sample_moves),
             target_samples_per_shard=int(target_samples_per_shard), chunk_target_bytes=int(chunk_target_bytes),
-            chunk_output_dir=out_dir, chunk_file_prefix=f"{stem}.w{idx:02d}", chunk_file_ext=ext)
+            chunk_output_dir=out_dir, chunk_file_prefix=f"{stem}.w{idx:02d}", chunk_file_ext=ext,
+            **({} if eval_symmetry == "none" else {"eval_symmetry": eval_symmetry}))
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

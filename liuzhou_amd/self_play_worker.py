@@ -579,7 +579,13 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          chunk_file_ext: str = ".pt", sparse_ply: int = 1, sparse_top_k: int = 8,
                          search_backend: str = "cuda_root", portable_mcts_backend: str = "python",
                          portable_cpp_threads: int = 1, policy_target_temperature: Optional[float] = None,
-                         policy_target_prior_pseudocount: float = 0.0) -> Dict[str, Any]:
+                         policy_target_prior_pseudocount: float = 0.0, eval_symmetry="none") -> Dict[str, Any]:
+    """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS."""
+    from .tree_engine import parse_eval_symmetry
+    eval_symmetry = parse_eval_symmetry(eval_symmetry)
+    if eval_symmetry != "none" and str(search_backend).strip().lower() not in ("portable", "tree"):
+        raise ValueError(f"eval_symmetry={eval_symmetry!r} needs the tree backend: the root-PUCT search "
+                         f"({search_backend!r}) evaluates children without the symmetry hook")
     try:
         t_worker = time.perf_counter()
         torch.manual_seed(int(seed))
@@ -643,7 +649,7 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                           policy_target_temperature=policy_target_temperature,
                                           policy_target_prior_pseudocount=float(policy_target_prior_pseudocount),
                                           seed=rng_seed, collect_timing=os.environ.get("LZ_WORKER_TIMING", "1") != "0", row_log=row_log,
-                                          **common)
+                                          eval_symmetry=eval_symmetry, **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
                                     sparse_top_k=int(sparse_top_k), row_log=row_log, **common)
@@ -658,7 +664,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        # which network evaluator played this shard: the hand-written kernel or the module through
                        # PyTorch (a shape the kernel is not built for; `evaluator_reason` says which)
                        "evaluator": evaluator_name, **({"evaluator_reason": evaluator_why} if evaluator_why else {}),
-                       "streamed": bool(stream), **({"stream_fallback": stream_fallback} if stream_fallback else {})}
+                       "streamed": bool(stream), **({"stream_fallback": stream_fallback} if stream_fallback else {}),
+                       **({"eval_symmetry": eval_symmetry} if eval_symmetry != "none" else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

@@ -13,12 +13,13 @@ from __future__ import annotations
 import os
 import time
 from contextlib import nullcontext
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 from torch import nn, optim
 
+from .symmetry import transform_samples
 from .train_loss import fused_policy_value_loss
 from .trajectory_buffer import TensorSelfPlayBatch
 
@@ -189,6 +190,35 @@ def _resolve_strategy(parallel_strategy: str, device: str):
     return strategy, dev, rank, world
 
 
+class _SymmetryDraw:
+    """Training augmentation by the board symmetries (symmetry.py): one element id per row, drawn uniformly from
+    `symmetry_set` by a generator of its own (seeded by `symmetry_seed` and the DDP rank), so the shuffle of the
+    default generator is the same with and without augmentation.  Value targets do not change under a symmetry."""
+
+    def __init__(self, symmetry_set: Sequence[int], seed: int, rank: int, dev: torch.device) -> None:
+        ids = [int(k) for k in symmetry_set]
+        if not ids or any(not 0 <= k < 8 for k in ids):
+            raise ValueError(f"symmetry_set must be a non-empty sequence of ids in 0..7, got {tuple(symmetry_set)!r}")
+        self.ids = ids
+        self.choices = torch.tensor(ids, dtype=torch.int8, device=dev)
+        self.gen = torch.Generator(device=dev)
+        self.gen.manual_seed((int(seed) * 1000003 + int(rank)) & ((1 << 63) - 1))
+        self.counts = torch.zeros(8, dtype=torch.int64, device=dev)
+        self.ones = torch.ones(1, dtype=torch.int64, device=dev)
+        self.seed, self.dev = int(seed), dev
+
+    def draw(self, rows: int) -> torch.Tensor:
+        if self.ones.numel() < rows:
+            self.ones = torch.ones(rows, dtype=torch.int64, device=self.dev)
+        pick = torch.randint(len(self.ids), (rows,), generator=self.gen, device=self.dev)
+        sym = self.choices.index_select(0, pick)
+        self.counts.index_add_(0, sym.to(torch.int64), self.ones[:rows])      # no host read (bincount sizes on the host)
+        return sym
+
+    def metrics(self) -> Dict[str, Any]:
+        return {"seed": self.seed, "set": list(self.ids), "counts": [int(c) for c in self.counts.tolist()]}
+
+
 def _wrap(model, strategy, dev):
     model.to(dev)
     model.train()
@@ -203,11 +233,13 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                                anti_draw_penalty: float = 0.0, policy_draw_weight: float = 1.0, device: str = "cuda:0",
                                use_amp: bool = True, grad_clip_norm: float = 1.0, warmup_steps: int = 0,
                                parallel_devices: Optional[List[str]] = None, parallel_strategy: str = "none",
-                               ddp_pre_sharded: bool = False, optimizer_state_path: Optional[str] = None
-                               ) -> Tuple[Any, Dict[str, Any]]:
+                               ddp_pre_sharded: bool = False, optimizer_state_path: Optional[str] = None,
+                               symmetry_augment: bool = False, symmetry_seed: int = 0,
+                               symmetry_set: Sequence[int] = tuple(range(8))) -> Tuple[Any, Dict[str, Any]]:
     if samples.num_samples <= 0:
         return model, {"epoch_stats": [], "num_samples": 0}
     strategy, dev, rank, world = _resolve_strategy(parallel_strategy, device)
+    sym_draw = _SymmetryDraw(symmetry_set, symmetry_seed, rank, dev) if symmetry_augment else None
     train_model = _wrap(model, strategy, dev)
     global_n = int(samples.num_samples)
     t0 = time.perf_counter()
@@ -269,8 +301,11 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                 break
             tb = time.perf_counter()
             idx = perm[start:min(start + bsz, n)]
-            stepper.step(states.index_select(0, idx), masks.index_select(0, idx), policy.index_select(0, idx),
-                         values.index_select(0, idx), soft.index_select(0, idx))
+            if sym_draw is not None:                  # gather + transform in one pass
+                b_states, b_masks, b_policy = transform_samples(states, masks, policy, sym_draw.draw(int(idx.numel())), idx)
+            else:
+                b_states, b_masks, b_policy = states.index_select(0, idx), masks.index_select(0, idx), policy.index_select(0, idx)
+            stepper.step(b_states, b_masks, b_policy, values.index_select(0, idx), soft.index_select(0, idx))
             if not first_done:
                 first_batch_sec, first_done = time.perf_counter() - tb, True
         st, _ = stepper.epoch_stats(epoch + 1, {"parallel_strategy": strategy, "ddp_world_size": world,
@@ -284,7 +319,7 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
             torch.save(optimizer.state_dict(), optimizer_state_path)
         except Exception:
             pass
-    return model, {
+    out = {
         "epoch_stats": epoch_stats, "num_samples": global_n, "num_samples_after_filter": n,
         "filtered_non_finite_samples": filtered, "parallel_strategy": strategy, "ddp_world_size": world,
         "local_batch_count": int(local_batches), "synced_batch_count": int(synced),
@@ -294,6 +329,9 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
         "wdl_aux_loss_weight": 0.0, "warmup_steps": int(warm), "total_train_steps": int(total_steps),
         "timing": {"cpu_shard_sec": float(shard_sec), "h2d_copy_sec": float(copy_sec),
                    "first_batch_sec": float(first_batch_sec), "ddp_pre_sharded": bool(ddp_pre_sharded)}}
+    if sym_draw is not None:
+        out["symmetry_augment"] = sym_draw.metrics()
+    return model, out
 
 
 def train_network_streaming(model, dataloader, *, total_samples: int, batch_size: int = 512, epochs: int = 1,
@@ -301,13 +339,16 @@ def train_network_streaming(model, dataloader, *, total_samples: int, batch_size
                             anti_draw_penalty: float = 0.0, policy_draw_weight: float = 1.0, device: str = "cuda:0",
                             use_amp: bool = True, grad_clip_norm: float = 1.0, warmup_steps: int = 0,
                             parallel_devices: Optional[List[str]] = None, parallel_strategy: str = "none",
-                            optimizer_state_path: Optional[str] = None, streaming_workers: int = 8
-                            ) -> Tuple[Any, Dict[str, Any]]:
+                            optimizer_state_path: Optional[str] = None, streaming_workers: int = 8,
+                            symmetry_augment: bool = False, symmetry_seed: int = 0,
+                            symmetry_set: Sequence[int] = tuple(range(8))) -> Tuple[Any, Dict[str, Any]]:
     """Train from an iterable of (states, masks, policy, values, soft) batches -- `streaming.build_streaming_dataloader`
     over the shards of a self-play manifest -- mirroring `v1/python/train_bridge.py:547-900`: the number of steps per
     epoch is fixed up front from `total_samples` (synchronised with MIN over DDP ranks), an exhausted loader turns the
-    remaining steps into no-ops that still take part in the rank votes, non-finite rows are dropped per batch."""
+    remaining steps into no-ops that still take part in the rank votes, non-finite rows are dropped per batch.
+    `symmetry_augment`: every batch is transformed on the device after the copy (see `train_network_from_tensors`)."""
     strategy, dev, rank, world = _resolve_strategy(parallel_strategy, device)
+    sym_draw = _SymmetryDraw(symmetry_set, symmetry_seed, rank, dev) if symmetry_augment else None
     train_model = _wrap(model, strategy, dev)
     bsz = max(1, int(batch_size))
     est = max(1, (int(total_samples) + bsz - 1) // bsz)
@@ -366,6 +407,9 @@ def train_network_streaming(model, dataloader, *, total_samples: int, batch_size
                     continue
                 b_states, b_masks, b_policy, b_values, b_soft = (t.index_select(0, keep) for t in
                                                                  (b_states, b_masks, b_policy, b_values, b_soft))
+            if sym_draw is not None:
+                b_states, b_masks, b_policy = transform_samples(b_states.reshape(-1, 11, 6, 6), b_masks, b_policy,
+                                                                sym_draw.draw(int(b_states.shape[0])))
             stepper.step(b_states, b_masks, b_policy, b_values, b_soft)
             batches += 1
             if not first_done:
@@ -381,7 +425,7 @@ def train_network_streaming(model, dataloader, *, total_samples: int, batch_size
             torch.save(optimizer.state_dict(), optimizer_state_path)
         except Exception:
             pass
-    return model, {
+    out = {
         "epoch_stats": epoch_stats, "num_samples": int(total_samples), "num_samples_seen": int(seen_all),
         "filtered_non_finite_samples": int(total_filtered), "parallel_strategy": strategy, "ddp_world_size": world,
         "est_batches_per_epoch": int(est), "optimizer_loaded": opt_loaded, "optimizer_load_error": opt_err,
@@ -389,3 +433,6 @@ def train_network_streaming(model, dataloader, *, total_samples: int, batch_size
         "device_fallback_reasons": [], "anti_draw_penalty": float(anti_draw_penalty), "wdl_aux_loss_weight": 0.0,
         "warmup_steps": int(warm), "total_train_steps": int(total_steps), "streaming": True,
         "streaming_workers": int(streaming_workers), "timing": {"first_batch_sec": float(first_batch_sec)}}
+    if sym_draw is not None:
+        out["symmetry_augment"] = sym_draw.metrics()
+    return model, out

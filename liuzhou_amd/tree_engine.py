@@ -47,7 +47,28 @@ class LzTreeDesc(C.Structure):
                [(n, C.c_void_p) for n in ("chunk_list", "n_chunks", "free_chunks", "pool_top", "pool_stats")] + \
                [("pool_chunks", C.c_int64)] + \
                [(n, C.c_void_p) for n in ("live_state", "live_row", "live_count")] + [("live_count_cap", C.c_int64)] + \
-               [(n, C.c_void_p) for n in ("pos_index", "node_value", "leaf_src", "share_count")] + [("pos_slots", C.c_int64)]
+               [(n, C.c_void_p) for n in ("pos_index", "node_value", "leaf_src", "share_count")] + [("pos_slots", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("leaf_sym", "trace_sym", "sym_salt", "sym_game", "sym_ply")] + \
+               [("sym_seed", C.c_uint64), ("sym_mode", C.c_int32), ("sym_fixed", C.c_int32)]
+
+
+def parse_eval_symmetry(value) -> "str | int":
+    """`eval_symmetry` of the tree search: "none", "random" or a fixed element id 0..7 (liuzhou_amd/symmetry.py).  Env
+    LZ_EVAL_SYMMETRY=random / none / 0..7 overrides the argument (A/B runs)."""
+    env = os.environ.get("LZ_EVAL_SYMMETRY", "").strip().lower()
+    if env:
+        value = env
+    if isinstance(value, str):
+        v = value.strip().lower()
+        if v in ("none", "random"):
+            return v
+        if v.isdigit():
+            value = int(v)
+        else:
+            raise ValueError(f"eval_symmetry must be 'none', 'random' or an id 0..7, got {value!r}")
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 8:
+        raise ValueError(f"eval_symmetry must be 'none', 'random' or an id 0..7, got {value!r}")
+    return int(value)
 
 
 class LzTreeWaveDesc(C.Structure):
@@ -271,11 +292,42 @@ class TreeEngine:
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         self.trace = {"trace_kind": z((n, B), torch.int32), "trace_leaf": z((n, B, 4), torch.int64),
                       "trace_heads": z((n, B, 108), torch.float32), "trace_priors": z((n, B, 220), torch.float32),
-                      "trace_value": z((n, B), torch.float32)}
+                      "trace_value": z((n, B), torch.float32), "trace_sym": z((n, B), torch.int32)}
         for name, t in self.trace.items():
             setattr(self.desc, name, t.data_ptr())
         self.desc.trace_cap = n
         return self.trace
+
+    def set_eval_symmetry(self, mode, seed: int = 0, game: Optional[torch.Tensor] = None,
+                          ply: Optional[torch.Tensor] = None) -> None:
+        """Symmetric leaf evaluation (LzTreeDesc.sym_*): every evaluation is of sigma_k(leaf), the heads mapped back in the
+        expand step.  `mode`: "none", "random" (k per evaluation from Philox keyed by `seed`, the game key `game[g]`, its
+        ply `ply[g]` -- device tensors read at every launch -- a per-run salt and the leaf state) or a fixed id 0..7.  Must be
+        set before a search is captured into a graph."""
+        d = self.desc
+        if mode == "none":
+            d.sym_mode = 0
+            return
+        if self.batch_k > 1:
+            raise ValueError("eval_symmetry is not supported by the legacy waves (batch_k > 1): their wave kernels "
+                             "evaluate leaves without the symmetry hook")
+        dev = self.device
+        if "leaf_sym" not in self.buf:
+            self.buf["leaf_sym"] = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+            self.buf["sym_salt"] = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+            d.leaf_sym, d.sym_salt = self.buf["leaf_sym"].data_ptr(), self.buf["sym_salt"].data_ptr()
+        # per-run salt: the run's seed lives in device memory too, so an engine whose searches were captured under another
+        # seed (a cached engine, reset_run) still draws that run's own ids
+        self.buf["sym_salt"].fill_(int(seed) * 0x9E3779B1 & 0x7FFFFFFF)
+        if mode == "random":
+            if game is None or ply is None:
+                raise ValueError("eval_symmetry='random' needs the per-game RNG keys (game, ply)")
+            self._sym_keys = (game, ply)
+            d.sym_game, d.sym_ply = game.data_ptr(), ply.data_ptr()
+            d.sym_mode, d.sym_fixed, d.sym_seed = 2, 0, int(seed) & 0xFFFFFFFFFFFFFFFF
+        else:
+            d.sym_mode, d.sym_fixed = 1, int(mode)
+        self.persistent = False           # the persistent kernel's own network pass is not part of this: the fused search
 
     _NODE_DT = [("w0", "<u8"), ("w1", "<u8"), ("w2", "<u8"), ("w3", "<u8"), ("edge_begin", "<i4"), ("nedges", "<i4"),
                 ("parent", "<i4"), ("old_begin", "<i4")]
@@ -530,8 +582,10 @@ class PortableTreeMCTS:
                  reuse_factor: float = -1.0, policy_target_temperature: Optional[float] = None,
                  policy_target_prior_pseudocount: float = 0.0, batch_k: int = 1, seed: int = 12345,
                  game_offset: int = 0, game_stride: Optional[int] = None, trace: bool = False,
-                 collect_timing: bool = False, compact_evals: Optional[bool] = None) -> None:
-        """`compact_evals` (fused network only): per simulation only the leaves that need the network are evaluated
+                 collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none") -> None:
+        """`eval_symmetry`: "none" (default), "random" or a fixed element id 0..7 -- every leaf is evaluated as
+        sigma_k(leaf) and the heads are mapped back (parse_eval_symmetry, TreeEngine.set_eval_symmetry); not with
+        batch_k > 1 (ValueError).  `compact_evals` (fused network only): per simulation only the leaves that need the network are evaluated
         (`TreeEngine(compact_evals=True)`); True = in every search; None = the engine is built for both forms when a launch
         of all slots is at least two network passes per CU (C3: eight) and uses the lists for the searches that say so
         (`search_batch(compact=True)`, the runner's hint that the wave is draining) -- env LZ_TREE_COMPACT=0 / 1 overrides.
@@ -571,6 +625,8 @@ class PortableTreeMCTS:
                 raise ValueError("an external evaluator supports batch_k = 1 only")
             self._eval_device = None if isinstance(net, PriorEvaluator) else next(net.parameters()).device
         self.rng = GameRng(num_games, device, seed=seed, game_offset=game_offset, game_stride=game_stride)
+        self.eval_symmetry = parse_eval_symmetry(eval_symmetry)
+        self.engine.set_eval_symmetry(self.eval_symmetry, seed, self.rng.game, self.rng.ply)
         self._game0 = self.rng.game.clone()
         self._uniforms = torch.zeros((self.engine.B,), dtype=torch.float32, device=self.engine.device)
         self.injected_noise: Optional[torch.Tensor] = None       # parity runs: [B, <= OUT_CAP] instead of the RNG's draws
@@ -767,6 +823,8 @@ class PortableTreeMCTS:
         self.rng.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.rng.game.copy_(self._game0)
         self.rng.ply.zero_()
+        if self.eval_symmetry != "none":
+            self.engine.buf["sym_salt"].fill_(int(seed) * 0x9E3779B1 & 0x7FFFFFFF)
         self._root_evals = 0
         self.extra_rounds = 0
         self.engine.eval_count.zero_()
@@ -1183,7 +1241,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        policy_target_prior_pseudocount: float = 0.0, reuse_tree: bool = True,
                        reuse_factor: float = -1.0, dual_stream: Optional[bool] = None, continuous_waves: bool = True,
                        device_tail: bool = True, batch_k: int = 1, evaluator: str = "auto", seed: int = 12345,
-                       collect_timing: bool = False, row_log=None) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
+                       collect_timing: bool = False, row_log=None, eval_symmetry="none"
+                       ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
     `model` may also be a `PriorEvaluator` (states -> priors over the 220 actions + values, the reference's own
@@ -1192,8 +1251,14 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     device (what the reference's portable runner does with its `model`); "auto" = fused when the net has a fused
     kernel.  `seed`: key of the per-game counter RNG (noise, sampled moves); game ids are the runner's game numbers.
     `row_log` (finished_log.FinishedRowLog, the streaming worker): the rows of every game leave through the log when the
-    game ends and the returned batch is empty; needs `device_tail` and `continuous_waves`."""
+    game ends and the returned batch is empty; needs `device_tail` and `continuous_waves`.
+    `eval_symmetry`: "none" (default), "random" or an id 0..7 -- each leaf evaluated under a board symmetry
+    (PortableTreeMCTS); not with batch_k > 1."""
     dev = torch.device(device)
+    eval_symmetry = parse_eval_symmetry(eval_symmetry)
+    if eval_symmetry != "none" and int(batch_k) > 1:
+        raise ValueError("eval_symmetry is not supported by the legacy waves (batch_k > 1): their wave kernels evaluate "
+                         "leaves without the symmetry hook")
     if row_log is not None and not (device_tail and continuous_waves):
         raise RuntimeError("self_play_tree_gpu: a finished-row log needs device_tail and continuous_waves")
     if evaluator not in ("auto", "fused", "module"):
@@ -1210,7 +1275,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     # two half-batches on two streams (see DualStreamTreeMCTS) once a wave is large enough to fill the chip twice over
     if dual_stream is None:
         dual_stream = use_fused and net.pack.channels == 64 and wave >= 1024 and int(batch_k) <= 1   # waves: large launches already
-    if use_fused and persistent_search_available(net, batch_k):
+    if use_fused and persistent_search_available(net, batch_k) and eval_symmetry == "none":
         dual_stream = False                                  # the persistent kernel overlaps the phases inside every CU
     cls = DualStreamTreeMCTS if (dual_stream and use_fused and net.pack.channels == 64 and wave >= 2) else PortableTreeMCTS
     t_setup = time.perf_counter()
@@ -1220,6 +1285,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
               policy_target_temperature=policy_target_temperature,
               policy_target_prior_pseudocount=float(policy_target_prior_pseudocount), batch_k=int(batch_k),
               collect_timing=bool(collect_timing))
+    if eval_symmetry != "none":
+        kw["eval_symmetry"] = eval_symmetry
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a

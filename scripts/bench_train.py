@@ -83,3 +83,22 @@ for name in ("b6c64", "b10c128"):
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     print(f"train step {name}: {2 * n / dt:,.0f} samples/s (batch 4096, AMP fp16, Adam, {m['total_train_steps']} steps, "
           f"loss {m['epoch_stats'][0]['avg_loss']:.3f} -> {m['epoch_stats'][1]['avg_loss']:.3f})", flush=True)
+
+# symmetry augmentation (train_bridge.symmetry_augment): whole training steps at batch 512 on b10c128, runs with and
+# without the flag alternated on the same data so that clock and thermal drift fall on both sides
+torch.manual_seed(0)
+model = ChessNet(**MODEL_CONFIGS["b10c128"]); stable_resnet_init(model, 20260314); model.to(dev)
+n = B
+batch = TensorSelfPlayBatch(state_tensors=(torch.rand((n, 11, 6, 6), device=dev) < 0.2).float(),
+                            legal_masks=mask[:n], policy_targets=target[:n], value_targets=value[:n],
+                            soft_value_targets=soft[:n])
+train_network_from_tensors(model, batch, batch_size=512, epochs=1, device="cuda:0")           # MIOpen warm-up
+times = {False: [], True: []}
+for rep in range(6):
+    for aug in ((False, True) if rep % 2 == 0 else (True, False)):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        _, m = train_network_from_tensors(model, batch, batch_size=512, epochs=1, device="cuda:0", symmetry_augment=aug)
+        torch.cuda.synchronize(); times[aug].append((time.perf_counter() - t0) / m["total_train_steps"] * 1e3)
+off, on = (sorted(times[a])[len(times[a]) // 2] for a in (False, True))
+print(f"train step b10c128 batch 512: {off:.3f} ms without, {on:.3f} ms with symmetry augmentation "
+      f"({(on / off - 1) * 100:+.1f} %, medians of 6 alternated epochs of {n // 512} steps)", flush=True)

@@ -48,6 +48,9 @@ def parse(argv=None):
     ap.add_argument("--model_init_seed", type=int, default=int(os.environ.get("V1_MODEL_INIT_SEED", "20260314")))
     ap.add_argument("--model", default="b10c128", choices=["b6c64", "b10c128"])
     ap.add_argument("--metrics_output", default=None)
+    ap.add_argument("--symmetry-augment", dest="symmetry_augment", type=int, nargs="?", const=1, default=0,
+                    help="show every training row under a random one of the 8 board symmetries (default off)")
+    ap.add_argument("--symmetry-seed", dest="symmetry_seed", type=int, default=0)
     args, ignored = ap.parse_known_args(argv)
     args.ignored = ignored
     return args
@@ -86,6 +89,8 @@ def main(argv=None) -> int:
                   soft_label_alpha=args.soft_label_alpha, anti_draw_penalty=args.anti_draw_penalty,
                   policy_draw_weight=args.policy_draw_weight, device=device, warmup_steps=args.warmup_steps,
                   parallel_strategy=strategy, optimizer_state_path=args.optimizer_state_path)
+    if int(args.symmetry_augment):
+        common.update(symmetry_augment=True, symmetry_seed=int(args.symmetry_seed))
     t0 = time.perf_counter()
     if int(args.streaming_load):
         budget = int(args.replay_budget_per_file)
