@@ -338,6 +338,17 @@ LZ_API int lz_net_forward_packed_f16(const LzNetDesc* net, const void* packed_st
 LZ_API int lz_net_forward_packed_counted_f16(const LzNetDesc* net, const void* packed_states, int64_t capacity,
                                              const int64_t* count, float* log_p1, float* log_p2, float* log_pmc,
                                              float* value_logits, float* value, void* stream);
+/* Several networks of the same architecture in one launch, input from packed states.  Network k evaluates the rows
+ * [align16(seg_off[k]), seg_off[k + 1]) (seg_off: device int64[num_nets + 1], read by the kernel, so a producer kernel can
+ * write it; seg_off[num_nets] <= capacity): every segment starts on a 16-row boundary, so no pass of the kernel's 8 or 16
+ * samples mixes two networks, and the rows between one segment's end and the next boundary are padding that no pass
+ * covers (an empty segment: seg_off[k + 1] <= align16(seg_off[k])).  1 <= num_nets <= 8.  The networks must agree in
+ * everything but `wfrag` and `fparams` (channels, blocks, layer / head / parameter offsets, buffer sizes, max_blocks,
+ * flags bits 0-1): LZ_ERR_ARG otherwise; fp32-operand and split-fp16 networks (flags bits 2-3): LZ_ERR_UNSUPPORTED.
+ * Every row's outputs are bit-identical to lz_net_forward_packed_f16 of that row with its own network. */
+LZ_API int lz_net_forward_packed_multi_f16(const LzNetDesc* const* nets, int32_t num_nets, const void* packed_states,
+                                           int64_t capacity, const int64_t* seg_off, float* log_p1, float* log_p2,
+                                           float* log_pmc, float* value_logits, float* value, void* stream);
 /* one-time kernel attribute setup (dynamic LDS size); call once per process before graph capture */
 LZ_API int lz_net_configure(void);
 /* sizeof(LzNetDesc) as the library was compiled: a binding that lays the struct out itself (ctypes) compares */
@@ -454,6 +465,13 @@ typedef struct LzTreeDesc {
     const int64_t* sym_ply;        /* [B] (mode 2) */
     uint64_t sym_seed;
     int32_t  sym_mode, sym_fixed;
+    /* Several networks in one search (lz_tree_search_multi; unused by every other entry point): slot g belongs to
+     * network g / seg_games (seg_games a multiple of 16, num_games = num_nets * seg_games).  Each simulation's compact
+     * list (live_*, required) then holds network k's leaves at consecutive rows from a 16-aligned base, and
+     * seg_off[s * (num_nets + 1) .. + num_nets] is that simulation's segment row of lz_net_forward_packed_multi_f16;
+     * live_count[s] = the padded total. */
+    int64_t  seg_games;
+    int64_t* seg_off;              /* [live_count_cap * (num_nets + 1)] */
 } LzTreeDesc;
 LZ_API int64_t lz_tree_desc_bytes(void);
 
@@ -531,6 +549,17 @@ LZ_API int lz_tree_finish(const LzTreeDesc* tree, const float* temperatures, con
 LZ_API int lz_tree_search(const LzTreeDesc* tree, const LzNetDesc* net, int64_t sims, float* planes /*[B,11,36]*/,
                           float* log_p1, float* log_p2, float* log_pmc, float* values, const float* noise,
                           int64_t noise_stride, float epsilon, void* stream);
+/* lz_tree_search / _continue with one network per segment of seg_games slots (LzTreeDesc.seg_games / seg_off and the
+ * compact lists required; 1 <= num_nets <= 8, networks as lz_net_forward_packed_multi_f16 accepts them).  One network
+ * launch per simulation for all segments; no host synchronisation, capturable.  Each game's tree is what
+ * lz_tree_search builds with that game's network.  Symmetric evaluation (sym_mode != 0) is refused (LZ_ERR_UNSUPPORTED);
+ * the persistent kernel, waves and two-stream searches have no multi-network form. */
+LZ_API int lz_tree_search_multi(const LzTreeDesc* tree, const LzNetDesc* const* nets, int32_t num_nets, int64_t sims,
+                                float* log_p1, float* log_p2, float* log_pmc, float* values, const float* noise,
+                                int64_t noise_stride, float epsilon, void* stream);
+LZ_API int lz_tree_search_multi_continue(const LzTreeDesc* tree, const LzNetDesc* const* nets, int32_t num_nets,
+                                         int64_t sims, float* log_p1, float* log_p2, float* log_pmc, float* values,
+                                         const float* noise, int64_t noise_stride, float epsilon, void* stream);
 /* ---- per-game counter RNG -----------------------------------------------------------------------------------
  * Replaces the library generators behind the reference's root noise and move sampling
  * (torch.distributions.Gamma / torch.multinomial on the device generator, v1/python/mcts_gpu.py:1329-1339,1410-1424;

@@ -167,6 +167,70 @@ __global__ __launch_bounds__(kScanBlock) void tree_live_scan_kernel(Tree t, unsi
     if (tid == 0) *count = (unsigned long long)total;
 }
 
+// Segmented form of the scan (lz_tree_search_multi): slots [k * seg_games, (k + 1) * seg_games) belong to network k.
+// Segment k's live leaves get consecutive rows from base_k, a multiple of 16, in the order of the plain scan within the
+// segment; base_{k+1} = align16(base_k + live_k).  seg_row[0] = 0 and seg_row[k + 1] = base_k + live_k (the end of segment
+// k's live rows: the segment layout of lz_net_forward_packed_multi_f16), *count = align16(last end), the padded total.
+// One workgroup; the segments one after the other.
+__global__ __launch_bounds__(kScanBlock) void tree_live_scan_seg_kernel(Tree t, int seg_games, int num_segs,
+                                                                        unsigned long long* __restrict__ count,
+                                                                        long long* __restrict__ seg_row) {
+    __shared__ int wave_total[kScanBlock / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
+    const int rounds = (seg_games + kScanBlock - 1) / kScanBlock;
+    int base = 0, end = 0;
+    if (tid == 0) seg_row[0] = 0;
+    for (int k = 0; k < num_segs; ++k) {
+        const int g0 = k * seg_games;
+        int cnt = 0;
+        for (int r0 = 0; r0 < rounds; r0 += kScanUnroll) {
+            int kind[kScanUnroll];
+#pragma unroll
+            for (int u = 0; u < kScanUnroll; ++u) {
+                const int i = (r0 + u) * kScanBlock + tid;
+                kind[u] = (r0 + u < rounds && i < seg_games) ? t.leaf_kind[g0 + i] : kLeafInactive;
+            }
+#pragma unroll
+            for (int u = 0; u < kScanUnroll; ++u) cnt += kind[u] == kLeafExpand ? 1 : 0;
+        }
+        int incl = cnt;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const int v = __shfl_up(incl, d, kWave);
+            if (lane >= d) incl += v;
+        }
+        if (lane == kWave - 1) wave_total[w] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int i = 0; i < kScanBlock / kWave; ++i) { if (i < w) before += wave_total[i]; total += wave_total[i]; }
+        __syncthreads();                                           // wave_total is rewritten by the next segment
+        int row = base + before + incl - cnt;
+        for (int r0 = 0; r0 < rounds; r0 += kScanUnroll) {
+            int kind[kScanUnroll];
+            Packed st[kScanUnroll];
+#pragma unroll
+            for (int u = 0; u < kScanUnroll; ++u) {
+                const int i = (r0 + u) * kScanBlock + tid;
+                const bool in = r0 + u < rounds && i < seg_games;
+                kind[u] = in ? t.leaf_kind[g0 + i] : kLeafInactive;
+                if (in) st[u] = load_state(&t.leaf_state[g0 + i]);
+            }
+#pragma unroll
+            for (int u = 0; u < kScanUnroll; ++u) {
+                if (kind[u] != kLeafExpand) continue;
+                const int g = g0 + (r0 + u) * kScanBlock + tid;
+                t.live_row[g] = row;
+                t.live_state[row] = st[u];
+                ++row;
+            }
+        }
+        end = base + total;
+        if (tid == 0) seg_row[k + 1] = end;
+        base = (end + 15) & ~15;
+    }
+    if (tid == 0) *count = (unsigned long long)base;
+}
+
 // expand + backup of simulation s fused with the selection of simulation s+1 (same wave, same game: the edge
 // records it just touched are still in L1/L2) -- one launch per simulation besides the network kernel.
 // (forcing 8 waves / SIMD -- <= 96 SGPRs, 126 scalar spills -- was measured: no gain at 16 384 games, 1 % slower at C2)
@@ -1430,6 +1494,58 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     return st();
 }
 
+// lz_net.hip (internal): the checks of lz_net_forward_packed_multi_f16 on its networks
+int lz_net_multi_validate(const LzNetDesc* const* nets, int num_nets);
+
+// tree_search_impl's compact-list search with one network per segment of d->seg_games slots: the segmented scan after
+// every select step, one multi-network launch per simulation on that simulation's seg_off row.  The expand / select
+// kernels are the list path's own: they read live_row[g] whatever the order of the rows.
+static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* nets, int num_nets, int64_t sims,
+                                  float* lp1, float* lp2, float* lpmc, float* values, const float* noise,
+                                  int64_t noise_stride, float epsilon, bool continue_trees, void* stream) {
+    if (!tree_ok(d) || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
+    int rc = lz_net_multi_validate(nets, num_nets);
+    if (rc) return rc;
+    const int64_t B = d->num_games, G = d->seg_games;
+    if (G <= 0 || (G & 15) || B != (int64_t)num_nets * G || !d->seg_off) return LZ_ERR_ARG;
+    if (!(d->live_state && d->live_row && d->live_count) || d->live_count_cap < sims + 2) return LZ_ERR_ARG;
+    if (d->sym_mode != 0) return LZ_ERR_UNSUPPORTED;                // symmetric evaluation: one network per search only
+    rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
+    if (rc) return rc;
+    const Tree t = split_step(B) ? no_share(make_tree(d)) : make_tree(d);
+    const int64_t R = num_nets + 1;
+    auto scan = [&](int64_t s) {
+        hipLaunchKernelGGL(tree_live_scan_seg_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t, (int)G, num_nets,
+                           t.live_count + s, reinterpret_cast<long long*>(d->seg_off + s * R));
+    };
+    scan(0);                                                        // the roots
+    for (int64_t s = 0; s <= sims; ++s) {
+        rc = lz_net_forward_packed_multi_f16(nets, num_nets, d->live_state, B, d->seg_off + s * R, lp1, lp2, lpmc, nullptr,
+                                             values, stream);
+        if (rc) return rc;
+        if (s == sims) {
+            if (s == 0)
+                hipLaunchKernelGGL((tree_expand_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
+                                   lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s);
+            else
+                hipLaunchKernelGGL((tree_expand_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
+                                   lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s);
+        } else if (s == 0) {
+            hipLaunchKernelGGL((tree_expand_select_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s);
+        } else {
+            if (split_step(t.B))
+                hipLaunchKernelGGL((tree_expand_select_split_kernel<true>), dim3(gw2(t.B)), dim3(kBlock), 0,
+                                   as_stream(stream), t, lp1, lp2, lpmc, values, (int)s);
+            else
+                hipLaunchKernelGGL((tree_expand_select_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s);
+        }
+        if (s < sims) scan(s + 1);                                  // the leaves of simulation s + 1
+    }
+    return st();
+}
+
 #ifdef LZ_EXP_TREE_STAMPS
 LZ_API int lz_exp_tree_stamps(unsigned long long* out32, int reset) {
     if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_tree_stamps), 32 * sizeof(unsigned long long)) != hipSuccess) return LZ_ERR_LAUNCH;
@@ -1511,6 +1627,20 @@ int lz_tree_search_continue(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
                             float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                             float epsilon, void* stream) {
     return tree_search_impl(d, net, sims, planes, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, true, stream);
+}
+
+int lz_tree_search_multi(const LzTreeDesc* d, const LzNetDesc* const* nets, int32_t num_nets, int64_t sims, float* lp1,
+                         float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride, float epsilon,
+                         void* stream) {
+    return tree_search_multi_impl(d, nets, num_nets, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, false,
+                                  stream);
+}
+
+int lz_tree_search_multi_continue(const LzTreeDesc* d, const LzNetDesc* const* nets, int32_t num_nets, int64_t sims,
+                                  float* lp1, float* lp2, float* lpmc, float* values, const float* noise,
+                                  int64_t noise_stride, float epsilon, void* stream) {
+    return tree_search_multi_impl(d, nets, num_nets, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, true,
+                                  stream);
 }
 
 int lz_rng_gamma(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t B, float alpha, int64_t count,

@@ -72,6 +72,73 @@ int launch_net(const NetParams& P, const float* planes, const uint64_t* packed, 
     return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
 }
 
+// ---- several networks of one architecture in one launch (lz_net_forward_packed_multi_f16) --------------------------------
+// Network k owns the rows [align16(seg_off[k]), seg_off[k + 1]): every segment starts on a 16-row boundary (16 = the
+// largest S), so no pass of S samples mixes two networks; rows between a segment's end and the next boundary are padding
+// and no pass covers them.  The networks differ only in their two buffers: a pass looks up its segment (wave-uniform,
+// from the pass index) and, when that differs from the workgroup's previous pass, points the buffer descriptors at that
+// network's weights.  That is the whole per-network set-up: net_setup loads nothing network-specific (the head
+// parameters are fetched by the pass that uses them) and every pass starts with a workgroup barrier.
+constexpr int kMaxNets = 8;
+struct MultiNets {
+    const _Float16* wfrag[kMaxNets];
+    const float* fp[kMaxNets];
+};
+
+template <int C, int S, int W>
+__global__ __launch_bounds__(W * 64, (C == 128 && W == 4) ? 1 : 2) void net_forward_multi_kernel(
+        NetParams P, MultiNets M, int num_nets, const uint64_t* __restrict__ packed, int64_t capacity,
+        const long long* __restrict__ seg_off, float* __restrict__ lp1, float* __restrict__ lp2, float* __restrict__ lpm,
+        float* __restrict__ vlogits, float* __restrict__ value) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    NetCtx<C, S, W> ctx;
+    net_setup<C, S, W>(P, lds, ctx);
+    const long long total = seg_off[num_nets];
+    const int last = (int)(total < capacity ? total : capacity);
+    const int n_pass = (last + S - 1) / S;
+    int cur = -1;
+    const float* fp = nullptr;
+    for (int pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
+        const int n0 = pass * S;
+        // the pass's segment: the last one that starts at or before it (an empty segment starts where the next one does).
+        // Re-read per pass (scalar loads, a few per pass of a whole network): nothing network-specific held in SGPRs
+        int k = 0;
+        for (int j = 1; j < num_nets; ++j)
+            if (((seg_off[j] + 15) & ~15LL) <= n0) k = j;
+        k = __builtin_amdgcn_readfirstlane(k);
+        const long long b = (seg_off[k] + 15) & ~15LL, e = seg_off[k + 1] < last ? seg_off[k + 1] : last;
+        const int nvalid = (int)((e - n0) < S ? (e - n0) : S);
+        if (n0 < b || nvalid <= 0) continue;                       // padding behind a segment's live rows
+        if (k != cur) {
+            fp = M.fp[k];
+            net_use_weights<C, S, W>(P, ctx, M.wfrag[k], fp);
+            cur = k;
+        }
+        net_pass<C, S, W>(P, lds, ctx, nullptr, packed, (int64_t)n0, nvalid, lp1, lp2, lpm, vlogits, value, fp);
+    }
+}
+
+template <int C, int S, int W>
+int launch_net_multi(const NetParams& P, const MultiNets& M, int num_nets, const uint64_t* packed, int64_t capacity,
+                     const int64_t* seg_off, float* lp1, float* lp2, float* lpm, float* vlogits, float* value,
+                     int max_blocks, hipStream_t st) {
+    using K = Cfg<C, S, W>;
+    // the rows are known on the device only (seg_off[num_nets] <= capacity): size the grid for a full list
+    const int64_t n_pass = (capacity + S - 1) / S;
+    int grid = (int)(n_pass < max_blocks ? n_pass : max_blocks);
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL((net_forward_multi_kernel<C, S, W>), dim3(grid), dim3(K::THREADS), K::LDS_BYTES, st, P, M, num_nets,
+                       packed, capacity, reinterpret_cast<const long long*>(seg_off), lp1, lp2, lpm, vlogits, value);
+    return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
+}
+
+template <int C, int S, int W>
+int configure_net_multi() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(net_forward_multi_kernel<C, S, W>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<C, S, W>::LDS_BYTES) == hipSuccess
+               ? LZ_OK : LZ_ERR_LAUNCH;
+}
+
 template <int C, int S, int W>
 int configure_net() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(net_forward_kernel<C, S, W>),
@@ -218,7 +285,11 @@ int64_t lz_net_desc_bytes(void) { return (int64_t)sizeof(LzNetDesc); }
 int lz_net_configure(void) {
     const int a = configure_net<64, 16, 8>(), b = configure_net<128, 8, 8>(), c = configure_net<64, 8, 4>(),
               e = configure_net<128, 8, 4>();
-    return a != LZ_OK ? a : (b != LZ_OK ? b : (c != LZ_OK ? c : e));
+    const int ma = configure_net_multi<64, 16, 8>(), mb = configure_net_multi<128, 8, 8>(),
+              mc = configure_net_multi<64, 8, 4>(), me = configure_net_multi<128, 8, 4>();
+    for (int rc : {a, b, c, e, ma, mb, mc, me})
+        if (rc != LZ_OK) return rc;
+    return LZ_OK;
 }
 
 // fp32-operand parity mode (lz_net_f32.hip)
@@ -286,6 +357,78 @@ int lz_net_forward_packed_counted_f16(const LzNetDesc* d, const void* packed_sta
     if (!count) return LZ_ERR_ARG;
     return net_forward_impl(d, nullptr, reinterpret_cast<const uint64_t*>(packed_states), capacity, lp1, lp2, lpmc,
                             value_logits, value, stream, count);
+}
+
+// Networks that may share one launch: the same kernel shape and the same layout of both buffers -- everything but the
+// two buffer pointers.  fp32-operand / split-fp16 networks (flags bits 2-3) are not supported here.
+static int multi_net_check(const LzNetDesc* a, const LzNetDesc* b) {
+    if (a->channels != b->channels || a->blocks != b->blocks || a->num_layers != b->num_layers ||
+        a->max_blocks != b->max_blocks || a->wfrag_bytes != b->wfrag_bytes || a->fparams_bytes != b->fparams_bytes ||
+        (a->flags & 3) != (b->flags & 3))
+        return LZ_ERR_ARG;
+    for (int i = 0; i < LZ_NET_MAX_LAYERS; ++i)
+        if (i < a->num_layers && a->layer_offsets[i] != b->layer_offsets[i]) return LZ_ERR_ARG;
+    for (int i = 0; i < 4; ++i)
+        if (a->head_frag_offsets[i] != b->head_frag_offsets[i]) return LZ_ERR_ARG;
+    const int32_t oa[13] = {a->off_stem_bias, a->off_block0, a->off_trunk_a, a->off_trunk_b, a->off_head_bias, a->off_p_gwT,
+                            a->off_p_a2, a->off_p_b2, a->off_p_out, a->off_v_w1T, a->off_v_b1, a->off_v_w2T, a->off_v_b2};
+    const int32_t ob[13] = {b->off_stem_bias, b->off_block0, b->off_trunk_a, b->off_trunk_b, b->off_head_bias, b->off_p_gwT,
+                            b->off_p_a2, b->off_p_b2, b->off_p_out, b->off_v_w1T, b->off_v_b1, b->off_v_w2T, b->off_v_b2};
+    for (int i = 0; i < 13; ++i)
+        if (oa[i] != ob[i]) return LZ_ERR_ARG;
+    return LZ_OK;
+}
+
+/* internal (not exported; lz_tree_search_multi checks its networks before it launches anything) */
+int lz_net_multi_validate(const LzNetDesc* const* nets, int num_nets) {
+    if (!nets || num_nets < 1 || num_nets > kMaxNets) return LZ_ERR_ARG;
+    for (int k = 0; k < num_nets; ++k) {
+        const LzNetDesc* n = nets[k];
+        if (!n || !n->wfrag || !n->fparams) return LZ_ERR_ARG;
+        if (n->flags & (4 | 8)) return LZ_ERR_UNSUPPORTED;
+        if ((reinterpret_cast<uintptr_t>(n->wfrag) & 15) || (reinterpret_cast<uintptr_t>(n->fparams) & 15)) return LZ_ERR_ALIGN;
+    }
+    const LzNetDesc* d = nets[0];
+    if (d->blocks < 0 || d->blocks > (LZ_NET_MAX_LAYERS - 2) / 2 || d->num_layers != 2 + 2 * d->blocks) return LZ_ERR_ARG;
+    for (int k = 1; k < num_nets; ++k) {
+        const int rc = multi_net_check(d, nets[k]);
+        if (rc) return rc;
+    }
+    return d->channels == 64 || d->channels == 128 ? LZ_OK : LZ_ERR_UNSUPPORTED;
+}
+
+int lz_net_forward_packed_multi_f16(const LzNetDesc* const* nets, int32_t num_nets, const void* packed_states,
+                                    int64_t capacity, const int64_t* seg_off, float* lp1, float* lp2, float* lpmc,
+                                    float* value_logits, float* value, void* stream) {
+    if (!nets || num_nets < 1 || num_nets > kMaxNets || capacity < 0 || capacity > (int64_t)INT32_MAX - 64) return LZ_ERR_ARG;
+    if (capacity == 0) return LZ_OK;
+    if (!packed_states || !seg_off) return LZ_ERR_ARG;
+    const bool heads = lp1 && lp2 && lpmc;
+    if (!heads && (lp1 || lp2 || lpmc || !value)) return LZ_ERR_ARG;
+    const int vrc = lz_net_multi_validate(nets, num_nets);
+    if (vrc) return vrc;
+    const LzNetDesc* d = nets[0];
+    MultiNets M{};
+    for (int k = 0; k < kMaxNets; ++k) {                        // unused entries repeat network 0 (never selected)
+        const LzNetDesc* n = nets[k < num_nets ? k : 0];
+        M.wfrag[k] = reinterpret_cast<const _Float16*>(n->wfrag);
+        M.fp[k] = n->fparams;
+    }
+    const NetParams P = make_net_params(d);
+    const bool half_wg = d->channels == 64 && (d->flags & 1);
+    const bool wide = d->channels == 128 && (d->flags & 2);
+    const int max_blocks = d->max_blocks > 0 ? d->max_blocks : (half_wg ? 512 : 256);
+    const uint64_t* packed = reinterpret_cast<const uint64_t*>(packed_states);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return d->channels == 64
+               ? (half_wg ? launch_net_multi<64, 8, 4>(P, M, num_nets, packed, capacity, seg_off, lp1, lp2, lpmc, value_logits,
+                                                       value, max_blocks, st)
+                          : launch_net_multi<64, 16, 8>(P, M, num_nets, packed, capacity, seg_off, lp1, lp2, lpmc, value_logits,
+                                                        value, max_blocks, st))
+               : (wide ? launch_net_multi<128, 8, 4>(P, M, num_nets, packed, capacity, seg_off, lp1, lp2, lpmc, value_logits,
+                                                     value, max_blocks, st)
+                       : launch_net_multi<128, 8, 8>(P, M, num_nets, packed, capacity, seg_off, lp1, lp2, lpmc, value_logits,
+                                                     value, max_blocks, st));
 }
 
 }  // extern "C"

@@ -574,19 +574,30 @@ __device__ __forceinline__ void net_setup(const NetParams& P, unsigned char* lds
     //  them -- a launch of one pass per workgroup starts with LDS writes only)
 }
 
+// Multi-network launch: point the workgroup's buffer descriptors at network (wfrag, fp) -- wave-uniform pointers, so
+// the descriptors stay in SGPRs.  The networks of one launch share every offset and size of NetParams.
+template <int C, int S, int W>
+__device__ __forceinline__ void net_use_weights(const NetParams& P, NetCtx<C, S, W>& ctx, const _Float16* wfrag,
+                                                const float* fp) {
+    ctx.rw = make_rsrc(wfrag, P.wfrag_bytes);
+    ctx.rf = make_rsrc(fp, P.fparams_bytes);
+}
+
 // One pass: samples n0 .. n0 + nvalid - 1 (nvalid <= S) of `packed` (32-byte bitboard records) or `planes`.
 // Starts with a workgroup barrier (the previous user of the LDS buffers is done, and -- in the persistent search
 // kernel -- the leaf states the tree step wrote are visible); ends without one.  Outputs go to global memory.
+// `fp_net` (multi-network launch): this pass's float parameters instead of P.fp; ctx.rw / ctx.rf are then that network's
+// descriptors too (net_use_weights).  nullptr everywhere else, which folds away.
 template <int C, int S, int W>
 __device__ __forceinline__ void net_pass(const NetParams& P, unsigned char* lds, NetCtx<C, S, W>& ctx, const float* planes,
                                          const uint64_t* packed, int64_t n0, int nvalid, float* lp1, float* lp2,
-                                         float* lpm, float* vlogits, float* value) {
+                                         float* lpm, float* vlogits, float* value, const float* fp_net = nullptr) {
     using K = Cfg<C, S, W>;
     constexpr int NW = K::CTW;
     using Acc = AccT<NW>;
     constexpr int NTHR = K::THREADS;
     const int tid = ctx.tid, lane = ctx.lane, wave = ctx.wave, cg = ctx.cg, ct0 = ctx.ct0, chan0 = ctx.chan0;
-    const float* fp = P.fp;
+    const float* fp = fp_net != nullptr ? fp_net : P.fp;
     const __amdgpu_buffer_rsrc_t rw = ctx.rw, rf = ctx.rf;
     int (&base)[9] = ctx.base;
     const bool mirror = ctx.mirror;

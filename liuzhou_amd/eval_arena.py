@@ -9,11 +9,18 @@ move.  Semantics kept from the reference worker (`_eval_worker_v1`, :448-654):
     are played uniformly at random by whoever is to move,
   * the opponent is another checkpoint (same search settings) or `RandomAgent` (uniform over the legal moves),
   * result payload = wins / losses / draws / rates from the challenger's side (+ per-colour breakdown).
+Two search backends: `RootSearchAgent` (the reference's `--backend v1`, root PUCT) and `TreeSearchAgent` (its
+`--backend portable`, `_PortableEvalAgent`, eval_checkpoint.py:324-445: the full-tree search, a fresh tree every move, no
+root noise).  When both sides are tree agents the games are searched JOINTLY: one engine with a segment of slots per
+network (slot g of segment k = game g, active when network k is to move there), so one search per ply covers every game
+and each simulation is one network launch for both networks.  `play_matches(joint=False)` searches each agent's games
+with its own engine instead -- the same moves (each game's tree depends on its position and its network only; the RNG
+is keyed by game and ply).  In the tree backend the opening random moves of a ply are drawn in one call over all games.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Any, Dict, Optional
+from typing import Any, Dict, List, Optional, Sequence
 
 import torch
 
@@ -105,10 +112,166 @@ class RootSearchAgent:
         return out.chosen_action_codes, out.chosen_valid_mask, out.terminal_mask
 
 
+def _pad16(n: int) -> int:
+    return max(16, -(-int(n) // 16) * 16)
+
+
+class TreeSearchAgent:
+    """Checkpoint + the full-tree search (`PortableTreeMCTS`), as the reference's `_PortableEvalAgent`
+    (eval_checkpoint.py:324-445): a fresh tree for every move (no subtree reuse), no Dirichlet noise, and the pick by
+    `sample_moves` (visit counts ^ 1/temperature) or the N -> Q -> P -> index order of the deterministic pick."""
+
+    def __init__(self, model, device, mcts_simulations: int, temperature: float = 0.1, sample_moves: bool = False,
+                 seed: int = 0) -> None:
+        dev = torch.device(device)
+        from .net_hip import fused_supported
+        self.net = FusedNet(model.to(dev).eval(), dev) if fused_supported(model) else model.to(dev).eval()
+        self.evaluator = "fused_f16" if isinstance(self.net, FusedNet) else "torch"
+        self.device = dev
+        self.sims = max(1, int(mcts_simulations))
+        self.temperature = float(temperature)
+        self.sample_moves = bool(sample_moves)
+        self.seed = int(seed)
+        self._engines: Dict[int, Any] = {}
+
+    def engine(self, slots: int):
+        """This agent's own engine of `slots` slots (per-agent searches), built once per size."""
+        e = self._engines.get(int(slots))
+        if e is None:
+            e = _tree_engine([self], int(slots))
+            self._engines[int(slots)] = e
+        return e
+
+
+def _tree_engine(agents: Sequence[TreeSearchAgent], slots: int):
+    """One engine over `agents` (one segment of `slots` slots each when several)."""
+    from .tree_engine import PortableTreeMCTS
+    a = agents[0]
+    nets = [x.net for x in agents]
+    kw = dict(add_dirichlet_noise=False, sample_moves=a.sample_moves, reuse_tree=False, compact_evals=True, seed=a.seed)
+    if len(agents) == 1:
+        return PortableTreeMCTS(nets[0], slots, a.sims, a.device, **kw)
+    return PortableTreeMCTS(nets, slots * len(agents), a.sims, a.device, segment_games=slots, **kw)
+
+
+def _joint_engine(group: Sequence[TreeSearchAgent], slots: int):
+    """The engine that searches `group` together, kept on the first agent for the next match against the same networks.
+    Keyed by the networks themselves (the cached engine holds them, so no other object can take their ids while it is
+    kept) and the search settings; one joint engine per agent: another group replaces it."""
+    a = group[0]
+    key = ("joint", tuple(id(x.net) for x in group), int(slots), a.sims, a.sample_moves, a.seed)
+    eng = a._engines.get(key)
+    if eng is None or any(x is not y for x, y in zip(eng.nets, [x.net for x in group])):
+        for k in [k for k in a._engines if isinstance(k, tuple) and k[0] == "joint"]:
+            del a._engines[k]
+        eng = a._engines[key] = _tree_engine(group, slots)
+    return eng
+
+
+def _joinable(agents: Sequence[TreeSearchAgent]) -> bool:
+    """Tree agents one engine can search together: the same search settings (the networks may differ in anything)."""
+    a = agents[0]
+    return 2 <= len(agents) <= 8 and all(x.sims == a.sims and x.sample_moves == a.sample_moves and x.seed == a.seed and
+                                         x.device == a.device for x in agents)
+
+
+def _play_games(agents: Sequence[Any], player_a: torch.Tensor, player_b: torch.Tensor, a_black: torch.Tensor, device, *,
+                joint: bool = True, opening_random_moves: int = 0, max_game_plies: int = 512,
+                record_moves: bool = False):
+    """Tree-backend game loop: game g between agents player_a[g] (black iff a_black[g]) and player_b[g].  Returns
+    (result from black's side float32[n], move log int32[n, plies] or None)."""
+    dev = torch.device(device)
+    n = int(player_a.numel())
+    G = _pad16(n)
+    states = GpuStateBatch.initial(dev, n)
+    plies = torch.zeros((n,), dtype=torch.int64, device=dev)
+    done = torch.zeros((n,), dtype=torch.bool, device=dev)
+    result_black = torch.zeros((n,), dtype=torch.float32, device=dev)
+    pad_idx = torch.clamp(torch.arange(G, device=dev), max=n - 1)
+    game_ids = torch.arange(G, dtype=torch.int64, device=dev)
+    tree_ids = [k for k, a in enumerate(agents) if isinstance(a, TreeSearchAgent)]
+    joint_engine = None
+    if joint and len(tree_ids) >= 2 and _joinable([agents[k] for k in tree_ids]):
+        joint_engine = _joint_engine([agents[k] for k in tree_ids], G)
+    log = []
+    while True:
+        live = ~done
+        if not bool(live.any()):
+            break
+        mover = torch.where((states.current_player > 0) == a_black, player_a, player_b)
+        codes = torch.full((n, 4), -1, dtype=torch.int32, device=dev)
+        valid = torch.zeros((n,), dtype=torch.bool, device=dev)
+        term = torch.zeros((n,), dtype=torch.bool, device=dev)
+        opening = states.move_count < int(opening_random_moves)
+
+        def put(rows, c, v, t):
+            codes.index_copy_(0, rows, c.to(torch.int32))
+            valid.index_copy_(0, rows, v.to(torch.bool))
+            term.index_copy_(0, rows, t.to(torch.bool))
+
+        rows = torch.nonzero(live & opening).view(-1)
+        if int(rows.numel()) > 0:
+            put(rows, *_uniform_legal_codes(states.select(rows)))
+        search = live & ~opening
+        for k, agent in enumerate(agents):
+            if k in tree_ids:
+                continue
+            rows = torch.nonzero(search & (mover == k)).view(-1)
+            if int(rows.numel()) > 0:
+                put(rows, *agent.select(states.select(rows), None))
+        if tree_ids and bool(search.any()):
+            groups = [tree_ids] if joint_engine is not None else [[k] for k in tree_ids]
+            padded = states.select(pad_idx)
+            ply_pad = plies.index_select(0, pad_idx)
+            for group in groups:
+                want = [torch.zeros((G,), dtype=torch.bool, device=dev) for _ in group]
+                for w, k in zip(want, group):
+                    w[:n] = search & (mover == k)
+                if not any(bool(w.any()) for w in want):
+                    continue
+                eng = joint_engine if len(group) > 1 else agents[group[0]].engine(G)
+                K = len(group)
+                st = padded if K == 1 else padded.select(torch.arange(K * G, device=dev) % G)
+                temps = torch.cat([torch.full((G,), agents[k].temperature, dtype=torch.float32, device=dev) for k in group])
+                out = eng.search_batch(st, temperatures=temps, active=torch.cat(want), add_dirichlet_noise=False,
+                                       rng_game_ids=game_ids.repeat(K), rng_plies=ply_pad.repeat(K))
+                for j, w in enumerate(want):
+                    rows = torch.nonzero(w[:n]).view(-1)
+                    if int(rows.numel()) > 0:
+                        src = rows + j * G
+                        put(rows, out.chosen_action_codes.index_select(0, src), out.chosen_valid_mask.index_select(0, src),
+                            out.terminal_mask.index_select(0, src))
+        active = torch.nonzero(live).view(-1)
+        c, v, t = codes.index_select(0, active), valid.index_select(0, active), term.index_select(0, active)
+        if record_moves:
+            row = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            row.index_copy_(0, active, torch.where(v & ~t, codes_to_indices(c), torch.full_like(c[:, 0], -1)))
+            log.append(row)
+        fin, res, _soft = v0_core.self_play_step_inplace(*states.tensors(), plies, done, active, c, t, v,
+                                                         int(max_game_plies), 2.0)
+        if int(fin.numel()) > 0:
+            result_black.index_copy_(0, fin, res)
+    return result_black, (torch.stack(log, dim=1) if (record_moves and log) else None)
+
+
+def _stats(result_black: torch.Tensor, challenger_black: torch.Tensor, move_log) -> EvaluationStats:
+    n = int(result_black.numel())
+    res = torch.where(challenger_black, result_black, -result_black)
+    win, loss, draw = res > 0, res < 0, res == 0
+    cb = {}
+    for name, sel in (("black", challenger_black), ("white", ~challenger_black)):
+        cb[name] = {"wins": int((win & sel).sum()), "losses": int((loss & sel).sum()), "draws": int((draw & sel).sum()),
+                    "games": int(sel.sum())}
+    return EvaluationStats(wins=int(win.sum()), losses=int(loss.sum()), draws=int(draw.sum()), total_games=n,
+                           color_breakdown=cb, move_log=move_log)
+
+
 def play_matches(challenger, opponent, num_games: int, device, *, opening_random_moves: int = 0,
-                 max_game_plies: int = 512, seed: Optional[int] = None, record_moves: bool = False) -> EvaluationStats:
+                 max_game_plies: int = 512, seed: Optional[int] = None, record_moves: bool = False,
+                 joint: bool = True) -> EvaluationStats:
     """All `num_games` games at once on `device`; returns the challenger's W/L/D (`record_moves`: plus every game's
-    sequence of 220-d action indices in `move_log`)."""
+    sequence of 220-d action indices in `move_log`).  With a `TreeSearchAgent` on either side the tree backend's loop
+    runs; `joint` (two tree agents): one search per ply over both sides' games, else one per agent."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("eval arena needs a HIP device (no CPU path)")
@@ -116,6 +279,13 @@ def play_matches(challenger, opponent, num_games: int, device, *, opening_random
         torch.manual_seed(int(seed))
         torch.cuda.manual_seed(int(seed))
     n = int(num_games)
+    if isinstance(challenger, TreeSearchAgent) or isinstance(opponent, TreeSearchAgent):
+        challenger_black = torch.arange(n, device=dev) < (n / 2)
+        res, log = _play_games([challenger, opponent], torch.zeros((n,), dtype=torch.int64, device=dev),
+                               torch.ones((n,), dtype=torch.int64, device=dev), challenger_black, dev, joint=joint,
+                               opening_random_moves=opening_random_moves, max_game_plies=max_game_plies,
+                               record_moves=record_moves)
+        return _stats(res, challenger_black, log)
     states = GpuStateBatch.initial(dev, n)
     plies = torch.zeros((n,), dtype=torch.int64, device=dev)
     done = torch.zeros((n,), dtype=torch.bool, device=dev)
@@ -176,18 +346,87 @@ def load_checkpoint_model(path: str):
     return model.eval()
 
 
+SEARCH_BACKENDS = ("v1", "portable")
+
+
+def make_agent(model, search_backend: str, device, mcts_simulations: int, temperature: float, sample_moves: bool,
+               seed: int = 0):
+    """`search_backend` "v1" (root PUCT, RootSearchAgent) or "portable" (the tree search, TreeSearchAgent)."""
+    if search_backend == "v1":
+        return RootSearchAgent(model, device, mcts_simulations, temperature, sample_moves)
+    if search_backend == "portable":
+        return TreeSearchAgent(model, device, mcts_simulations, temperature, sample_moves, seed=seed)
+    raise ValueError(f"search_backend must be one of {SEARCH_BACKENDS}, got {search_backend!r}")
+
+
 def evaluate_checkpoint(challenger_checkpoint: str, opponent_checkpoint: Optional[str] = None, *, num_games: int = 200,
                         device: str = "cuda:0", mcts_simulations: int = 64, temperature: float = 0.1,
                         sample_moves: bool = False, opening_random_moves: int = 0, max_game_plies: int = 512,
-                        seed: int = 0) -> Dict[str, Any]:
-    """vs-previous (two checkpoints) or vs-random (opponent None) probe; payload as eval_checkpoint.py:139-154."""
+                        seed: int = 0, search_backend: str = "v1") -> Dict[str, Any]:
+    """vs-previous (two checkpoints) or vs-random (opponent None) probe; payload as eval_checkpoint.py:139-154.
+    `search_backend`: "v1" (root PUCT) or "portable" (the tree search, both sides in one engine)."""
     games = int(num_games) if int(num_games) % 2 == 0 else max(2, (int(num_games) // 2) * 2)   # even (:48-54)
-    chall = RootSearchAgent(load_checkpoint_model(challenger_checkpoint), device, mcts_simulations, temperature,
-                            sample_moves)
-    opp = RandomAgent() if not opponent_checkpoint else RootSearchAgent(
-        load_checkpoint_model(opponent_checkpoint), device, mcts_simulations, temperature, sample_moves)
+    if search_backend not in SEARCH_BACKENDS:
+        raise ValueError(f"search_backend must be one of {SEARCH_BACKENDS}, got {search_backend!r}")
+    chall = make_agent(load_checkpoint_model(challenger_checkpoint), search_backend, device, mcts_simulations,
+                       temperature, sample_moves, seed)
+    opp = RandomAgent() if not opponent_checkpoint else make_agent(
+        load_checkpoint_model(opponent_checkpoint), search_backend, device, mcts_simulations, temperature, sample_moves,
+        seed)
     stats = play_matches(chall, opp, games, device, opening_random_moves=opening_random_moves,
                          max_game_plies=max_game_plies, seed=seed)
     payload = stats.to_payload("vs_previous" if opponent_checkpoint else "vs_random")
     payload["seed"] = int(seed)
     return payload
+
+
+@dataclass
+class RoundRobinResult:
+    wdl: torch.Tensor                         # int64[K, K, 3]: wins / draws / losses of model i against model j
+    points: List[int]                         # 3 per win, 1 per draw (tournament_v1_eval.py:28-30)
+    pairs: List[tuple]                        # (i, j) in the order their games were laid out
+    pair_stats: Dict[tuple, EvaluationStats]  # model i's W/L/D against j (i < j), move logs if recorded
+
+    def to_payload(self, names: Optional[Sequence[str]] = None) -> Dict[str, Any]:
+        K = int(self.wdl.shape[0])
+        names = list(names) if names is not None else [str(i) for i in range(K)]
+        return {"models": names, "points": [int(p) for p in self.points],
+                "wdl": [[[int(x) for x in self.wdl[i, j]] for j in range(K)] for i in range(K)],
+                "pairs": [{"a": names[i], "b": names[j], **self.pair_stats[(i, j)].to_payload(f"{names[i]}_vs_{names[j]}")}
+                          for (i, j) in self.pairs]}
+
+
+def play_round_robin(models: Sequence[Any], games_per_pair: int, device, *, joint: bool = True,
+                     opening_random_moves: int = 0, max_game_plies: int = 512, seed: Optional[int] = None,
+                     record_moves: bool = False) -> RoundRobinResult:
+    """Every pair (i < j) of up to 8 agents (TreeSearchAgents in one engine, one segment each, when `joint`) plays
+    `games_per_pair` games, i black in the first half of them; all games at once.  Pair (i, j)'s games are what
+    play_matches(models[i], models[j], games_per_pair) plays when no random moves are drawn."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("eval arena needs a HIP device (no CPU path)")
+    K, m = len(models), int(games_per_pair)
+    if not 2 <= K <= 8 or m < 1:
+        raise ValueError("a round robin takes 2..8 models and at least one game per pair")
+    if seed is not None:
+        torch.manual_seed(int(seed))
+        torch.cuda.manual_seed(int(seed))
+    pairs = [(i, j) for i in range(K) for j in range(i + 1, K)]
+    first = torch.arange(m, device=dev) < (m / 2)
+    pa = torch.cat([torch.full((m,), i, dtype=torch.int64, device=dev) for i, _ in pairs])
+    pb = torch.cat([torch.full((m,), j, dtype=torch.int64, device=dev) for _, j in pairs])
+    a_black = first.repeat(len(pairs))
+    res, log = _play_games(list(models), pa, pb, a_black, dev, joint=joint, opening_random_moves=opening_random_moves,
+                           max_game_plies=max_game_plies, record_moves=record_moves)
+    wdl = torch.zeros((K, K, 3), dtype=torch.int64)
+    points = [0] * K
+    pair_stats = {}
+    for p, (i, j) in enumerate(pairs):
+        sl = slice(p * m, (p + 1) * m)
+        st = _stats(res[sl], first, None if log is None else log[sl])
+        pair_stats[(i, j)] = st
+        wdl[i, j] = torch.tensor([st.wins, st.draws, st.losses])
+        wdl[j, i] = torch.tensor([st.losses, st.draws, st.wins])
+        points[i] += 3 * st.wins + st.draws
+        points[j] += 3 * st.losses + st.draws
+    return RoundRobinResult(wdl=wdl, points=points, pairs=pairs, pair_stats=pair_stats)

@@ -20,6 +20,7 @@ from .net_pack import NetPack, pack_model, BINS
 
 MAX_LAYERS = 96                 # include/liuzhou_hip.h: LZ_NET_MAX_LAYERS (stem + 2 per block + head convs)
 MAX_BLOCKS = (MAX_LAYERS - 2) // 2
+MAX_MULTI_NETS = 8              # lz_net_forward_packed_multi_f16 / lz_tree_search_multi
 
 
 class LzNetDesc(C.Structure):
@@ -207,6 +208,56 @@ class FusedNet:
         self.forward_into(x, None, None, None, None, val)
         self.last_value = val
         return val
+
+
+def multi_layout_key(net: "FusedNet") -> Optional[bytes]:
+    """What lz_net_forward_packed_multi_f16 requires networks of one launch to share: the descriptor without its two
+    buffer pointers.  None for networks it does not take (fp32-operand / split-fp16 modes)."""
+    if net.desc.flags & (4 | 8):
+        return None
+    d = LzNetDesc()
+    C.memmove(C.byref(d), C.byref(net.desc), C.sizeof(LzNetDesc))
+    d.wfrag = d.fparams = None
+    d.flags &= 3
+    return bytes(memoryview(d))
+
+
+def multi_compatible(nets) -> bool:
+    """Whether `nets` (FusedNets) can be evaluated in one multi-network launch."""
+    if not nets or len(nets) > MAX_MULTI_NETS or not all(isinstance(n, FusedNet) for n in nets):
+        return False
+    keys = {multi_layout_key(n) for n in nets}
+    return len(keys) == 1 and None not in keys
+
+
+class DescArray:
+    """`const LzNetDesc* const*` of several FusedNets (keeps the descriptors alive with it)."""
+
+    def __init__(self, nets) -> None:
+        self.nets = list(nets)
+        self.arr = (C.c_void_p * len(self.nets))(*[C.addressof(n.desc) for n in self.nets])
+
+    def __len__(self) -> int:
+        return len(self.nets)
+
+
+def forward_packed_multi(nets, packed: torch.Tensor, seg_off: torch.Tensor, capacity: Optional[int] = None):
+    """lz_net_forward_packed_multi_f16: network k evaluates rows [align16(seg_off[k]), seg_off[k + 1]) of the packed
+    states int64[N,4] (seg_off int64[len(nets) + 1] on the device).  Returns (log_p1, log_p2, log_pmc, value) of
+    `capacity` rows; rows outside every segment are left as allocated (zero)."""
+    L.require_hip(packed, "net_forward_packed_multi_f16")
+    x = packed.contiguous()
+    N = int(x.shape[0]) if capacity is None else int(capacity)
+    dev = x.device
+    lp1, lp2, lpm = (torch.zeros((N, 36), dtype=torch.float32, device=dev) for _ in range(3))
+    val = torch.zeros((N,), dtype=torch.float32, device=dev)
+    arr = DescArray(nets)
+    with torch.cuda.device(dev):
+        L.check(L.lib().lz_net_forward_packed_multi_f16(arr.arr, C.c_int32(len(arr)), L.ptr(x), L.i64(N),
+                                                        L.ptr(seg_off), L.ptr(lp1), L.ptr(lp2), L.ptr(lpm), None,
+                                                        L.ptr(val), L.stream_ptr(dev)),
+                "net_forward_packed_multi_f16")
+    return lp1, lp2, lpm, val
 
 
 def _flops(C: int, NB: int) -> float:

@@ -26,7 +26,7 @@ from . import v0_core
 from .game_rng import GameRng, PURPOSE_PICK
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput, TOTAL_ACTION_DIM, states_to_model_input, \
     encode_actions_fast
-from .net_hip import FusedNet, LzNetDesc
+from .net_hip import DescArray, FusedNet, LzNetDesc, MAX_MULTI_NETS, multi_compatible
 from .self_play_types import SelfPlayV1Stats
 from .streams import CAPTURE_MODE
 from .trajectory_buffer import TensorSelfPlayBatch, TensorTrajectoryBuffer
@@ -49,7 +49,8 @@ class LzTreeDesc(C.Structure):
                [(n, C.c_void_p) for n in ("live_state", "live_row", "live_count")] + [("live_count_cap", C.c_int64)] + \
                [(n, C.c_void_p) for n in ("pos_index", "node_value", "leaf_src", "share_count")] + [("pos_slots", C.c_int64)] + \
                [(n, C.c_void_p) for n in ("leaf_sym", "trace_sym", "sym_salt", "sym_game", "sym_ply")] + \
-               [("sym_seed", C.c_uint64), ("sym_mode", C.c_int32), ("sym_fixed", C.c_int32)]
+               [("sym_seed", C.c_uint64), ("sym_mode", C.c_int32), ("sym_fixed", C.c_int32)] + \
+               [("seg_games", C.c_int64), ("seg_off", C.c_void_p)]
 
 
 def parse_eval_symmetry(value) -> "str | int":
@@ -161,8 +162,12 @@ def samples_per_launch_pass(net) -> int:
 class TreeEngine:
     def __init__(self, num_games: int, max_sims: int, device, exploration_weight: float = 1.0,
                  reuse_factor: float = 0.0, batch_k: int = 1, edge_chunk: int = EDGE_CHUNK,
-                 pool_chunks: Optional[int] = None, compact_evals: bool = False, max_backtrack_steps: int = 0) -> None:
-        """`max_backtrack_steps` (batch_k > 1): the reference's MAX_BACKTRACK_STEPS (src/mcts.py:337; 0 = its 128).
+                 pool_chunks: Optional[int] = None, compact_evals: bool = False, max_backtrack_steps: int = 0,
+                 segment_games: Optional[int] = None) -> None:
+        """`segment_games`: the slots form num_games / segment_games segments of that many slots (a multiple of 16), slot
+        g searched with network g // segment_games (search_multi: one network launch per simulation for all segments,
+        compact lists always on).
+        `max_backtrack_steps` (batch_k > 1): the reference's MAX_BACKTRACK_STEPS (src/mcts.py:337; 0 = its 128).
         `compact_evals`: the fused search evaluates, per simulation, only the leaves that need the network (compact
         device-side list, `LzTreeDesc.live_*`) -- a launch then costs ceil(live / samples per pass) network passes instead
         of one per slot, so a draining wave gets cheaper as its games end; bit-identical results.
@@ -266,6 +271,20 @@ class TreeEngine:
         self.desc.eval_count = self.eval_count.data_ptr()
         self.share_count = z((B,), torch.int32)         # leaves that took a transposed twin's evaluation (LzTreeDesc.share_count)
         self.desc.share_count = self.share_count.data_ptr()
+        self.segment_games = None if segment_games is None else int(segment_games)
+        self.num_segments = 1
+        if self.segment_games is not None:
+            G = self.segment_games
+            if G <= 0 or G % 16 or B % G:
+                raise ValueError(f"segment_games must be a positive multiple of 16 dividing num_games, got {G} of {B}")
+            self.num_segments = B // G
+            if self.num_segments > MAX_MULTI_NETS:
+                raise ValueError(f"at most {MAX_MULTI_NETS} segments, got {self.num_segments}")
+            if self.batch_k > 1:
+                raise ValueError("segments (several networks) need batch_k = 1")
+            compact_evals = True
+            self.seg_off = z(((self.max_sims + 2) * (self.num_segments + 1),), torch.int64)
+            self.desc.seg_games, self.desc.seg_off = G, self.seg_off.data_ptr()
         self.compact_evals = bool(compact_evals) and self.batch_k == 1
         self.live_total = z((1,), torch.int64)          # compact_evals: evaluations launched so far (sum of the per-simulation counts)
         if self.compact_evals:
@@ -525,6 +544,28 @@ class TreeEngine:
             else:
                 self.live_total.add_(self.B * (int(sims) + 1))
 
+    def search_multi(self, nets, sims: int, noise: Optional[torch.Tensor] = None, epsilon: float = 0.25,
+                     continue_trees: bool = False) -> None:
+        """search() with one FusedNet per segment (lz_tree_search_multi): one network launch per simulation evaluates
+        every segment's leaves with its own network; each tree is the one search() builds with that network."""
+        if self.segment_games is None:
+            raise ValueError("search_multi needs an engine built with segment_games")
+        if len(nets) != self.num_segments:
+            raise ValueError(f"{self.num_segments} segments need as many networks, got {len(nets)}")
+        if int(sims) > self.max_sims:
+            raise ValueError(f"sims={sims} exceeds the arena capacity max_sims={self.max_sims}")
+        arr = nets if isinstance(nets, DescArray) else DescArray(nets)
+        fn = L.lib().lz_tree_search_multi_continue if continue_trees else L.lib().lz_tree_search_multi
+        nz_stride = int(noise.shape[1]) if noise is not None else 0
+        with torch.cuda.device(self.device):
+            L.check(fn(C.byref(self.desc), arr.arr, C.c_int32(len(arr)), L.i64(sims), L.ptr(self.lp1), L.ptr(self.lp2),
+                       L.ptr(self.lpm), L.ptr(self.values), L.ptr(noise), L.i64(nz_stride), C.c_float(float(epsilon)),
+                       self._stream()), "tree_search_multi")
+        # evaluations launched: the rows of every segment, not the padding between them (live_count is the padded total)
+        seg = self.seg_off[: (int(sims) + 1) * (len(arr) + 1)].view(int(sims) + 1, len(arr) + 1)
+        start = torch.div(seg[:, :-1] + 15, 16, rounding_mode="floor") * 16
+        self.live_total.add_((seg[:, 1:] - start).clamp_min(0).sum())
+
     def persistent_ok(self, net: FusedNet) -> bool:
         """Whether search() runs the one-launch-per-move kernel: 64-channel net in fp16 mode, not switched off
         (`persistent` attribute; env LZ_TREE_PERSISTENT=0)."""
@@ -582,8 +623,15 @@ class PortableTreeMCTS:
                  reuse_factor: float = -1.0, policy_target_temperature: Optional[float] = None,
                  policy_target_prior_pseudocount: float = 0.0, batch_k: int = 1, seed: int = 12345,
                  game_offset: int = 0, game_stride: Optional[int] = None, trace: bool = False,
-                 collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none") -> None:
-        """`eval_symmetry`: "none" (default), "random" or a fixed element id 0..7 -- every leaf is evaluated as
+                 collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none",
+                 segment_games: Optional[int] = None, multi_launch: bool = True) -> None:
+        """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
+        searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
+        FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
+        split-phase protocol, each segment's rows through its own evaluator.  Not with batch_k > 1, eval_symmetry or the
+        persistent kernel.  `multi_launch=False` takes the split-phase path for FusedNets too (parity tests).  A single
+        network behaves as below.
+        `eval_symmetry`: "none" (default), "random" or a fixed element id 0..7 -- every leaf is evaluated as
         sigma_k(leaf) and the heads are mapped back (parse_eval_symmetry, TreeEngine.set_eval_symmetry); not with
         batch_k > 1 (ValueError).  `compact_evals` (fused network only): per simulation only the leaves that need the network are evaluated
         (`TreeEngine(compact_evals=True)`); True = in every search; None = the engine is built for both forms when a launch
@@ -600,12 +648,27 @@ class PortableTreeMCTS:
         `reuse_tree`: keep the played child's subtree between consecutive search_batch calls on the same games
         (the reference's portable self-play does, v1/python/portable_self_play.py:191); the arenas then hold
         (1 + reuse_factor) * sims nodes per game (reuse_factor < 0: as much as a third of the free memory allows).  `policy_target_*`: portable_mcts.py:690-700."""
+        self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
+        self.multi = segment_games is not None
+        if not self.multi and len(self.nets) != 1:
+            raise ValueError("several networks need segment_games")
+        if self.multi:
+            if len(self.nets) * int(segment_games) != int(num_games):
+                raise ValueError(f"{len(self.nets)} networks x segment_games={segment_games} != num_games={num_games}")
+            if int(batch_k) > 1 or parse_eval_symmetry(eval_symmetry) != "none":
+                raise ValueError("several networks in one search: batch_k = 1 and eval_symmetry='none' only")
+            if sum(isinstance(n, PriorEvaluator) for n in self.nets) not in (0, len(self.nets)):
+                raise ValueError("PriorEvaluators and networks cannot share one search")
+            compact_evals = True
+        net = self.nets[0]
         self.net, self.sims = net, int(num_simulations)
-        self.fused = isinstance(net, FusedNet)
+        self.fused_multi = self.multi and bool(multi_launch) and multi_compatible(self.nets)
+        self.fused = isinstance(net, FusedNet) and (not self.multi or self.fused_multi)
+        self._desc_array = DescArray(self.nets) if self.fused_multi else None
         self.reuse_tree = bool(reuse_tree)
         self.batch_k = max(1, int(batch_k))
         env_c = os.environ.get("LZ_TREE_COMPACT", "").strip()
-        if env_c in ("0", "1"):
+        if env_c in ("0", "1") and not self.multi:
             compact_evals = env_c == "1"
         # asked for explicitly: every search uses the lists.  Chosen automatically: the engine can do both and launches
         # every slot unless a search is told otherwise (`compact=` of search_batch: the runner's hint that the wave is
@@ -617,13 +680,16 @@ class PortableTreeMCTS:
             self.compact_default = compact_evals and self.batch_k == 1 and shares_leaves(num_games)
         self.engine = TreeEngine(num_games, num_simulations, device, exploration_weight,
                                  reuse_factor=float(reuse_factor) if self.reuse_tree else 0.0, batch_k=self.batch_k,
-                                 compact_evals=bool(compact_evals) and self.fused and self.batch_k == 1)
+                                 compact_evals=bool(compact_evals) and self.fused and self.batch_k == 1,
+                                 segment_games=segment_games if self.fused_multi else None)
         if trace:
             self.engine.enable_trace()
         if not self.fused:
             if self.batch_k > 1:
                 raise ValueError("an external evaluator supports batch_k = 1 only")
-            self._eval_device = None if isinstance(net, PriorEvaluator) else next(net.parameters()).device
+            self._eval_devices = [None if isinstance(n, PriorEvaluator) else
+                                  (n.device if isinstance(n, FusedNet) else next(n.parameters()).device) for n in self.nets]
+            self._eval_device = self._eval_devices[0]
         self.rng = GameRng(num_games, device, seed=seed, game_offset=game_offset, game_stride=game_stride)
         self.eval_symmetry = parse_eval_symmetry(eval_symmetry)
         self.engine.set_eval_symmetry(self.eval_symmetry, seed, self.rng.game, self.rng.ply)
@@ -688,15 +754,20 @@ class PortableTreeMCTS:
             self._timing_ms, self._timing_calls = {}, {}
         return out
 
-    def _evaluate_external(self, planes: torch.Tensor):
+    def _evaluate_external(self, planes: torch.Tensor, net=None, eval_device=None):
         """External fp32 evaluator: module(planes) -> (log_p1, log_p2, log_pmc, value_logits); scalar value = bucket
         expectation (src/neural_network.py:201-210), everything back on the engine's device."""
         dev = self.engine.device
+        net = self.net if net is None else net
+        eval_device = self._eval_device if eval_device is None else eval_device
         with torch.inference_mode():
-            lp1, lp2, lpm, raw = self.net(planes.to(self._eval_device))
-            probs = torch.softmax(raw.float(), dim=-1)
-            centers = torch.linspace(-1.0, 1.0, steps=raw.shape[-1], dtype=probs.dtype, device=probs.device)
-            val = (probs * centers).sum(-1)
+            lp1, lp2, lpm, raw = net(planes.to(eval_device))
+            if raw.dim() == 2 and int(raw.shape[1]) == 1:          # a scalar value head (portable_mcts.py:374-375)
+                val = raw[:, 0].float()
+            else:
+                probs = torch.softmax(raw.float(), dim=-1)
+                centers = torch.linspace(-1.0, 1.0, steps=raw.shape[-1], dtype=probs.dtype, device=probs.device)
+                val = (probs * centers).sum(-1)
         f = lambda t: t.float().to(dev).contiguous()
         return f(lp1), f(lp2), f(lpm), f(val)
 
@@ -707,6 +778,9 @@ class PortableTreeMCTS:
         for s in range(self.sims + 1):
             if s > 0:
                 e.select()
+            if self.multi:
+                self._expand_segments(s, noise)
+                continue
             if isinstance(self.net, PriorEvaluator):
                 pri, val = self.net(e.leaf_planes(), e.buf["leaf_state"])
                 e.expand(is_root=(s == 0), values=val.to(torch.float32).contiguous(),
@@ -715,6 +789,46 @@ class PortableTreeMCTS:
             lp1, lp2, lpm, val = self._evaluate_external(e.leaf_planes())
             e.expand(is_root=(s == 0), values=val, heads=(lp1, lp2, lpm), noise=noise if s == 0 else None,
                      epsilon=self.eps)
+
+    def _expand_segments(self, s: int, noise: Optional[torch.Tensor]) -> None:
+        """Split-phase step with one evaluator per segment: segment k's leaves that need the network (leaf_kind 1: not
+        inactive slots, terminal leaves) go to network k, as the compact lists of the fused path; the other rows are
+        never read by the expand step and stay zero."""
+        e = self.engine
+        planes = e.leaf_planes()
+        G = e.B // len(self.nets)
+        need = e.buf["leaf_kind"] == 1
+        prior_mode = isinstance(self.nets[0], PriorEvaluator)
+        if prior_mode:
+            pri = torch.zeros((e.B, TOTAL_ACTION_DIM), dtype=torch.float32, device=e.device)
+        heads = [torch.zeros((e.B, 36), dtype=torch.float32, device=e.device) for _ in range(3)]
+        val = torch.zeros((e.B,), dtype=torch.float32, device=e.device)
+        for k, n in enumerate(self.nets):
+            rows = torch.nonzero(need[k * G:(k + 1) * G]).view(-1) + k * G
+            if int(rows.numel()) == 0:
+                continue
+            if prior_mode:
+                p, v = n(planes.index_select(0, rows), e.buf["leaf_state"].index_select(0, rows))
+                pri.index_copy_(0, rows, p.to(torch.float32))
+                val.index_copy_(0, rows, v.to(torch.float32).view(-1))
+                continue
+            if isinstance(n, FusedNet):                            # the fused search's own input: packed leaves
+                lp1, lp2, lpm, _, v = n.forward_packed(e.buf["leaf_state"].index_select(0, rows))
+            else:
+                lp1, lp2, lpm, v = self._evaluate_external(planes.index_select(0, rows), n, self._eval_devices[k])
+            for h, x in zip(heads, (lp1, lp2, lpm)):
+                h.index_copy_(0, rows, x.reshape(-1, 36))
+            val.index_copy_(0, rows, v.view(-1))
+        if prior_mode:
+            e.expand(is_root=(s == 0), values=val, priors220=pri, noise=noise if s == 0 else None, epsilon=self.eps)
+        else:
+            e.expand(is_root=(s == 0), values=val, heads=tuple(heads), noise=noise if s == 0 else None, epsilon=self.eps)
+
+    def _run_search(self, sims: int, noise, continue_trees: bool, lists: bool) -> None:
+        if self.fused_multi:
+            self.engine.search_multi(self._desc_array, sims, noise, self.eps, continue_trees)
+        else:
+            self.engine.search(self.net, sims, noise, self.eps, continue_trees, compact=lists)
 
     def _search(self, add_noise: bool, continue_trees: bool) -> None:
         e = self.engine
@@ -726,7 +840,7 @@ class PortableTreeMCTS:
         self.list_searches = getattr(self, "list_searches", 0) + int(lists)      # searches that used the compact lists
         self.last_search_lists = lists
         if not self.use_graph:
-            e.search(self.net, self.sims, noise, self.eps, continue_trees, compact=lists)
+            self._run_search(self.sims, noise, continue_trees, lists)
             return
         key = (add_noise, continue_trees, lists)
         g = self._graphs.get(key)
@@ -741,14 +855,14 @@ class PortableTreeMCTS:
                 # (an engine with compact lists warms up both launch forms: the other one may be captured later inside a
                 #  continued search, which cannot be preceded by a warm-up of its own)
                 counted = (e.live_total.clone(), e.eval_count.clone(), e.share_count.clone())   # warm-ups are not searches
-                for form in ((lists, not lists) if e.compact_evals else (lists,)):
-                    e.search(self.net, min(self.sims, 2), noise, self.eps, False, compact=form)
+                for form in ((lists, not lists) if (e.compact_evals and not self.fused_multi) else (lists,)):
+                    self._run_search(min(self.sims, 2), noise, False, form)
                 e.live_total.copy_(counted[0]); e.eval_count.copy_(counted[1]); e.share_count.copy_(counted[2])
             torch.cuda.synchronize(e.device)
             try:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                    e.search(self.net, self.sims, noise, self.eps, continue_trees, compact=lists)
+                    self._run_search(self.sims, noise, continue_trees, lists)
                 if os.environ.get("LZ_TREE_GRAPH_FAULT", "") == "capture":      # test hook: pretend the capture failed
                     raise RuntimeError("injected stream capture failure (LZ_TREE_GRAPH_FAULT=capture)")
             except RuntimeError as exc:
@@ -761,7 +875,7 @@ class PortableTreeMCTS:
                 self._graphs.clear()
                 print(f"[liuzhou_amd] hipGraph capture of the tree search failed ({exc!r}); falling back to direct launches",
                       flush=True)
-                e.search(self.net, self.sims, noise, self.eps, continue_trees, compact=lists)
+                self._run_search(self.sims, noise, continue_trees, lists)
                 return
             self._graphs[key] = g
         g.replay()

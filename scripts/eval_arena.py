@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Checkpoint evaluation on the device-resident arena: the `--backend v1` path of the reference's
-`scripts/eval_checkpoint.py` (flags of :831-872; other backends' flags are accepted and ignored).
+"""Checkpoint evaluation on the device-resident arena: the `--backend v1` (root PUCT) and `--backend portable` (full-tree
+search, both checkpoints in one engine) paths of the reference's `scripts/eval_checkpoint.py` (flags of :831-872; other
+backends run the v1 path, other backends' flags are accepted and ignored).  The result records the backend that ran.
 
     python scripts/eval_arena.py --challenger_checkpoint ck/model_iter_003.pt --previous_checkpoint ck/best.pt \
         --eval_games_vs_random 200 --eval_games_vs_previous 400 --mcts_simulations 256 --output_json out/eval.json
@@ -21,6 +22,8 @@ def parse(argv=None):
     ap.add_argument("--previous_checkpoint", default=None)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--backend", default="v1")
+    ap.add_argument("--portable_mcts_backend", default=None)      # accepted, no effect: one tree-search implementation
+    ap.add_argument("--portable_cpp_threads", type=int, default=None)   # accepted, no effect
     ap.add_argument("--mcts_simulations", type=int, default=256)
     ap.add_argument("--temperature", type=float, default=0.05)
     ap.add_argument("--sample_moves", action="store_true")
@@ -35,14 +38,22 @@ def parse(argv=None):
     return args
 
 
+def backend_of(args) -> str:
+    """The search that runs: "portable" (tree search) when asked for, "v1" (root PUCT) for anything else."""
+    return "portable" if str(args.backend).strip().lower() == "portable" else "v1"
+
+
 def main(argv=None) -> int:
     args = parse(argv)
     from liuzhou_amd.eval_arena import evaluate_checkpoint
     seed = 0 if args.seed is None else int(args.seed)
+    backend = backend_of(args)
     common = dict(device=args.device, mcts_simulations=args.mcts_simulations, temperature=args.temperature,
                   sample_moves=bool(args.sample_moves), opening_random_moves=args.v1_opening_random_moves, seed=seed)
+    if backend != "v1":
+        common["search_backend"] = backend
     out = {"challenger_checkpoint": args.challenger_checkpoint, "previous_checkpoint": args.previous_checkpoint,
-           "backend": "v1", "mcts_simulations": int(args.mcts_simulations), "seed": seed}
+           "backend": backend, "mcts_simulations": int(args.mcts_simulations), "seed": seed}
     if args.eval_games_vs_random > 0:
         out["vs_random"] = evaluate_checkpoint(args.challenger_checkpoint, None, num_games=args.eval_games_vs_random, **common)
     if args.eval_games_vs_previous > 0 and args.previous_checkpoint:
