@@ -231,13 +231,15 @@ LZ_API int lz_finalize_trajectory_inplace(float* value_targets, float* soft_valu
  * finished slots); *cursor += live count.  A row >= capacity or a full step_index row drops the sample and bumps
  * *overflow (the host sizes both so that this never happens).
  * cursor == NULL and step_index_matrix == NULL select the SLOT-MAJOR arena of the finished-row log
- * (lz_wave_log_finished): the row of slot g's step n is g * max_steps + n, capacity >= num_slots * max_steps. */
+ * (lz_wave_log_finished): the row of slot g's step n is g * max_steps + n, capacity >= num_slots * max_steps.
+ * record (optional uint8[num_slots], the playout cap's full searches): a live slot with record[g] == 0 records nothing
+ * (rows[g] = -1, step_counts unchanged, no cursor advance); the recorded slots' rows stay dense.  NULL: every live slot. */
 LZ_API int lz_wave_record(const uint8_t* done, int64_t num_slots, int64_t* cursor, int64_t capacity,
                           int64_t max_steps, int64_t* step_index_matrix, int64_t* step_counts, int64_t* rows,
                           int32_t* overflow, const float* model_input, const uint8_t* legal_mask,
                           const float* policy_dense, const int64_t* current_player, int64_t action_dim,
                           float* arena_state, uint8_t* arena_legal, float* arena_policy, float* arena_value,
-                          float* arena_soft, int8_t* arena_sign, void* stream);
+                          float* arena_soft, int8_t* arena_sign, const uint8_t* record, void* stream);
 
 /* lz_wave_step_finish: for every live slot apply chosen_action_codes[g] (self_play_step_inplace rules,
  * module.cpp:724-856); a game that ends has value = sign*result / soft = sign*tanh(k*delta/18) written over its rows
@@ -245,14 +247,17 @@ LZ_API int lz_wave_record(const uint8_t* done, int64_t num_slots, int64_t* curso
  * delta_hist int64[37] (optional) += final black-white piece difference clamped to [-18,18], lengths[slot_game ?
  * slot_game[g] : g] (optional) = recorded steps, *finished (optional) += 1.  reseat == 0: done[g] = 1.  reseat != 0: the slot restarts from the empty
  * board (plies, step_counts = 0, reseated[g] = 1 if given) -- the steady-state population of bench.py.
- * step_index_matrix == NULL: slot-major arena, the rows of slot g are g * max_steps + [0, step_counts[g]). */
+ * step_index_matrix == NULL: slot-major arena, the rows of slot g are g * max_steps + [0, step_counts[g]).
+ * game_plies (optional, indexed like lengths; the playout cap, where not every search records a row): = the searches
+ * the game made (plies played, + 1 when it ended at a searched terminal root), and a game is booked in outcome by
+ * those, not by its recorded rows -- a game all of whose searches were fast still counts.  NULL: as above. */
 LZ_API int lz_wave_step_finish(const LzStateSoA* states, int64_t num_slots, int64_t* plies, uint8_t* done,
                                const int32_t* chosen_action_codes, const uint8_t* terminal_mask,
                                const uint8_t* chosen_valid_mask, int64_t max_game_plies, float soft_value_k,
                                float* value_targets, float* soft_value_targets, const int8_t* player_signs,
                                const int64_t* step_index_matrix, int64_t* step_counts, int64_t max_steps,
                                int64_t* outcome, int64_t* delta_hist, int64_t* lengths, const int64_t* slot_game,
-                               int64_t* finished, uint8_t* reseated, int reseat, void* stream);
+                               int64_t* finished, uint8_t* reseated, int reseat, int64_t* game_plies, void* stream);
 
 /* lz_wave_reseat: the wave loop of self_play_gpu_runner.py:84-90 starts the next `concurrent_games` games only when the
  * whole wave has finished; here finished slots (done[g] != 0, ascending g) restart from the empty board at once while
@@ -472,6 +477,14 @@ typedef struct LzTreeDesc {
      * live_count[s] = the padded total. */
     int64_t  seg_games;
     int64_t* seg_off;              /* [live_count_cap * (num_nets + 1)] */
+    /* Optional playout cap (lz_tree_search / lz_tree_search_continue only; NULL = off, every game runs `sims` and
+     * gets the noise mix when noise is passed).  Both arrays are device memory read at every launch, so one captured
+     * graph serves every ply whatever its mix of budgets.  A game with budget b expands the leaf of its simulation b and
+     * selects nothing more: its tree is bit for bit the one a search with sims = b builds, and it leaves the compact
+     * lists.  root_noise[g] == 0: no noise mix on game g's root (neither a fresh root nor a kept one).  The other search
+     * entry points refuse a descriptor that sets either array (LZ_ERR_UNSUPPORTED). */
+    const int32_t* sim_budget;     /* [B] simulations of this search per game (values above sims: sims) */
+    const uint8_t* root_noise;     /* [B] 0: no root noise for game g */
 } LzTreeDesc;
 LZ_API int64_t lz_tree_desc_bytes(void);
 
@@ -568,7 +581,8 @@ LZ_API int lz_tree_search_multi_continue(const LzTreeDesc* tree, const LzNetDesc
  * every variate is a pure function of those, so a game plays the same moves whichever slot / stream / rank runs it.
  *   lz_rng_gamma:   out[g*stride + k] = Gamma(alpha, 1) draw k of game_id[g] at ply[g], k < count (Marsaglia-Tsang);
  *                   normalised over a game's legal children these are Dirichlet(alpha) noise.
- *   lz_rng_uniform: out[g] = uniform [0,1) for `purpose` (1 = move pick, 2 = opening move) of game_id[g] at ply[g].
+ *   lz_rng_uniform: out[g] = uniform [0,1) for `purpose` (1 = move pick, 2 = opening move, 3 = full / fast search of
+ *                   the playout cap) of game_id[g] at ply[g].
  * game_id NULL: g itself; ply NULL: 0. */
 LZ_API int lz_rng_gamma(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t batch, float alpha,
                         int64_t count, float* out, int64_t stride, void* stream);

@@ -90,19 +90,23 @@ __global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t) {
 
 // COMPACT: the evaluator rows are those of the compact list (Tree::live_row); tree_expand indexes its inputs with g, so
 // the base pointers are shifted by row - g (rows of leaves that needed no evaluation are never read for their content)
-template <bool IS_ROOT, bool COMPACT = false>
+// CAP (here and in the expand + select kernels): the playout cap's per-game budgets and root noise switch (`cap`); the
+// default instantiations never read them.  A fast search (root_noise[g] == 0) gets no mix at all: neither on a fresh
+// root nor on a kept one.
+template <bool IS_ROOT, bool COMPACT = false, bool CAP = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_kernel(Tree t, const float* __restrict__ lp1,
                                                              const float* __restrict__ lp2,
                                                              const float* __restrict__ lpm,
                                                              const float* __restrict__ priors220,
                                                              const float* __restrict__ values,
                                                              const float* __restrict__ noise, int noise_stride,
-                                                             float epsilon, int step) {
+                                                             float epsilon, int step, CapArrays cap) {
     LZ_EXPAND_SCRATCH(sc);
     const int g = wave_game();
     if (g >= t.B) return;
     ptrdiff_t o = 0;
     if (COMPACT) o = (ptrdiff_t)(t.leaf_kind[g] == kLeafExpand ? t.live_row[g] : 0) - g;
+    if (CAP && IS_ROOT && !cap_noise(cap, g)) noise = nullptr;
     tree_expand<IS_ROOT>(t, g, lane_id(), lp1 ? lp1 + o * 36 : nullptr, lp2 ? lp2 + o * 36 : nullptr,
                          lpm ? lpm + o * 36 : nullptr, priors220 ? priors220 + o * 220 : nullptr, values + o, noise,
                          noise_stride, epsilon, sc, nullptr, step);
@@ -234,13 +238,13 @@ __global__ __launch_bounds__(kScanBlock) void tree_live_scan_seg_kernel(Tree t, 
 // expand + backup of simulation s fused with the selection of simulation s+1 (same wave, same game: the edge
 // records it just touched are still in L1/L2) -- one launch per simulation besides the network kernel.
 // (forcing 8 waves / SIMD -- <= 96 SGPRs, 126 scalar spills -- was measured: no gain at 16 384 games, 1 % slower at C2)
-template <bool IS_ROOT, bool COMPACT = false>
+template <bool IS_ROOT, bool COMPACT = false, bool CAP = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, const float* __restrict__ lp1,
                                                                     const float* __restrict__ lp2,
                                                                     const float* __restrict__ lpm,
                                                                     const float* __restrict__ values,
                                                                     const float* __restrict__ noise, int noise_stride,
-                                                                    float epsilon, int step) {
+                                                                    float epsilon, int step, CapArrays cap) {
 #ifndef LZ_EXP_NO_TREE_PRIO
     // The kernel is a chain of dependent loads with a few dozen instructions in between; in the two-stream search it
     // shares the SIMDs with the other half's network waves, which always have MFMAs to issue.  Raised wave priority
@@ -257,9 +261,14 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
 #ifdef LZ_EXP_TREE_STAMPS
     const unsigned long long lz_t0 = __builtin_readcyclecounter();
 #endif
+    if (CAP && IS_ROOT && !cap_noise(cap, g)) noise = nullptr;
     tree_expand<IS_ROOT>(t, g, lane, lp1 + o * 36, lp2 + o * 36, lpm + o * 36, nullptr, values + o, noise, noise_stride,
                          epsilon, sc, &root, step, nullptr, nullptr LZ_TSTAMP_PASS);
     __threadfence_block();
+    if (CAP && cap_spent(cap, g, step)) {                        // budget spent: no further leaf, out of the lists
+        if (lane == 0) t.leaf_kind[g] = kLeafInactive;
+        return;
+    }
     if (IS_ROOT) root = load_root_info(t, g);                  // the root record itself was just written
     LZ_TSTAMP(g, 7)                                            // fence (+ root reload)
     tree_select(t, g, lane, root, -1, -1, nullptr LZ_TSTAMP_PASS);
@@ -280,11 +289,12 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
 // this kernel; LZ_TREE_SPLIT=0 takes the one-wave kernel, tests/test_gpu_tree.py compares the two).  Used for launches of
 // at most kSplitMaxGames games: at 16 384 games the SIMDs are issue-bound and twice the waves buy nothing.
 constexpr int kSplitMaxGames = 8192;
-template <bool COMPACT>
+template <bool COMPACT, bool CAP = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_select_split_kernel(Tree t, const float* __restrict__ lp1,
                                                                           const float* __restrict__ lp2,
                                                                           const float* __restrict__ lpm,
-                                                                          const float* __restrict__ values, int step) {
+                                                                          const float* __restrict__ values, int step,
+                                                                          CapArrays cap) {
     __builtin_amdgcn_s_setprio(3);
     LZ_EXPAND_SCRATCH(sc);
     __shared__ int s_flag[kWavesPerBlock / 2];
@@ -310,6 +320,10 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_split_kernel(Tree t
                               &root, step, flag, &split);
         __threadfence_block();
         split_wait(flag, kSplitInputsRead);                        // the descent's end overwrites the leaf record
+        if (CAP && cap_spent(cap, g, step)) {                      // budget spent (after the partner read leaf_kind)
+            if (lane == 0) t.leaf_kind[g] = kLeafInactive;
+            return;
+        }
         tree_select(t, g, lane, root, split.wait_edge, split.nolegal_edge, flag);
     }
 }
@@ -1331,6 +1345,7 @@ int lz_tree_begin(const LzTreeDesc* d, void* stream) {
 
 int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (!tree_ok(d)) return LZ_ERR_ARG;
+    if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: lz_tree_search only
     if (d->num_games == 0) return LZ_OK;
     hipLaunchKernelGGL(tree_select_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), no_share(make_tree(d)));
     return st();
@@ -1340,15 +1355,16 @@ int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const flo
                    const float* priors220, const float* values, const float* noise, int64_t noise_stride,
                    float epsilon, void* stream) {
     if (!tree_ok(d) || !values) return LZ_ERR_ARG;
+    if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
     if (!priors220 && (!lp1 || !lp2 || !lpmc)) return LZ_ERR_ARG;
     if (d->num_games == 0) return LZ_OK;
     const Tree t = no_share(make_tree(d));
     if (is_root)
         hipLaunchKernelGGL(tree_expand_kernel<true>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                           lpmc, priors220, values, noise, (int)noise_stride, epsilon, -1);
+                           lpmc, priors220, values, noise, (int)noise_stride, epsilon, -1, CapArrays{});
     else
         hipLaunchKernelGGL(tree_expand_kernel<false>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                           lpmc, priors220, values, nullptr, 0, 0.f, -1);
+                           lpmc, priors220, values, nullptr, 0, 0.f, -1, CapArrays{});
     return st();
 }
 
@@ -1420,19 +1436,13 @@ int lz_tree_advance(const LzTreeDesc* d, const int32_t* played_action, const uin
 // Whole search of one move, enqueued from C++ (no Python in the simulation loop, hipGraph-capturable):
 //   begin -> [net -> expand_root + select] -> (sims-1) x [net -> expand+backup + select] -> net -> expand+backup
 // `continue_trees`: the roots were prepared by lz_tree_advance (kept subtrees or fresh roots), so no begin.
-static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t sims, float* planes, float* lp1,
-                            float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
-                            float epsilon, bool continue_trees, void* stream) {
-    if (!tree_ok(d) || !net || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
+// CAP: the kernels of the playout cap (LzTreeDesc.sim_budget / root_noise), the same launch sequence.
+extern "C++" template <bool CAP>
+static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const LzNetDesc* net, int64_t sims, float* lp1,
+                              float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
+                              float epsilon, void* stream) {
     const int64_t B = d->num_games;
-    if (B == 0) return LZ_OK;
-    int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
-    if (rc) return rc;
-    (void)planes;   // the network kernel stages its input straight from the 32-byte packed leaf states
-    // Shared leaves (position index) only in the one-wave step, whose evaluator is this network: its outputs are a
-    // function of the packed state alone.  The step-by-step entry points (external evaluators) and the two-wave split
-    // step (where the descent runs beside the expansion that inserts into the index) keep the index but do not look it up.
-    const Tree t = split_step(B) ? no_share(make_tree(d)) : make_tree(d);
+    int rc = LZ_OK;
     if (t.live_count != nullptr) {
         // compact evaluation lists: simulation s evaluates live_count[s] leaves (see LzTreeDesc.live_*)
         if (d->live_count_cap < sims + 2) return LZ_ERR_ARG;
@@ -1443,22 +1453,22 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
             if (rc) return rc;
             if (s == sims) {
                 if (s == 0)
-                    hipLaunchKernelGGL((tree_expand_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                       lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s);
+                    hipLaunchKernelGGL((tree_expand_kernel<true, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
+                                       lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, cap);
                 else
-                    hipLaunchKernelGGL((tree_expand_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                       lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s);
+                    hipLaunchKernelGGL((tree_expand_kernel<false, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
+                                       lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap);
             } else if (s == 0) {
-                hipLaunchKernelGGL((tree_expand_select_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s);
+                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap);
             } else {
                 (void)lz_prof_aux_begin(0, stream);
                 if (split_step(t.B))
-                    hipLaunchKernelGGL((tree_expand_select_split_kernel<true>), dim3(gw2(t.B)), dim3(kBlock), 0,
-                                       as_stream(stream), t, lp1, lp2, lpmc, values, (int)s);
+                    hipLaunchKernelGGL((tree_expand_select_split_kernel<true, CAP>), dim3(gw2(t.B)), dim3(kBlock), 0,
+                                       as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, cap);
                 else
-                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s);
+                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap);
                 (void)lz_prof_aux_end(0, stream, B);
             }
             if (s < sims)                                           // the leaves of simulation s + 1
@@ -1472,26 +1482,44 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
         if (rc) return rc;
         if (s == sims) {   // last simulation: nothing left to select
             if (s == 0)
-                hipLaunchKernelGGL(tree_expand_kernel<true>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                                   lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s);
+                hipLaunchKernelGGL((tree_expand_kernel<true, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
+                                   lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, cap);
             else
-                hipLaunchKernelGGL(tree_expand_kernel<false>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                                   lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s);
+                hipLaunchKernelGGL((tree_expand_kernel<false, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
+                                   lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap);
         } else if (s == 0) {
-            hipLaunchKernelGGL(tree_expand_select_kernel<true>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s);
+            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap);
         } else {
             (void)lz_prof_aux_begin(0, stream);                      // no-ops unless lz_prof_enable(1) (never in a capture)
             if (split_step(t.B))
-                hipLaunchKernelGGL((tree_expand_select_split_kernel<false>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, (int)s);
+                hipLaunchKernelGGL((tree_expand_select_split_kernel<false, CAP>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, (int)s, cap);
             else
-                hipLaunchKernelGGL(tree_expand_select_kernel<false>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s);
+                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap);
             (void)lz_prof_aux_end(0, stream, B);
         }
     }
     return st();
+}
+
+static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t sims, float* planes, float* lp1,
+                            float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
+                            float epsilon, bool continue_trees, void* stream) {
+    if (!tree_ok(d) || !net || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
+    const int64_t B = d->num_games;
+    if (B == 0) return LZ_OK;
+    int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
+    if (rc) return rc;
+    (void)planes;   // the network kernel stages its input straight from the 32-byte packed leaf states
+    // Shared leaves (position index) only in the one-wave step, whose evaluator is this network: its outputs are a
+    // function of the packed state alone.  The step-by-step entry points (external evaluators) and the two-wave split
+    // step (where the descent runs beside the expansion that inserts into the index) keep the index but do not look it up.
+    const Tree t = split_step(B) ? no_share(make_tree(d)) : make_tree(d);
+    if (cap_set(d))
+        return tree_search_launch<true>(d, t, make_cap(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    return tree_search_launch<false>(d, t, CapArrays{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
 }
 
 // lz_net.hip (internal): the checks of lz_net_forward_packed_multi_f16 on its networks
@@ -1504,6 +1532,7 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
                                   float* lp1, float* lp2, float* lpmc, float* values, const float* noise,
                                   int64_t noise_stride, float epsilon, bool continue_trees, void* stream) {
     if (!tree_ok(d) || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
+    if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: one network per search only
     int rc = lz_net_multi_validate(nets, num_nets);
     if (rc) return rc;
     const int64_t B = d->num_games, G = d->seg_games;
@@ -1526,20 +1555,20 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
         if (s == sims) {
             if (s == 0)
                 hipLaunchKernelGGL((tree_expand_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                   lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s);
+                                   lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{});
             else
                 hipLaunchKernelGGL((tree_expand_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                   lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s);
+                                   lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, CapArrays{});
         } else if (s == 0) {
             hipLaunchKernelGGL((tree_expand_select_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s);
+                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{});
         } else {
             if (split_step(t.B))
                 hipLaunchKernelGGL((tree_expand_select_split_kernel<true>), dim3(gw2(t.B)), dim3(kBlock), 0,
-                                   as_stream(stream), t, lp1, lp2, lpmc, values, (int)s);
+                                   as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, CapArrays{});
             else
                 hipLaunchKernelGGL((tree_expand_select_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s);
+                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{});
         }
         if (s < sims) scan(s + 1);                                  // the leaves of simulation s + 1
     }
@@ -1665,6 +1694,7 @@ int lz_rng_uniform(uint64_t seed, const int64_t* game_id, const int64_t* ply, in
 
 int lz_tree_wave_select(const LzTreeDesc* d, const LzTreeWaveDesc* w, int64_t sims, int reset_budget, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || sims < 0) return LZ_ERR_ARG;
+    if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
     if (d->num_games == 0) return LZ_OK;
     const Tree t = make_tree(d);
     const WaveArrays a = make_wave(w);
@@ -1676,6 +1706,7 @@ int lz_tree_wave_select(const LzTreeDesc* d, const LzTreeWaveDesc* w, int64_t si
 int lz_tree_wave_expand(const LzTreeDesc* d, const LzTreeWaveDesc* w, const float* lp1, const float* lp2,
                         const float* lpmc, const float* priors220, const float* values, int slot_major, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || !values) return LZ_ERR_ARG;
+    if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
     if (!priors220 && (!lp1 || !lp2 || !lpmc)) return LZ_ERR_ARG;
     if (d->num_games == 0) return LZ_OK;
     hipLaunchKernelGGL(tree_expand_wave_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),

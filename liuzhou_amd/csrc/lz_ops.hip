@@ -1161,17 +1161,19 @@ __global__ __launch_bounds__(kBlock) void finalize_trajectory_kernel(
 // games are finalised (and optionally re-seated) without a host round trip.
 // =================================================================================================
 constexpr int kRowsBlock = 1024;
-// rows[g] = *cursor + (number of live slots below g), -1 for finished slots; step_index / step_counts updated.
+// rows[g] = *cursor + (number of recorded live slots below g), -1 for finished slots and for live slots whose search
+// records nothing (record[g] == 0, the playout cap's fast searches; record NULL: every live slot records);
+// step_index / step_counts updated.
 __global__ __launch_bounds__(kRowsBlock) void wave_rows_kernel(
     const uint8_t* __restrict__ done, int64_t G, int64_t* __restrict__ cursor, int64_t capacity, int64_t Tmax,
     int64_t* __restrict__ step_index, int64_t* __restrict__ step_counts, int64_t* __restrict__ rows,
-    int32_t* __restrict__ overflow) {
+    int32_t* __restrict__ overflow, const uint8_t* __restrict__ record) {
     __shared__ int wave_total[kRowsBlock / kWave];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
     const int64_t per = (G + kRowsBlock - 1) / kRowsBlock;
     const int64_t lo = tid * per, hi = (lo + per < G) ? lo + per : G;
     int cnt = 0;
-    for (int64_t j = lo; j < hi; ++j) cnt += done[j] == 0 ? 1 : 0;
+    for (int64_t j = lo; j < hi; ++j) cnt += (done[j] == 0 && (record == nullptr || record[j] != 0)) ? 1 : 0;
     int incl = cnt;
 #pragma unroll
     for (int d = 1; d < kWave; d <<= 1) {
@@ -1185,7 +1187,7 @@ __global__ __launch_bounds__(kRowsBlock) void wave_rows_kernel(
     int64_t row = *cursor + before + incl - cnt;
     __syncthreads();                                    // every thread has read the cursor
     for (int64_t j = lo; j < hi; ++j) {
-        if (done[j] != 0) { rows[j] = -1; continue; }
+        if (done[j] != 0 || (record != nullptr && record[j] == 0)) { rows[j] = -1; continue; }
         const int64_t n = step_counts[j];
         if (row >= capacity || n >= Tmax) { rows[j] = -1; atomicAdd(overflow, 1); }
         else { rows[j] = row; step_index[j * Tmax + n] = row; step_counts[j] = n + 1; }
@@ -1198,10 +1200,10 @@ __global__ __launch_bounds__(kRowsBlock) void wave_rows_kernel(
 // g * Tmax + n until the game ends, so there is nothing to scan and no step_index matrix.
 __global__ __launch_bounds__(kBlock) void wave_rows_slot_kernel(
     const uint8_t* __restrict__ done, int64_t G, int64_t Tmax, int64_t* __restrict__ step_counts,
-    int64_t* __restrict__ rows, int32_t* __restrict__ overflow) {
+    int64_t* __restrict__ rows, int32_t* __restrict__ overflow, const uint8_t* __restrict__ record) {
     const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (g >= G) return;
-    if (done[g] != 0) { rows[g] = -1; return; }
+    if (done[g] != 0 || (record != nullptr && record[g] == 0)) { rows[g] = -1; return; }
     const int64_t n = step_counts[g];
     if (n >= Tmax) { rows[g] = -1; atomicAdd(overflow, 1); return; }
     rows[g] = g * Tmax + n;
@@ -1284,6 +1286,7 @@ __global__ __launch_bounds__(kBlock) void wave_record_kernel(
 
 // one wave per slot: lane 0 plays the move (same rules as self_play_step_kernel), then the wave finalises a
 // finished game's rows (finalize_trajectory_kernel) and books it; `reseat` puts a fresh game into the slot.
+// game_plies (the playout cap): the game's searches are booked there and decide whether it counts in `outcome`.
 __global__ __launch_bounds__(kBlock) void wave_step_finish_kernel(
     LzStateSoA s, int64_t G, int64_t* __restrict__ plies, uint8_t* __restrict__ done, const int4* __restrict__ codes,
     const uint8_t* __restrict__ terminal, const uint8_t* __restrict__ cvalid, int64_t max_plies, float k,
@@ -1291,14 +1294,16 @@ __global__ __launch_bounds__(kBlock) void wave_step_finish_kernel(
     const int64_t* __restrict__ step_index, int64_t* __restrict__ step_counts, int64_t Tmax,
     unsigned long long* __restrict__ outcome, unsigned long long* __restrict__ delta_hist,
     int64_t* __restrict__ lengths, const int64_t* __restrict__ slot_game, unsigned long long* __restrict__ finished,
-    uint8_t* __restrict__ reseated, int reseat) {
+    uint8_t* __restrict__ reseated, int reseat, int64_t* __restrict__ game_plies) {
     const int lane = lane_id();
     const int64_t g = wave_item();
     if (g >= G) return;
     if (done[g] != 0) return;
     int fin = 0, delta = 0;
+    int64_t searched = 0;                               // searches of the game: one per ply, this one included
     float res = 0.f, sft = 0.f;
     if (lane == 0) {
+        searched = plies[g] + 1;
         State st = load_state(s, g);
         const bool term = terminal[g] != 0;
         if (term || cvalid[g] == 0) {
@@ -1332,10 +1337,12 @@ __global__ __launch_bounds__(kBlock) void wave_step_finish_kernel(
         soft_t[idx] = sg * sft;
     }
     if (lane == 0) {
-        if (n > 0) {
+        const int64_t gi = slot_game ? slot_game[g] : g;
+        if (n > 0 || (game_plies != nullptr && searched > 0)) {
             atomicAdd(&outcome[res > 0.f ? 0 : (res < 0.f ? 1 : 2)], 1ull);
-            if (lengths) lengths[slot_game ? slot_game[g] : g] = n;
+            if (lengths) lengths[gi] = n;
         }
+        if (game_plies) game_plies[gi] = searched;
         if (delta_hist) atomicAdd(&delta_hist[delta < -18 ? 0 : (delta > 18 ? 36 : delta + 18)], 1ull);
         if (finished) atomicAdd(finished, 1ull);
         if (reseat) {
@@ -1828,7 +1835,7 @@ int lz_wave_record(const uint8_t* done, int64_t G, int64_t* cursor, int64_t capa
                    int64_t* step_counts, int64_t* rows, int32_t* overflow, const float* model_input,
                    const uint8_t* legal_mask, const float* policy, const int64_t* current_player, int64_t T,
                    float* a_state, uint8_t* a_legal, float* a_policy, float* a_value, float* a_soft, int8_t* a_sign,
-                   void* stream) {
+                   const uint8_t* record, void* stream) {
     if (G < 0 || capacity < 0 || Tmax <= 0 || T <= 0) return LZ_ERR_ARG;
     if (G == 0) return LZ_OK;
     if (!done || !step_counts || !rows || !overflow || !model_input || !legal_mask || !policy ||
@@ -1839,10 +1846,10 @@ int lz_wave_record(const uint8_t* done, int64_t G, int64_t* cursor, int64_t capa
     if (!cursor) {                                       // slot-major live arena: row = slot * Tmax + step
         if (capacity < G * Tmax) return LZ_ERR_ARG;
         hipLaunchKernelGGL(wave_rows_slot_kernel, dim3(grid_threads(G)), dim3(kBlock), 0, st, done, G, Tmax, step_counts,
-                           rows, overflow);
+                           rows, overflow, record);
     } else {
         hipLaunchKernelGGL(wave_rows_kernel, dim3(1), dim3(kRowsBlock), 0, st, done, G, cursor, capacity, Tmax, step_index,
-                           step_counts, rows, overflow);
+                           step_counts, rows, overflow, record);
     }
     hipLaunchKernelGGL(wave_record_kernel, dim3(grid_waves(G)), dim3(kBlock), 0, st, rows, G, model_input, legal_mask,
                        policy, current_player, (int)T, a_state, a_legal, a_policy, a_value, a_soft, a_sign);
@@ -1853,7 +1860,8 @@ int lz_wave_step_finish(const LzStateSoA* s, int64_t G, int64_t* plies, uint8_t*
                         const uint8_t* terminal, const uint8_t* cvalid, int64_t max_plies, float k, float* value_t,
                         float* soft_t, const int8_t* signs, const int64_t* step_index, int64_t* step_counts,
                         int64_t Tmax, int64_t* outcome, int64_t* delta_hist, int64_t* lengths,
-                        const int64_t* slot_game, int64_t* finished, uint8_t* reseated, int reseat, void* stream) {
+                        const int64_t* slot_game, int64_t* finished, uint8_t* reseated, int reseat, int64_t* game_plies,
+                        void* stream) {
     if (G < 0 || max_plies <= 0 || Tmax <= 0) return LZ_ERR_ARG;
     if (G == 0) return LZ_OK;
     if (!soa_ok(s) || !plies || !done || !codes || !terminal || !cvalid || !value_t || !soft_t || !signs ||
@@ -1864,7 +1872,7 @@ int lz_wave_step_finish(const LzStateSoA* s, int64_t G, int64_t* plies, uint8_t*
                        done, reinterpret_cast<const int4*>(codes), terminal, cvalid, max_plies, k, value_t, soft_t,
                        signs, step_index, step_counts, Tmax, reinterpret_cast<unsigned long long*>(outcome),
                        reinterpret_cast<unsigned long long*>(delta_hist), lengths, slot_game,
-                       reinterpret_cast<unsigned long long*>(finished), reseated, reseat);
+                       reinterpret_cast<unsigned long long*>(finished), reseated, reseat, game_plies);
     return launch_status();
 }
 

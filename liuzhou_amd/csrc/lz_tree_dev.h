@@ -93,6 +93,9 @@ struct Tree {
     int* leaf_sym; int* trace_sym; const int* sym_salt; const int64_t* sym_game; const int64_t* sym_ply;
     uint64_t sym_seed; int sym_mode, sym_fixed;
 };
+// Optional playout cap (LzTreeDesc.sim_budget / root_noise): a trailing argument of the expand / select kernels, read only
+// by their CAP instantiations -- kept out of Tree so that every other kernel's arguments stay where they were.
+struct CapArrays { const int* sim_budget; const uint8_t* root_noise; };
 
 // Edge / node records are read with plain (L1 + L2 cached, normal retention) 16-byte loads.  This is safe next to the
 // device-scope atomics of the backup because a launch never loads an edge line before its own atomics on it have
@@ -188,6 +191,15 @@ __device__ __forceinline__ double terminal_value_for_mover(const State& s) {   /
     return 0.0;
 }
 
+
+// Playout cap: the expand / select step `step` of game g is its last one (no further selection) when the game's budget
+// is spent; budgets above the search's own count change nothing.  Root noise off for the game: root_noise[g] == 0.
+__device__ __forceinline__ bool cap_spent(const CapArrays& c, int g, int step) {
+    return c.sim_budget != nullptr && step >= c.sim_budget[g];
+}
+__device__ __forceinline__ bool cap_noise(const CapArrays& c, int g) {
+    return c.root_noise == nullptr || c.root_noise[g] != 0;
+}
 
 // ---- begin a search: fresh tree per game -----------------------------------------------------------------
 // give chunks [keep, n_chunks) of game g back to the pool (one thread)
@@ -854,6 +866,8 @@ Tree make_tree(const LzTreeDesc* d) {
     return t;
 }
 inline Tree no_share(Tree t) { t.share = 0; return t; }     // paths that keep the index but do not look it up
+inline bool cap_set(const LzTreeDesc* d) { return d->sim_budget != nullptr || d->root_noise != nullptr; }
+inline CapArrays make_cap(const LzTreeDesc* d) { return CapArrays{d->sim_budget, d->root_noise}; }
 bool tree_ok(const LzTreeDesc* d) {
     return d && d->num_games >= 0 && d->node_cap >= 2 && d->path_cap >= 3 &&
            d->edge_chunk >= 128 && (d->edge_chunk & (d->edge_chunk - 1)) == 0 && d->chunk_cap >= 1 &&

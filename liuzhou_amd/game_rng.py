@@ -17,6 +17,7 @@ import torch
 from . import _lib as L
 
 PURPOSE_NOISE, PURPOSE_PICK, PURPOSE_OPENING = 0, 1, 2
+PURPOSE_PLAYOUT_CAP = 3        # full or fast search of the playout cap (tree_engine.PortableTreeMCTS)
 
 
 class GameRng:

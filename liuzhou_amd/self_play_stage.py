@@ -78,6 +78,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     summaries: Dict[str, List[Dict[str, Any]]] = {"value_target_summary": [], "soft_value_target_summary": [],
                                                   "mixed_value_target_summary": []}
     bps_num = bps_den = 0
+    cap_meta: Optional[Dict[str, Any]] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -92,6 +93,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
                 files.append(name)
                 sizes.append(int(ws[i]) if i < len(ws) else 0)
         stats.append(stats_from_payload(wm.get("stats", {})))
+        wcap = (wm.get("metadata") or {}).get("playout_cap")
+        if isinstance(wcap, dict) and cap_meta is None:
+            cap_meta = {"fast_simulations": int(wcap.get("fast_simulations", 0)), "full_prob": float(wcap.get("full_prob", 1.0))}
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -106,6 +110,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     meta.update({"self_play_target_samples_per_shard": int(target_samples_per_shard),
                  "self_play_chunk_target_bytes": int(chunk_target_bytes)})
     meta.update({k: merge_target_summaries(v) for k, v in summaries.items()})
+    if cap_meta is not None:            # playout cap: its settings and the searches of every kind over all workers
+        meta["playout_cap"] = {**cap_meta, **{k: int(merged.mcts_counters.get(k, 0))
+                                              for k in ("full_searches", "fast_searches")}}
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -127,11 +134,17 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         portable_cpp_threads: int = 1, policy_target_temperature: Optional[float] = None,
                         policy_target_prior_pseudocount: float = 0.0, sample_moves: bool = True,
                         eval_symmetry: Any = "none", worker_fn: Optional[Callable[..., Dict[str, Any]]] = None,
-                        in_process: bool = False) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        in_process: bool = False, playout_cap_fast_simulations: int = 0,
+                        playout_cap_full_prob: float = 1.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
-    "random" or a fixed id 0..7) reaches the workers only when it is not "none"."""
+    "random" or a fixed id 0..7) reaches the workers only when it is not "none"; so do `playout_cap_fast_simulations` /
+    `playout_cap_full_prob` (tree backend, playout cap randomization) only when the cap is on."""
+    from .tree_engine import playout_cap_on
+    cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
+    if cap and str(search_backend).strip().lower() not in ("portable", "tree"):
+        raise ValueError(f"playout cap randomization needs the tree backend, not the root-PUCT search ({search_backend!r})")
     if worker_fn is None:
         from .self_play_worker import run_self_play_worker as worker_fn
     shards = split_games(int(num_games), len(devices))
@@ -165,7 +178,9 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             policy_target_prior_pseudocount=float(policy_target_prior_pseudocount), sample_moves=bool(sample_moves),
             target_samples_per_shard=int(target_samples_per_shard), chunk_target_bytes=int(chunk_target_bytes),
             chunk_output_dir=out_dir, chunk_file_prefix=f"{stem}.w{idx:02d}", chunk_file_ext=ext,
-            **({} if eval_symmetry == "none" else {"eval_symmetry": eval_symmetry}))
+            **({} if eval_symmetry == "none" else {"eval_symmetry": eval_symmetry}),
+            **({"playout_cap_fast_simulations": int(playout_cap_fast_simulations),
+                "playout_cap_full_prob": float(playout_cap_full_prob)} if cap else {}))
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

@@ -579,10 +579,16 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          chunk_file_ext: str = ".pt", sparse_ply: int = 1, sparse_top_k: int = 8,
                          search_backend: str = "cuda_root", portable_mcts_backend: str = "python",
                          portable_cpp_threads: int = 1, policy_target_temperature: Optional[float] = None,
-                         policy_target_prior_pseudocount: float = 0.0, eval_symmetry="none") -> Dict[str, Any]:
-    """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS."""
-    from .tree_engine import parse_eval_symmetry
+                         policy_target_prior_pseudocount: float = 0.0, eval_symmetry="none",
+                         playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0) -> Dict[str, Any]:
+    """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
+    `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
+    tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on."""
+    from .tree_engine import parse_eval_symmetry, playout_cap_on
     eval_symmetry = parse_eval_symmetry(eval_symmetry)
+    cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
+    if cap and str(search_backend).strip().lower() not in ("portable", "tree"):
+        raise ValueError(f"playout cap randomization needs the tree backend, not the root-PUCT search ({search_backend!r})")
     if eval_symmetry != "none" and str(search_backend).strip().lower() not in ("portable", "tree"):
         raise ValueError(f"eval_symmetry={eval_symmetry!r} needs the tree backend: the root-PUCT search "
                          f"({search_backend!r}) evaluates children without the symmetry hook")
@@ -649,7 +655,9 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                           policy_target_temperature=policy_target_temperature,
                                           policy_target_prior_pseudocount=float(policy_target_prior_pseudocount),
                                           seed=rng_seed, collect_timing=os.environ.get("LZ_WORKER_TIMING", "1") != "0", row_log=row_log,
-                                          eval_symmetry=eval_symmetry, **common)
+                                          eval_symmetry=eval_symmetry,
+                                          playout_cap_fast_simulations=int(playout_cap_fast_simulations) if cap else 0,
+                                          playout_cap_full_prob=float(playout_cap_full_prob) if cap else 1.0, **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
                                     sparse_top_k=int(sparse_top_k), row_log=row_log, **common)
@@ -665,7 +673,9 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        # PyTorch (a shape the kernel is not built for; `evaluator_reason` says which)
                        "evaluator": evaluator_name, **({"evaluator_reason": evaluator_why} if evaluator_why else {}),
                        "streamed": bool(stream), **({"stream_fallback": stream_fallback} if stream_fallback else {}),
-                       **({"eval_symmetry": eval_symmetry} if eval_symmetry != "none" else {})}
+                       **({"eval_symmetry": eval_symmetry} if eval_symmetry != "none" else {}),
+                       **({"playout_cap": {"fast_simulations": int(playout_cap_fast_simulations),
+                                           "full_prob": float(playout_cap_full_prob)}} if cap else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

@@ -23,7 +23,7 @@ from contextlib import contextmanager
 
 from . import _lib as L
 from . import v0_core
-from .game_rng import GameRng, PURPOSE_PICK
+from .game_rng import GameRng, PURPOSE_PICK, PURPOSE_PLAYOUT_CAP
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput, TOTAL_ACTION_DIM, states_to_model_input, \
     encode_actions_fast
 from .net_hip import DescArray, FusedNet, LzNetDesc, MAX_MULTI_NETS, multi_compatible
@@ -50,7 +50,21 @@ class LzTreeDesc(C.Structure):
                [(n, C.c_void_p) for n in ("pos_index", "node_value", "leaf_src", "share_count")] + [("pos_slots", C.c_int64)] + \
                [(n, C.c_void_p) for n in ("leaf_sym", "trace_sym", "sym_salt", "sym_game", "sym_ply")] + \
                [("sym_seed", C.c_uint64), ("sym_mode", C.c_int32), ("sym_fixed", C.c_int32)] + \
-               [("seg_games", C.c_int64), ("seg_off", C.c_void_p)]
+               [("seg_games", C.c_int64), ("seg_off", C.c_void_p)] + \
+               [(n, C.c_void_p) for n in ("sim_budget", "root_noise")]
+
+
+def playout_cap_on(fast_simulations: int, full_prob: float, sims: int) -> bool:
+    """Validate the playout cap's parameters against the search's `sims`: on when 0 < fast_simulations < sims, off for
+    fast_simulations == 0; anything else (and full_prob outside [0, 1]) is a ValueError."""
+    F, p = int(fast_simulations), float(full_prob)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"playout_cap_full_prob must lie in [0, 1], got {full_prob}")
+    if F == 0:
+        return False
+    if not 0 < F < int(sims):
+        raise ValueError(f"playout_cap_fast_simulations must be 0 (off) or in (0, mcts_simulations={int(sims)}), got {F}")
+    return True
 
 
 def parse_eval_symmetry(value) -> "str | int":
@@ -348,6 +362,16 @@ class TreeEngine:
             d.sym_mode, d.sym_fixed = 1, int(mode)
         self.persistent = False           # the persistent kernel's own network pass is not part of this: the fused search
 
+    def set_playout_cap(self, sim_budget: Optional[torch.Tensor], root_noise: Optional[torch.Tensor]) -> None:
+        """Playout cap (LzTreeDesc.sim_budget / root_noise): int32[B] simulations of every search per game and uint8[B]
+        root noise switch, device tensors read at every launch (None: off).  Only search() honours them; must be set
+        before a search is captured into a graph."""
+        for name, t, dt in (("sim_budget", sim_budget, torch.int32), ("root_noise", root_noise, torch.uint8)):
+            if t is not None and (t.dtype != dt or t.numel() != self.B or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of {self.B} elements on {self.device}")
+            setattr(self.desc, name, None if t is None else t.data_ptr())
+        self._cap_arrays = (sim_budget, root_noise)              # keep them alive while the descriptor points at them
+
     _NODE_DT = [("w0", "<u8"), ("w1", "<u8"), ("w2", "<u8"), ("w3", "<u8"), ("edge_begin", "<i4"), ("nedges", "<i4"),
                 ("parent", "<i4"), ("old_begin", "<i4")]
     _EDGE_DT = [("W", "<f8"), ("P", "<f4"), ("n_info", "<u4"), ("child", "<i4"), ("cbegin", "<i4"),
@@ -624,7 +648,8 @@ class PortableTreeMCTS:
                  policy_target_prior_pseudocount: float = 0.0, batch_k: int = 1, seed: int = 12345,
                  game_offset: int = 0, game_stride: Optional[int] = None, trace: bool = False,
                  collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none",
-                 segment_games: Optional[int] = None, multi_launch: bool = True) -> None:
+                 segment_games: Optional[int] = None, multi_launch: bool = True, fast_simulations: int = 0,
+                 full_prob: float = 1.0) -> None:
         """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
         searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
         FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
@@ -647,9 +672,24 @@ class PortableTreeMCTS:
         leaves per game are collected, evaluated in one network launch of batch_k * B positions and backed up per wave.
         `reuse_tree`: keep the played child's subtree between consecutive search_batch calls on the same games
         (the reference's portable self-play does, v1/python/portable_self_play.py:191); the arenas then hold
-        (1 + reuse_factor) * sims nodes per game (reuse_factor < 0: as much as a third of the free memory allows).  `policy_target_*`: portable_mcts.py:690-700."""
+        (1 + reuse_factor) * sims nodes per game (reuse_factor < 0: as much as a third of the free memory allows).  `policy_target_*`: portable_mcts.py:690-700.
+        `fast_simulations` / `full_prob`: playout cap randomization (on when 0 < fast_simulations < num_simulations): each
+        search of game g at ply t is full (num_simulations, root noise) when uniform(seed, g, t, purpose 3) < full_prob,
+        else fast (fast_simulations, no root noise).  The mask of the last search is `full_search` (uint8[B]); parity
+        runs inject one through `injected_full_search`.  Searches then always use the compact lists; not with batch_k > 1,
+        several networks, an external evaluator or the persistent kernel (ValueError)."""
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
+        self.cap = playout_cap_on(fast_simulations, full_prob, num_simulations)
+        self.fast_simulations, self.full_prob = int(fast_simulations), float(full_prob)
+        if self.cap:
+            why = ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
+                   "several networks in one search" if self.multi or len(self.nets) != 1 else
+                   "an external evaluator (split-phase path)" if not isinstance(self.nets[0], FusedNet) else
+                   "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else None)
+            if why is not None:
+                raise ValueError(f"playout cap randomization is not supported with {why}")
+            compact_evals = True           # a dense launch would evaluate every slot at every simulation: nothing saved
         if not self.multi and len(self.nets) != 1:
             raise ValueError("several networks need segment_games")
         if self.multi:
@@ -678,6 +718,8 @@ class PortableTreeMCTS:
         if compact_evals is None:
             compact_evals = self.fused and int(num_games) >= 2 * samples_per_launch_pass(net)
             self.compact_default = compact_evals and self.batch_k == 1 and shares_leaves(num_games)
+        if self.cap:
+            compact_evals = self.compact_default = True
         self.engine = TreeEngine(num_games, num_simulations, device, exploration_weight,
                                  reuse_factor=float(reuse_factor) if self.reuse_tree else 0.0, batch_k=self.batch_k,
                                  compact_evals=bool(compact_evals) and self.fused and self.batch_k == 1,
@@ -719,6 +761,37 @@ class PortableTreeMCTS:
         self._tail_graph = None
         self._tail_rounds = 0
         self._noise_buf = torch.zeros((self.engine.B, OUT_CAP), dtype=torch.float32, device=self.engine.device)
+        # playout cap: per-game budget / root noise switch of the next search, filled on the device before every launch
+        self.injected_full_search: Optional[torch.Tensor] = None   # parity runs: bool[B] instead of the RNG's draws
+        self.cap_counts = torch.zeros((2,), dtype=torch.int64, device=self.engine.device)   # full / fast searches of live games
+        if self.cap:
+            z = lambda dt: torch.zeros((self.engine.B,), dtype=dt, device=self.engine.device)
+            self._cap_u, self.sim_budget = z(torch.float32), z(torch.int32)
+            self.bind_full_search(z(torch.uint8))
+
+    def bind_full_search(self, buf: torch.Tensor) -> None:
+        """Use `buf` (uint8[B], contiguous; DualStreamTreeMCTS hands each part a slice of one mask) as the full / fast mask
+        of the playout cap, which the searches also read as their root noise switch.  Before the first search."""
+        self.full_search = buf
+        self.engine.set_playout_cap(self.sim_budget, buf)
+
+    @property
+    def last_full_search(self) -> Optional[torch.Tensor]:
+        """bool[B]: which games' last search was full (None: the playout cap is off)."""
+        return self.full_search.bool() if self.cap else None
+
+    def _draw_playout_cap(self, active: Optional[torch.Tensor]) -> None:
+        """Full / fast mask of this move on the device (no host synchronisation): u = uniform(seed, game, ply, purpose 3),
+        full iff u < full_prob (compared in double precision); budgets and root noise switch from it."""
+        if self.injected_full_search is not None:
+            full = self.injected_full_search.to(device=self.engine.device, dtype=torch.bool)
+        else:
+            self.rng.uniform_into(self._cap_u, PURPOSE_PLAYOUT_CAP)
+            full = self._cap_u.double() < self.full_prob
+        self.full_search.copy_(full)
+        self.sim_budget.copy_(torch.where(full, self.sims, self.fast_simulations))
+        live = torch.ones_like(full) if active is None else active.to(device=full.device, dtype=torch.bool)
+        self.cap_counts.add_(torch.stack(((full & live).sum(), (~full & live).sum())))
 
     # ---- tracing: roctx ranges (torch.cuda.nvtx is roctx on ROCm) + HIP-event timing buckets, as the reference's
     # V1RootMCTS._nvtx_range / _timed (v1/python/mcts_gpu.py:565-602); bucket names follow its runner
@@ -945,6 +1018,7 @@ class PortableTreeMCTS:
         self.engine.share_count.zero_()
         self.engine.live_total.zero_()
         self.engine.reuse_dropped.zero_()
+        self.cap_counts.zero_()
         # refused expansions / fewest free chunks are per run too (a cached engine must not report an earlier run's)
         # (pool_stats[2], the chunks reserved for fresh roots, follows the trees' state and is NOT a per-run statistic)
         self.engine.buf["pool_stats"][:2].copy_(torch.tensor([0, self.engine.pool_chunks], dtype=torch.int32))
@@ -967,6 +1041,7 @@ class PortableTreeMCTS:
         self.engine.eval_count.zero_()
         self.engine.share_count.zero_()
         self.engine.live_total.zero_()
+        self.cap_counts.zero_()
         self.get_timing(reset=True)
         if self.batch_k > 1:
             self.engine.wbuf["eval_total"].zero_(); self.engine.wbuf["eval_count"].zero_()
@@ -997,12 +1072,14 @@ class PortableTreeMCTS:
         e = self.engine
         # compact lists or dense launches for this move (engines built with compact_evals; the runner passes a hint from
         # the number of live games: the lists pay once a launch gets at least one network pass per CU shorter)
-        self.compact_now = self.compact_default if compact is None else bool(compact)
+        self.compact_now = self.compact_default if (compact is None or self.cap) else bool(compact)
         add_noise = self.add_noise if add_dirichlet_noise is None else bool(add_dirichlet_noise)
         e.set_roots(state, active)
         continue_trees = self.reuse_tree and self._have_trees
         self.rng.begin_move(reset if self._have_trees else None, rng_game_ids, rng_plies)
         self._explicit_plies = rng_plies is not None
+        if self.cap:
+            self._draw_playout_cap(active)
         with self._timed("root_puct_ms"):
             if continue_trees:
                 e.advance(played_action, reset, self.sims)
@@ -1087,6 +1164,13 @@ class DualStreamTreeMCTS:
             self.parts.append(PortableTreeMCTS(base.variant(half_workgroups=half), n, num_simulations, dev,
                                                game_offset=a, game_stride=self.B, **kw))
         self.sims = int(num_simulations)
+        # playout cap: one full / fast mask over all games, each part writing its slice (the wave tail reads the whole)
+        self.cap = self.parts[0].cap
+        self.full_search = None
+        if self.cap:
+            self.full_search = torch.zeros((self.B,), dtype=torch.uint8, device=dev)
+            for (a, b), part in zip(self.bounds, self.parts):
+                part.bind_full_search(self.full_search[a:b])
         self.serialize = False        # measurement aid: run the halves one after the other on the caller's stream
         # Overlap watch.  A probed pair of streams can still end up on one hardware queue later (the runtime maps streams
         # to its 4 queues when they become active; other streams of the process come and go): the halves then run one
@@ -1110,6 +1194,14 @@ class DualStreamTreeMCTS:
     @property
     def leaf_evals(self) -> int:
         return sum(p.leaf_evals for p in self.parts)
+
+    @property
+    def cap_counts(self) -> torch.Tensor:
+        return sum(p.cap_counts for p in self.parts)
+
+    @property
+    def last_full_search(self) -> Optional[torch.Tensor]:
+        return self.full_search.bool() if self.cap else None
 
     @property
     def consumed_evals(self) -> int:
@@ -1355,7 +1447,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        policy_target_prior_pseudocount: float = 0.0, reuse_tree: bool = True,
                        reuse_factor: float = -1.0, dual_stream: Optional[bool] = None, continuous_waves: bool = True,
                        device_tail: bool = True, batch_k: int = 1, evaluator: str = "auto", seed: int = 12345,
-                       collect_timing: bool = False, row_log=None, eval_symmetry="none"
+                       collect_timing: bool = False, row_log=None, eval_symmetry="none",
+                       playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0
                        ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
@@ -1367,8 +1460,14 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     `row_log` (finished_log.FinishedRowLog, the streaming worker): the rows of every game leave through the log when the
     game ends and the returned batch is empty; needs `device_tail` and `continuous_waves`.
     `eval_symmetry`: "none" (default), "random" or an id 0..7 -- each leaf evaluated under a board symmetry
-    (PortableTreeMCTS); not with batch_k > 1."""
+    (PortableTreeMCTS); not with batch_k > 1.
+    `playout_cap_fast_simulations` F / `playout_cap_full_prob` p: playout cap randomization (on when 0 < F <
+    mcts_simulations): a move's search is full with probability p (drawn per game and ply) and records a training row,
+    otherwise it is a fast search of F simulations without root noise that only advances the game.  `num_positions`
+    counts recorded rows, `avg_game_length` plies; mcts_counters gain full_searches / fast_searches /
+    recorded_positions.  Fused network and batch_k = 1 only (ValueError otherwise)."""
     dev = torch.device(device)
+    cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
     eval_symmetry = parse_eval_symmetry(eval_symmetry)
     if eval_symmetry != "none" and int(batch_k) > 1:
         raise ValueError("eval_symmetry is not supported by the legacy waves (batch_k > 1): their wave kernels evaluate "
@@ -1389,7 +1488,12 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     # two half-batches on two streams (see DualStreamTreeMCTS) once a wave is large enough to fill the chip twice over
     if dual_stream is None:
         dual_stream = use_fused and net.pack.channels == 64 and wave >= 1024 and int(batch_k) <= 1   # waves: large launches already
+    if cap and (not use_fused or int(batch_k) > 1):
+        raise ValueError("playout cap randomization needs the fused network search with batch_k = 1 (not the external-"
+                         "module evaluator, not legacy waves)")
     if use_fused and persistent_search_available(net, batch_k) and eval_symmetry == "none":
+        if cap:
+            raise ValueError("playout cap randomization is not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
         dual_stream = False                                  # the persistent kernel overlaps the phases inside every CU
     cls = DualStreamTreeMCTS if (dual_stream and use_fused and net.pack.channels == 64 and wave >= 2) else PortableTreeMCTS
     t_setup = time.perf_counter()
@@ -1401,6 +1505,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
               collect_timing=bool(collect_timing))
     if eval_symmetry != "none":
         kw["eval_symmetry"] = eval_symmetry
+    if cap:
+        kw.update(fast_simulations=int(playout_cap_fast_simulations), full_prob=float(playout_cap_full_prob))
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a
@@ -1429,6 +1535,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     buffer = TensorTrajectoryBuffer(dev, TOTAL_ACTION_DIM, max_steps_hint=max_game_plies, concurrent_games_hint=wave)
     outcome = torch.zeros((3,), dtype=torch.int64, device=dev)
     lengths = torch.zeros((int(num_games),), dtype=torch.int64, device=dev)
+    # playout cap: plies (searches) of every game, which `lengths` (recorded rows) no longer equals
+    game_plies = torch.zeros((int(num_games),), dtype=torch.int64, device=dev) if cap else None
     # device_tail: rows / move / finalisation on the device (wave_tail.WaveTail); continuous_waves: one wave whose
     # finished slots start the remaining games at once instead of sequential waves that idle until their longest game
     tail = None
@@ -1438,6 +1546,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         tail = WaveTail(buffer, wave, int(max_game_plies), dev, soft_value_k=float(soft_value_k), row_log=row_log)
         tail.collect_timing = bool(collect_timing)
         outcome, delta_hist = tail.outcome, tail.delta_hist
+        if cap:
+            tail.record_mask = mcts.full_search
     continuous = tail is not None and bool(continuous_waves)
     wasted_plies = 0
     started = time.perf_counter()
@@ -1452,11 +1562,14 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
             done[g:] = True
         mcts.reset_trees()
         slot_ids = torch.arange(wave, dtype=torch.int64, device=dev)
+        searched = torch.zeros((wave,), dtype=torch.int64, device=dev) if cap else None   # host loop: searches per slot
         if tail is not None:
             force_n = int(opening_random_moves)
             # compact evaluation lists once the wave has drained by at least one network pass per CU (the engine was built
             # for both launch forms if that can happen at all; two plies of lag in the estimate only delay the switch)
             lists_below = wave - (samples_per_launch_pass(net) if use_fused else 0)
+            if cap:
+                tail.game_plies = game_plies if continuous else game_plies[base:base + g]
             tail.run(lambda st, temps, dn, reseated: mcts.search_batch(
                          st, temperatures=temps, active=~dn, reset=reseated,
                          force_uniform_random_mask=(plies < force_n) if force_n > 0 else None,
@@ -1465,6 +1578,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                      states, plies, done, step_index, step_counts, lengths if continuous else lengths[base:base + g],
                      temperature_init, temperature_final, temperature_threshold,
                      games_to_start=int(num_games) - wave if continuous else 0)
+
             wasted_plies += 1
             continue
         while True:
@@ -1476,11 +1590,16 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
             force = (plies < int(opening_random_moves)) if int(opening_random_moves) > 0 else None
             out = mcts.search_batch(states, temperatures=temps, active=~done, force_uniform_random_mask=force,
                                     rng_game_ids=slot_ids + base, rng_plies=plies)
-            rows = buffer.append_steps(out.model_input.index_select(0, active), out.legal_mask.index_select(0, active),
-                                       out.policy_dense.index_select(0, active),
-                                       states.current_player.index_select(0, active))
-            step_index[active, step_counts.index_select(0, active)] = rows
-            step_counts.index_add_(0, active, torch.ones_like(active))
+            rec = active
+            if cap:                                          # only the full searches record a row
+                rec = active[mcts.full_search.index_select(0, active).bool()]
+                searched.index_add_(0, active, torch.ones_like(active))
+            if not cap or int(rec.numel()) > 0:
+                rows = buffer.append_steps(out.model_input.index_select(0, rec), out.legal_mask.index_select(0, rec),
+                                           out.policy_dense.index_select(0, rec),
+                                           states.current_player.index_select(0, rec))
+                step_index[rec, step_counts.index_select(0, rec)] = rows
+                step_counts.index_add_(0, rec, torch.ones_like(rec))
             fin, result, _ = v0_core.self_play_step_inplace(
                 *states.tensors(), plies, done, active, out.chosen_action_codes.index_select(0, active),
                 out.terminal_mask.index_select(0, active), out.chosen_valid_mask.index_select(0, active),
@@ -1495,6 +1614,10 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                 if int(f_slots.numel()) > 0:
                     lengths.index_copy_(0, f_slots + base, f_len)
                 outcome.add_(f_out)
+                if cap:                                      # games booked by plies: those without a recorded row too
+                    game_plies.index_copy_(0, fin + base, searched.index_select(0, fin))
+                    r = result.to(dev).view(-1)[step_counts.index_select(0, fin) == 0]
+                    outcome.add_(torch.stack(((r > 0).sum(), (r < 0).sum(), (r == 0).sum())))
     t_sync = time.perf_counter()
     torch.cuda.synchronize(dev)
     sync_ms = (time.perf_counter() - t_sync) * 1e3
@@ -1531,7 +1654,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
               "`pool_chunks` to TreeEngine or lower `concurrent_games`.", flush=True)
     stats = SelfPlayV1Stats(
         num_games=num_games, num_positions=positions, black_wins=int(o[0]), white_wins=int(o[1]), draws=int(o[2]),
-        avg_game_length=float(lengths.to(torch.float32).mean().item()), elapsed_sec=elapsed,
+        avg_game_length=float((game_plies if cap else lengths).to(torch.float32).mean().item()), elapsed_sec=elapsed,
         positions_per_sec=float(positions / elapsed), games_per_sec=float(num_games / elapsed),
         step_timing_ms=t_ms, step_timing_ratio={k: (t_ms[k] / t_total if t_total > 0 else 0.0) for k in keys},
         step_timing_calls={k: int(timing["timing_calls"].get(k, 0)) for k in keys},
@@ -1540,7 +1663,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         # (... unless that ply was launched densely: the two-plies-old live estimate had not seen the wave end yet)
         mcts_counters={"leaf_eval_count": int(mcts.leaf_evals) - (
                            wasted_plies * wave * (int(mcts_simulations) + 1)
-                           if int(batch_k) <= 1 and not (compact_lists and getattr(mcts, "last_search_lists", False)) else 0),
+                           if int(batch_k) <= 1 and not (compact_lists and (cap or getattr(mcts, "last_search_lists", False)))
+                           else 0),
                        "compact_eval_lists": int(compact_lists), "search_parts": len(engines),
                        "list_searches": int(sum(getattr(p, "list_searches", 0) for p in (getattr(mcts, "parts", None) or [mcts]))),
                        "masked_extra_plies": wasted_plies, "graph_retry_off": int(bool(mcts.graph_retry_off)),
@@ -1554,6 +1678,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        **({"stream_overlap_pct": int(round(100.0 * mcts.overlap_ratio))}
                           if getattr(mcts, "overlap_ratio", None) is not None else {}),
                        **({"loop_ms": int(tail.loop_ms), "host_wait_ms": int(tail.host_wait_ms),
-                           "plies_launched": int(tail.plies_launched)} if tail is not None else {})},
+                           "plies_launched": int(tail.plies_launched)} if tail is not None else {}),
+                       # playout cap: searches of live games by kind, and the rows the full ones recorded
+                       **(dict(zip(("full_searches", "fast_searches"), (int(x) for x in mcts.cap_counts.tolist())),
+                               recorded_positions=int(positions)) if cap else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))
     return batch, stats

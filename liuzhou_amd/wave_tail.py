@@ -39,6 +39,11 @@ class WaveTail:
         self.live_estimate = self.G                          # run(): live slots two plies ago (host-visible without a wait)
         self.host_wait_ms = self.loop_ms = 0.0              # run(): time the host spent waiting for the device / in the loop
         self.plies_launched = 0
+        # playout cap: `record_mask` uint8[G] (the search's full / fast mask, refreshed in place every ply) -- slots whose
+        # search was fast record no row; `game_plies` int64 (indexed like `lengths`) -- the searches of every finished
+        # game, which also decide that it counts in `outcome` when none of its searches recorded a row
+        self.record_mask: Optional[torch.Tensor] = None
+        self.game_plies: Optional[torch.Tensor] = None
         # finished_log.FinishedRowLog: the live rows are slot-major (row = slot * max_plies + step, no step_index matrix)
         # and the rows of a game move to the log when the game ends (the streaming worker)
         self.row_log = row_log
@@ -95,7 +100,8 @@ class WaveTail:
                 L.ptr(done), L.i64(G), L.ptr(cursor), L.i64(self.buffer.capacity), L.i64(steps),
                 L.ptr(step_index), L.ptr(step_counts), L.ptr(self.rows), L.ptr(self.overflow), L.ptr(mi), L.ptr(lm),
                 L.ptr(pol), L.ptr(states.current_player), L.i64(T), L.ptr(a_state), L.ptr(a_legal), L.ptr(a_policy),
-                L.ptr(a_value), L.ptr(a_soft), L.ptr(a_sign), L.stream_ptr(self.device)), "wave_record")
+                L.ptr(a_value), L.ptr(a_soft), L.ptr(a_sign), L.ptr(self.record_mask), L.stream_ptr(self.device)),
+                "wave_record")
 
     def step_finish(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, step_index: torch.Tensor,
                     step_counts: torch.Tensor, search: RootSearchBatchOutput, lengths: Optional[torch.Tensor] = None,
@@ -115,7 +121,7 @@ class WaveTail:
                 L.ptr(step_index), L.ptr(step_counts),
                 L.i64(self.max_plies if step_index is None else int(step_index.shape[1])), L.ptr(self.outcome),
                 L.ptr(self.delta_hist), L.ptr(lengths), L.ptr(slot_game), L.ptr(self.finished), L.ptr(reseated),
-                C.c_int(1 if self.reseat else 0), L.stream_ptr(self.device)), "wave_step_finish")
+                C.c_int(1 if self.reseat else 0), L.ptr(self.game_plies), L.stream_ptr(self.device)), "wave_step_finish")
 
     def start_next_games(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, step_counts: torch.Tensor,
                          budget: torch.Tensor, next_game: torch.Tensor, slot_game: torch.Tensor,

@@ -46,6 +46,10 @@ def parse(argv=None):
     ap.add_argument("--search_backend", default="cuda_root", choices=["cuda_root", "portable", "tree"])
     ap.add_argument("--policy_target_temperature", type=float, default=None)
     ap.add_argument("--policy_target_prior_pseudocount", type=float, default=0.0)
+    ap.add_argument("--playout_cap_fast_simulations", type=int, default=0,
+                    help="playout cap randomization (tree backend): simulations of a fast search, 0 = off")
+    ap.add_argument("--playout_cap_full_prob", type=float, default=1.0,
+                    help="playout cap randomization: probability that a move gets a full search and a training row")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -104,7 +108,8 @@ def main(argv=None) -> int:
         chunk_target_bytes=args.self_play_chunk_target_bytes, metadata_base=meta, sparse_ply=args.sparse_ply,
         sparse_top_k=args.sparse_top_k, search_backend=args.search_backend,
         policy_target_temperature=args.policy_target_temperature,
-        policy_target_prior_pseudocount=args.policy_target_prior_pseudocount)
+        policy_target_prior_pseudocount=args.policy_target_prior_pseudocount,
+        playout_cap_fast_simulations=args.playout_cap_fast_simulations, playout_cap_full_prob=args.playout_cap_full_prob)
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
