@@ -485,6 +485,14 @@ typedef struct LzTreeDesc {
      * entry points refuse a descriptor that sets either array (LZ_ERR_UNSUPPORTED). */
     const int32_t* sim_budget;     /* [B] simulations of this search per game (values above sims: sims) */
     const uint8_t* root_noise;     /* [B] 0: no root noise for game g */
+    /* Optional forced playouts and policy target pruning (Wu 2019, section 3.2; 0 / NULL = off).  A game's search is
+     * forced when forced_k > 0 and its root-noise switch is on (root_noise == NULL, or root_noise[g] != 0).  Select, root
+     * level only: a child with N > 0 and N * N < (forced_k * P) * root_visits (in double) is due, and the descent takes the
+     * due child with the lowest edge index.  lz_tree_finish_pruned takes those visits out of the training target again.
+     * Honoured by lz_tree_select, lz_tree_search / _continue and lz_tree_finish_pruned; the wave, multi-network and
+     * persistent searches refuse a descriptor with forced_k > 0 (LZ_ERR_UNSUPPORTED). */
+    double   forced_k;
+    int32_t* forced_count;         /* [B] optional: += 1 for every descent that took a due child */
 } LzTreeDesc;
 LZ_API int64_t lz_tree_desc_bytes(void);
 
@@ -557,6 +565,22 @@ LZ_API int lz_tree_finish(const LzTreeDesc* tree, const float* temperatures, con
                           uint8_t* chosen_valid, uint8_t* terminal_mask, float* root_value,
                           int32_t* child_count, int32_t* child_action, int32_t* child_visits,
                           float* child_prior, int64_t out_cap, void* stream);
+/* lz_tree_finish with policy target pruning: for a forced game (LzTreeDesc.forced_k > 0, root-noise switch on) with a
+ * non-terminal root the training target (policy_dense) is formed from the pruned visits N' instead of N:
+ *   c* = the most visited child (lowest index), S* = Q(c*) + c_puct P(c*) sqrt(max(T, 1)) / (1 + N(c*)), T = root visits;
+ *   every other child with N > 0: F = the smallest m with m * m >= (forced_k P) max(T, 1), L = the fewest visits at
+ *   which the child's PUCT score stays below S* (N when S* - Q <= 0), N' = min(N, max(N - F, L)), N' <= 1 -> 0.
+ * The selection policy, the pick, child_visits and root_value use the raw N.  child_target_visits [B,out_cap] (N'; = N
+ * for games that are not forced) and pruned_visits [B] (sum of N - N') are optional.  With forced_k == 0 it writes exactly
+ * what lz_tree_finish writes. */
+LZ_API int lz_tree_finish_pruned(const LzTreeDesc* tree, const float* temperatures, const float* target_temperatures,
+                                 float prior_pseudocount, const uint8_t* force_uniform, int sample_moves,
+                                 const float* uniforms,
+                                 float* policy_dense /*[B,220]*/, int32_t* chosen_index, int32_t* chosen_code /*[B,4]*/,
+                                 uint8_t* chosen_valid, uint8_t* terminal_mask, float* root_value,
+                                 int32_t* child_count, int32_t* child_action, int32_t* child_visits,
+                                 float* child_prior, int64_t out_cap, int32_t* child_target_visits,
+                                 int32_t* pruned_visits, void* stream);
 /* One whole search enqueued from C++: begin, root evaluation + expansion, then `sims` x
  * (select -> planes -> fused network -> expand + backup).  No host synchronisation; capturable. */
 LZ_API int lz_tree_search(const LzTreeDesc* tree, const LzNetDesc* net, int64_t sims, float* planes /*[B,11,36]*/,

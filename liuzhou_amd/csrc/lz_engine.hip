@@ -81,10 +81,13 @@ __global__ __launch_bounds__(kBlock) void pos_clear_kernel(int* __restrict__ tab
         reinterpret_cast<int4*>(tab)[i] = make_int4(-1, -1, -1, -1);
 }
 
-__global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t) {
+// FORCED (here and in the expand + select kernels): forced playouts at the root level (`fa`, tree_select); the default
+// instantiations never read it.
+template <bool FORCED = false>
+__global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t, ForcedArgs fa) {
     const int g = wave_game();
     if (g >= t.B) return;
-    tree_select(t, g, lane_id(), load_root_info(t, g));
+    tree_select<FORCED>(t, g, lane_id(), load_root_info(t, g), -1, -1, nullptr, FORCED ? fa.k : 0.0, fa.count);
 }
 
 
@@ -238,13 +241,14 @@ __global__ __launch_bounds__(kScanBlock) void tree_live_scan_seg_kernel(Tree t, 
 // expand + backup of simulation s fused with the selection of simulation s+1 (same wave, same game: the edge
 // records it just touched are still in L1/L2) -- one launch per simulation besides the network kernel.
 // (forcing 8 waves / SIMD -- <= 96 SGPRs, 126 scalar spills -- was measured: no gain at 16 384 games, 1 % slower at C2)
-template <bool IS_ROOT, bool COMPACT = false, bool CAP = false>
+template <bool IS_ROOT, bool COMPACT = false, bool CAP = false, bool FORCED = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, const float* __restrict__ lp1,
                                                                     const float* __restrict__ lp2,
                                                                     const float* __restrict__ lpm,
                                                                     const float* __restrict__ values,
                                                                     const float* __restrict__ noise, int noise_stride,
-                                                                    float epsilon, int step, CapArrays cap) {
+                                                                    float epsilon, int step, CapArrays cap,
+                                                                    ForcedArgs fa) {
 #ifndef LZ_EXP_NO_TREE_PRIO
     // The kernel is a chain of dependent loads with a few dozen instructions in between; in the two-stream search it
     // shares the SIMDs with the other half's network waves, which always have MFMAs to issue.  Raised wave priority
@@ -271,7 +275,9 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
     }
     if (IS_ROOT) root = load_root_info(t, g);                  // the root record itself was just written
     LZ_TSTAMP(g, 7)                                            // fence (+ root reload)
-    tree_select(t, g, lane, root, -1, -1, nullptr LZ_TSTAMP_PASS);
+    // forced playouts: the games whose root-noise switch is on (every game without the cap, the full searches with it)
+    const double fk = FORCED && (!CAP || cap_noise(cap, g)) ? fa.k : 0.0;
+    tree_select<FORCED>(t, g, lane, root, -1, -1, nullptr, fk, fa.count LZ_TSTAMP_PASS);
 #ifdef LZ_EXP_TREE_STAMPS
     LZ_TADD(g, 19, 1)
 #endif
@@ -289,12 +295,12 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
 // this kernel; LZ_TREE_SPLIT=0 takes the one-wave kernel, tests/test_gpu_tree.py compares the two).  Used for launches of
 // at most kSplitMaxGames games: at 16 384 games the SIMDs are issue-bound and twice the waves buy nothing.
 constexpr int kSplitMaxGames = 8192;
-template <bool COMPACT, bool CAP = false>
+template <bool COMPACT, bool CAP = false, bool FORCED = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_select_split_kernel(Tree t, const float* __restrict__ lp1,
                                                                           const float* __restrict__ lp2,
                                                                           const float* __restrict__ lpm,
                                                                           const float* __restrict__ values, int step,
-                                                                          CapArrays cap) {
+                                                                          CapArrays cap, ForcedArgs fa) {
     __builtin_amdgcn_s_setprio(3);
     LZ_EXPAND_SCRATCH(sc);
     __shared__ int s_flag[kWavesPerBlock / 2];
@@ -324,7 +330,8 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_split_kernel(Tree t
             if (lane == 0) t.leaf_kind[g] = kLeafInactive;
             return;
         }
-        tree_select(t, g, lane, root, split.wait_edge, split.nolegal_edge, flag);
+        const double fk = FORCED && (!CAP || cap_noise(cap, g)) ? fa.k : 0.0;
+        tree_select<FORCED>(t, g, lane, root, split.wait_edge, split.nolegal_edge, flag, fk, fa.count);
     }
 }
 
@@ -923,6 +930,10 @@ __device__ __forceinline__ void score_policy(const float (&sc)[2], const bool (&
     }
 }
 
+// PRUNE (lz_tree_finish_pruned): policy target pruning for the games whose search was forced (forced_k > 0, root-noise
+// switch on): the training target is formed from the pruned visits N' (see liuzhou_hip.h), everything else from N.
+// Every decision of the stage is in double, and no product meets a sum without a division or a comparison in between.
+template <bool PRUNE = false>
 __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float* __restrict__ temps,
                                                              const float* __restrict__ target_temps,
                                                              float prior_pseudocount,
@@ -938,7 +949,11 @@ __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float
                                                              int* __restrict__ child_count,
                                                              int* __restrict__ child_action,
                                                              int* __restrict__ child_visits,
-                                                             float* __restrict__ child_prior, int out_cap) {
+                                                             float* __restrict__ child_prior, int out_cap,
+                                                             double forced_k,
+                                                             const uint8_t* __restrict__ root_noise,
+                                                             int* __restrict__ child_target_visits,
+                                                             int* __restrict__ pruned_visits) {
     const int lane = lane_id();
     const int g = wave_game();
     if (g >= t.B) return;
@@ -955,6 +970,7 @@ __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float
         chosen_index[g] = -1;
         chosen_code[g] = make_int4(-1, -1, -1, -1);
         child_count[g] = term ? 0 : ne;
+        if (PRUNE && pruned_visits != nullptr) pruned_visits[g] = 0;
         const int rv = t.root_visits[g];
         root_value[g] = term ? (ne == 0 && game_status(root) == 0 ? -1.f : (float)terminal_value_for_mover(root))
                              : (rv > 0 ? (float)(t.root_W[g] / (double)rv) : t.root_init_value[g]);
@@ -963,12 +979,14 @@ __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float
     const int e0 = nodes[0].edge_begin;
     const float temp = temps[g];
     float v[2], pr[2]; int act[2]; double q[2]; bool ok[2];
+    int nv[2];                                                 // PRUNE: raw visits, then the target's visits N'
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int k = r * kWave + lane;
         ok[r] = k < ne;
         const Edge e = edges[(size_t)(e0 + (ok[r] ? k : 0))];
         const int n = ok[r] ? edge_n(e.n_info) : 0;
+        nv[r] = n;
         v[r] = (float)n;
         pr[r] = ok[r] ? e.P : 0.f;
         act[r] = ok[r] ? (int)e.act : 0;
@@ -987,17 +1005,70 @@ __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float
     float pol[2] = {0.f, 0.f};
     const float vmax = lzw::wave_max(fmaxf(ok[0] ? v[0] : -1.f, ok[1] ? v[1] : -1.f));
     score_policy(v, ok, temp, lane, pol);
-    if (target_temps == nullptr && !(prior_pseudocount > 0.f)) {
+    bool pruning = false;
+    if (PRUNE) {
+        pruning = forced_k > 0.0 && (root_noise == nullptr || root_noise[g] != 0);
+        if (pruning) {
+            // c*: most visits, lowest edge index among equals
+            const uint64_t lo = __ballot(ok[0] && v[0] == vmax);
+            const int cs = lo ? __ffsll((unsigned long long)lo) - 1
+                              : kWave + __ffsll((unsigned long long)__ballot(ok[1] && v[1] == vmax)) - 1;
+            const int src = cs & 63;
+            const bool up = cs >= kWave;
+            const int ns = lzw::lane_bcast(up ? nv[1] : nv[0], src);
+            const float ps = lzw::lane_bcast(up ? pr[1] : pr[0], src);
+            const double qsel = up ? q[1] : q[0];
+            const double qs = __hiloint2double(lzw::lane_bcast(__double2hiint(qsel), src),
+                                               lzw::lane_bcast(__double2loint(qsel), src));
+            const int T = t.root_visits[g];
+            const double tm = (double)(T > 1 ? T : 1);
+            const double sq = sqrt(tm);
+            const double s_star = qs + t.c_puct * (double)ps * sq / (1.0 + (double)ns);
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int n = nv[r];
+                if (!ok[r] || n <= 0 || r * kWave + lane == cs) continue;
+                const double thr = (forced_k * (double)pr[r]) * tm;
+                int keep = 0;                                  // max(N - F, 0): F > N exactly when N * N < thr
+                if ((double)n * (double)n >= thr) {
+                    int m = (int)ceil(sqrt(thr));              // F by squares: corrected by one either way
+                    while (m > 0 && (double)(m - 1) * (double)(m - 1) >= thr) --m;
+                    while ((double)m * (double)m < thr) ++m;
+                    keep = n - m;
+                }
+                int least = n;                                 // L: nothing may be taken unless the gap is positive
+                const double gap = s_star - q[r];
+                if (gap > 0.0) {
+                    const double x = (t.c_puct * (double)pr[r] * sq) / gap - 1.0;
+                    least = x < 0.0 ? 0 : (x >= (double)n ? n : (int)floor(x) + 1);
+                }
+                int np = keep > least ? keep : least;
+                np = np < n ? np : n;
+                nv[r] = np <= 1 ? 0 : np;
+            }
+            const int cut = lzw::wave_incl_scan(((int)v[0] - nv[0]) + ((int)v[1] - nv[1]));
+            if (pruned_visits != nullptr && lane == kWave - 1) pruned_visits[g] = cut;
+        }
+        if (child_target_visits != nullptr) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int k = r * kWave + lane;
+                if (ok[r] && k < out_cap) child_target_visits[(size_t)g * out_cap + k] = nv[r];
+            }
+        }
+    }
+    if (target_temps == nullptr && !(prior_pseudocount > 0.f) && !(PRUNE && pruning)) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) if (ok[r]) prow[act[r]] = pol[r];
     } else {
         float sc[2] = {v[0], v[1]};
+        if (PRUNE && pruning) { sc[0] = (float)nv[0]; sc[1] = (float)nv[1]; }
         if (prior_pseudocount > 0.f) {
             const float c0 = ok[0] ? fmaxf(pr[0], 1e-8f) : 0.f, c1 = ok[1] ? fmaxf(pr[1], 1e-8f) : 0.f;
             const float psum = lzw::wave_sum(c0 + c1);
             const bool bad = !(psum > 0.f) || !isfinite(psum);
-            sc[0] = v[0] + prior_pseudocount * (bad ? 1.0f / (float)ne : c0 / psum);
-            sc[1] = v[1] + prior_pseudocount * (bad ? 1.0f / (float)ne : c1 / psum);
+            sc[0] = sc[0] + prior_pseudocount * (bad ? 1.0f / (float)ne : c0 / psum);
+            sc[1] = sc[1] + prior_pseudocount * (bad ? 1.0f / (float)ne : c1 / psum);
         }
         float tpol[2] = {0.f, 0.f};
         score_policy(sc, ok, target_temps != nullptr ? target_temps[g] : temp, lane, tpol);
@@ -1347,7 +1418,12 @@ int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (!tree_ok(d)) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: lz_tree_search only
     if (d->num_games == 0) return LZ_OK;
-    hipLaunchKernelGGL(tree_select_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), no_share(make_tree(d)));
+    if (forced_set(d))
+        hipLaunchKernelGGL(tree_select_kernel<true>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream),
+                           no_share(make_tree(d)), make_forced(d));
+    else
+        hipLaunchKernelGGL(tree_select_kernel<false>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream),
+                           no_share(make_tree(d)), ForcedArgs{});
     return st();
 }
 
@@ -1368,22 +1444,51 @@ int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const flo
     return st();
 }
 
+extern "C++" template <bool PRUNE>
+static int tree_finish_impl(const LzTreeDesc* d, const float* temperatures, const float* target_temperatures,
+                            float prior_pseudocount, const uint8_t* force_uniform, int sample_moves, const float* uniforms,
+                            float* policy_dense,
+                            int32_t* chosen_index, int32_t* chosen_code, uint8_t* chosen_valid, uint8_t* terminal_mask,
+                            float* root_value, int32_t* child_count, int32_t* child_action, int32_t* child_visits,
+                            float* child_prior, int64_t out_cap, int32_t* child_target_visits, int32_t* pruned_visits,
+                            void* stream) {
+    if (!tree_ok(d) || !temperatures || !policy_dense || !chosen_index || !chosen_code || !chosen_valid ||
+        !terminal_mask || !root_value || !child_count || !child_action || !child_visits || !child_prior || out_cap < 1)
+        return LZ_ERR_ARG;
+    if (d->num_games == 0) return LZ_OK;
+    if (!(prior_pseudocount >= 0.f) || ((force_uniform || sample_moves) && !uniforms)) return LZ_ERR_ARG;
+    if (PRUNE && !(d->forced_k >= 0.0)) return LZ_ERR_ARG;
+    hipLaunchKernelGGL(tree_finish_kernel<PRUNE>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
+                       temperatures, target_temperatures, prior_pseudocount, force_uniform, sample_moves, uniforms, policy_dense, chosen_index, reinterpret_cast<int4*>(chosen_code),
+                       chosen_valid, terminal_mask, root_value, child_count, child_action, child_visits, child_prior,
+                       (int)out_cap, PRUNE ? d->forced_k : 0.0, PRUNE ? d->root_noise : nullptr, child_target_visits,
+                       pruned_visits);
+    return st();
+}
+
 int lz_tree_finish(const LzTreeDesc* d, const float* temperatures, const float* target_temperatures,
                    float prior_pseudocount, const uint8_t* force_uniform, int sample_moves, const float* uniforms,
                    float* policy_dense,
                    int32_t* chosen_index, int32_t* chosen_code, uint8_t* chosen_valid, uint8_t* terminal_mask,
                    float* root_value, int32_t* child_count, int32_t* child_action, int32_t* child_visits,
                    float* child_prior, int64_t out_cap, void* stream) {
-    if (!tree_ok(d) || !temperatures || !policy_dense || !chosen_index || !chosen_code || !chosen_valid ||
-        !terminal_mask || !root_value || !child_count || !child_action || !child_visits || !child_prior || out_cap < 1)
-        return LZ_ERR_ARG;
-    if (d->num_games == 0) return LZ_OK;
-    if (!(prior_pseudocount >= 0.f) || ((force_uniform || sample_moves) && !uniforms)) return LZ_ERR_ARG;
-    hipLaunchKernelGGL(tree_finish_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
-                       temperatures, target_temperatures, prior_pseudocount, force_uniform, sample_moves, uniforms, policy_dense, chosen_index, reinterpret_cast<int4*>(chosen_code),
-                       chosen_valid, terminal_mask, root_value, child_count, child_action, child_visits, child_prior,
-                       (int)out_cap);
-    return st();
+    return tree_finish_impl<false>(d, temperatures, target_temperatures, prior_pseudocount, force_uniform, sample_moves,
+                                   uniforms, policy_dense, chosen_index, chosen_code, chosen_valid, terminal_mask,
+                                   root_value, child_count, child_action, child_visits, child_prior, out_cap, nullptr,
+                                   nullptr, stream);
+}
+
+int lz_tree_finish_pruned(const LzTreeDesc* d, const float* temperatures, const float* target_temperatures,
+                          float prior_pseudocount, const uint8_t* force_uniform, int sample_moves, const float* uniforms,
+                          float* policy_dense,
+                          int32_t* chosen_index, int32_t* chosen_code, uint8_t* chosen_valid, uint8_t* terminal_mask,
+                          float* root_value, int32_t* child_count, int32_t* child_action, int32_t* child_visits,
+                          float* child_prior, int64_t out_cap, int32_t* child_target_visits, int32_t* pruned_visits,
+                          void* stream) {
+    return tree_finish_impl<true>(d, temperatures, target_temperatures, prior_pseudocount, force_uniform, sample_moves,
+                                  uniforms, policy_dense, chosen_index, chosen_code, chosen_valid, terminal_mask,
+                                  root_value, child_count, child_action, child_visits, child_prior, out_cap,
+                                  child_target_visits, pruned_visits, stream);
 }
 
 static long long* g_advance_ticks = nullptr;
@@ -1437,8 +1542,9 @@ int lz_tree_advance(const LzTreeDesc* d, const int32_t* played_action, const uin
 //   begin -> [net -> expand_root + select] -> (sims-1) x [net -> expand+backup + select] -> net -> expand+backup
 // `continue_trees`: the roots were prepared by lz_tree_advance (kept subtrees or fresh roots), so no begin.
 // CAP: the kernels of the playout cap (LzTreeDesc.sim_budget / root_noise), the same launch sequence.
-extern "C++" template <bool CAP>
-static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const LzNetDesc* net, int64_t sims, float* lp1,
+// FORCED: the select kernels of forced playouts (LzTreeDesc.forced_k), the same launch sequence.
+extern "C++" template <bool CAP, bool FORCED>
+static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const ForcedArgs& fa, const LzNetDesc* net, int64_t sims, float* lp1,
                               float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                               float epsilon, void* stream) {
     const int64_t B = d->num_games;
@@ -1459,16 +1565,16 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                     hipLaunchKernelGGL((tree_expand_kernel<false, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
                                        lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap);
             } else if (s == 0) {
-                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap);
+                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP, FORCED>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa);
             } else {
                 (void)lz_prof_aux_begin(0, stream);
                 if (split_step(t.B))
-                    hipLaunchKernelGGL((tree_expand_select_split_kernel<true, CAP>), dim3(gw2(t.B)), dim3(kBlock), 0,
-                                       as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, cap);
+                    hipLaunchKernelGGL((tree_expand_select_split_kernel<true, CAP, FORCED>), dim3(gw2(t.B)), dim3(kBlock), 0,
+                                       as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, cap, fa);
                 else
-                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap);
+                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP, FORCED>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa);
                 (void)lz_prof_aux_end(0, stream, B);
             }
             if (s < sims)                                           // the leaves of simulation s + 1
@@ -1488,16 +1594,16 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                 hipLaunchKernelGGL((tree_expand_kernel<false, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
                                    lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap);
         } else if (s == 0) {
-            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap);
+            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP, FORCED>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa);
         } else {
             (void)lz_prof_aux_begin(0, stream);                      // no-ops unless lz_prof_enable(1) (never in a capture)
             if (split_step(t.B))
-                hipLaunchKernelGGL((tree_expand_select_split_kernel<false, CAP>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, (int)s, cap);
+                hipLaunchKernelGGL((tree_expand_select_split_kernel<false, CAP, FORCED>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, (int)s, cap, fa);
             else
-                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap);
+                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP, FORCED>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa);
             (void)lz_prof_aux_end(0, stream, B);
         }
     }
@@ -1517,9 +1623,14 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     // function of the packed state alone.  The step-by-step entry points (external evaluators) and the two-wave split
     // step (where the descent runs beside the expansion that inserts into the index) keep the index but do not look it up.
     const Tree t = split_step(B) ? no_share(make_tree(d)) : make_tree(d);
+    if (forced_set(d)) {
+        if (cap_set(d))
+            return tree_search_launch<true, true>(d, t, make_cap(d), make_forced(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_launch<false, true>(d, t, CapArrays{}, make_forced(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    }
     if (cap_set(d))
-        return tree_search_launch<true>(d, t, make_cap(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    return tree_search_launch<false>(d, t, CapArrays{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_launch<true, false>(d, t, make_cap(d), ForcedArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    return tree_search_launch<false, false>(d, t, CapArrays{}, ForcedArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
 }
 
 // lz_net.hip (internal): the checks of lz_net_forward_packed_multi_f16 on its networks
@@ -1533,6 +1644,7 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
                                   int64_t noise_stride, float epsilon, bool continue_trees, void* stream) {
     if (!tree_ok(d) || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: one network per search only
+    if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
     int rc = lz_net_multi_validate(nets, num_nets);
     if (rc) return rc;
     const int64_t B = d->num_games, G = d->seg_games;
@@ -1561,14 +1673,14 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
                                    lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, CapArrays{});
         } else if (s == 0) {
             hipLaunchKernelGGL((tree_expand_select_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{});
+                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{});
         } else {
             if (split_step(t.B))
                 hipLaunchKernelGGL((tree_expand_select_split_kernel<true>), dim3(gw2(t.B)), dim3(kBlock), 0,
-                                   as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, CapArrays{});
+                                   as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, CapArrays{}, ForcedArgs{});
             else
                 hipLaunchKernelGGL((tree_expand_select_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{});
+                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{});
         }
         if (s < sims) scan(s + 1);                                  // the leaves of simulation s + 1
     }
@@ -1695,6 +1807,7 @@ int lz_rng_uniform(uint64_t seed, const int64_t* game_id, const int64_t* ply, in
 int lz_tree_wave_select(const LzTreeDesc* d, const LzTreeWaveDesc* w, int64_t sims, int reset_budget, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || sims < 0) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
     if (d->num_games == 0) return LZ_OK;
     const Tree t = make_tree(d);
     const WaveArrays a = make_wave(w);
@@ -1722,6 +1835,7 @@ int lz_tree_search_waves(const LzTreeDesc* d, const LzTreeWaveDesc* w, const LzN
                          float* lp1, float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                          float epsilon, int continue_trees, int skip_roots, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || !net || sims < 0 || waves < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
+    if (forced_set(d)) return LZ_ERR_UNSUPPORTED;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = LZ_OK;

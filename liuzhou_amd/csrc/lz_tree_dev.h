@@ -96,6 +96,9 @@ struct Tree {
 // Optional playout cap (LzTreeDesc.sim_budget / root_noise): a trailing argument of the expand / select kernels, read only
 // by their CAP instantiations -- kept out of Tree so that every other kernel's arguments stay where they were.
 struct CapArrays { const int* sim_budget; const uint8_t* root_noise; };
+// Optional forced playouts (LzTreeDesc.forced_k / forced_count): handed over the same way, read only by the FORCED
+// instantiations of the select / expand + select kernels.
+struct ForcedArgs { double k; int* count; };
 
 // Edge / node records are read with plain (L1 + L2 cached, normal retention) 16-byte loads.  This is safe next to the
 // device-scope atomics of the backup because a launch never loads an edge line before its own atomics on it have
@@ -309,8 +312,13 @@ __device__ __forceinline__ void split_wait(volatile int* flag, int phase) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// FORCED (forced playouts, root level only): with forced_k > 0 a root child that has visits but fewer than
+// sqrt(forced_k * P * root visits) is "due"; the descent takes the due child with the lowest edge index and skips the score
+// arithmetic of that level.  The test is on squares, all in double: N * N < (k * P) * n.
+template <bool FORCED = false>
 __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, const RootInfo& root, int wait_edge = -1,
-                                            int nolegal_edge = -1, volatile int* flag = nullptr LZ_TSTAMP_ARG) {
+                                            int nolegal_edge = -1, volatile int* flag = nullptr, double forced_k = 0.0,
+                                            int* forced_count = nullptr LZ_TSTAMP_ARG) {
     if (t.root_terminal[g]) { if (lane == 0) t.leaf_kind[g] = kLeafInactive; return; }
     const Node* nodes = t.nodes + (size_t)g * t.node_cap;
     const Edge* edges = t.edges;                               // pool indices
@@ -341,6 +349,24 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
         if (LZ_TSTAMP_ON(g)) { LZ_TCLOCK(g, lv_t1) LZ_TADD(g, 16, lv_t1 - lv_t0) lv_t0 = lv_t1; }   // wait for the run
 #endif
         int chosen = -1;
+        if (FORCED && depth == 0 && forced_k > 0.0) {
+            bool due[2] = {false, false};
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                if (r == 1 && ne <= kWave) break;
+                if (r * kWave + lane < ne) {
+                    const double n = (double)edge_n(mine[r].n_info);
+                    due[r] = n > 0.0 && n * n < (forced_k * (double)mine[r].P) * (double)parent_n;
+                }
+            }
+            const uint64_t lo = __ballot(due[0]);
+            if (lo) chosen = __ffsll((unsigned long long)lo) - 1;
+            else if (ne > kWave) {
+                const uint64_t hi = __ballot(due[1]);
+                if (hi) chosen = kWave + __ffsll((unsigned long long)hi) - 1;
+            }
+            if (chosen >= 0 && forced_count != nullptr && lane == 0) forced_count[g] += 1;   // this game's wave is the only writer
+        }
         // ---- the argmax in single precision, accepted only when it is PROVABLY the double-precision argmax (round 6; opt-in:
         // same-box A/B on the bench's random-init nets 19.0 - 19.7 -> 19.7 - 20.2 us at 2 048 games, 67.0 -> 68.9 us at 16 384,
         // profiles/r06_tree_f32sel_ab.jsonl -- their priors are nearly flat, so most levels end in the double path anyway) ----
@@ -353,7 +379,7 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
         // as before; so does a level on which some |W / n| exceeds 1 (an external evaluator with another value scale: the
         // bound above assumes values in [-1, 1]).  The double arithmetic of a level (sqrt, two divisions, a 64-bit wave
         // maximum) was the largest single item of the step (profiles/r05_pmc_sq_tree.md: 1.76 k of ~2.6 k cycles per level).
-        if (t.fast_select) {
+        if ((!FORCED || chosen < 0) && t.fast_select) {
             const float sqf = sqrtf((float)(parent_n > 1 ? parent_n : 1));
             const float cf = (float)t.c_puct;
             float fs[2] = {-INFINITY, -INFINITY};
@@ -868,6 +894,8 @@ Tree make_tree(const LzTreeDesc* d) {
 inline Tree no_share(Tree t) { t.share = 0; return t; }     // paths that keep the index but do not look it up
 inline bool cap_set(const LzTreeDesc* d) { return d->sim_budget != nullptr || d->root_noise != nullptr; }
 inline CapArrays make_cap(const LzTreeDesc* d) { return CapArrays{d->sim_budget, d->root_noise}; }
+inline bool forced_set(const LzTreeDesc* d) { return d->forced_k > 0.0; }
+inline ForcedArgs make_forced(const LzTreeDesc* d) { return ForcedArgs{d->forced_k, d->forced_count}; }
 bool tree_ok(const LzTreeDesc* d) {
     return d && d->num_games >= 0 && d->node_cap >= 2 && d->path_cap >= 3 &&
            d->edge_chunk >= 128 && (d->edge_chunk & (d->edge_chunk - 1)) == 0 && d->chunk_cap >= 1 &&

@@ -79,6 +79,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
                                                   "mixed_value_target_summary": []}
     bps_num = bps_den = 0
     cap_meta: Optional[Dict[str, Any]] = None
+    forced_meta: Optional[Dict[str, Any]] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -96,6 +97,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         wcap = (wm.get("metadata") or {}).get("playout_cap")
         if isinstance(wcap, dict) and cap_meta is None:
             cap_meta = {"fast_simulations": int(wcap.get("fast_simulations", 0)), "full_prob": float(wcap.get("full_prob", 1.0))}
+        wforced = (wm.get("metadata") or {}).get("forced_playouts")
+        if isinstance(wforced, dict) and forced_meta is None:
+            forced_meta = {"k": float(wforced.get("k", 0.0))}
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -113,6 +117,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     if cap_meta is not None:            # playout cap: its settings and the searches of every kind over all workers
         meta["playout_cap"] = {**cap_meta, **{k: int(merged.mcts_counters.get(k, 0))
                                               for k in ("full_searches", "fast_searches")}}
+    if forced_meta is not None:         # forced playouts: k, forced descents and pruned visits over all workers
+        meta["forced_playouts"] = {**forced_meta, **{k: int(merged.mcts_counters.get(k, 0))
+                                                     for k in ("forced_playouts", "pruned_visits")}}
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -135,13 +142,18 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         policy_target_prior_pseudocount: float = 0.0, sample_moves: bool = True,
                         eval_symmetry: Any = "none", worker_fn: Optional[Callable[..., Dict[str, Any]]] = None,
                         in_process: bool = False, playout_cap_fast_simulations: int = 0,
-                        playout_cap_full_prob: float = 1.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        playout_cap_full_prob: float = 1.0, forced_playouts_k: float = 0.0
+                        ) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
     "random" or a fixed id 0..7) reaches the workers only when it is not "none"; so do `playout_cap_fast_simulations` /
-    `playout_cap_full_prob` (tree backend, playout cap randomization) only when the cap is on."""
-    from .tree_engine import playout_cap_on
+    `playout_cap_full_prob` (tree backend, playout cap randomization) only when the cap is on, and `forced_playouts_k`
+    (tree backend, forced playouts and policy target pruning) only when it is > 0."""
+    from .tree_engine import forced_playouts_on, playout_cap_on
+    forced = forced_playouts_on(forced_playouts_k)
+    if forced and str(search_backend).strip().lower() not in ("portable", "tree"):
+        raise ValueError(f"forced playouts need the tree backend, not the root-PUCT search ({search_backend!r})")
     cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
     if cap and str(search_backend).strip().lower() not in ("portable", "tree"):
         raise ValueError(f"playout cap randomization needs the tree backend, not the root-PUCT search ({search_backend!r})")
@@ -180,7 +192,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             chunk_output_dir=out_dir, chunk_file_prefix=f"{stem}.w{idx:02d}", chunk_file_ext=ext,
             **({} if eval_symmetry == "none" else {"eval_symmetry": eval_symmetry}),
             **({"playout_cap_fast_simulations": int(playout_cap_fast_simulations),
-                "playout_cap_full_prob": float(playout_cap_full_prob)} if cap else {}))
+                "playout_cap_full_prob": float(playout_cap_full_prob)} if cap else {}),
+            **({"forced_playouts_k": float(forced_playouts_k)} if forced else {}))
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

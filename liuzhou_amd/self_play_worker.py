@@ -580,11 +580,17 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          search_backend: str = "cuda_root", portable_mcts_backend: str = "python",
                          portable_cpp_threads: int = 1, policy_target_temperature: Optional[float] = None,
                          policy_target_prior_pseudocount: float = 0.0, eval_symmetry="none",
-                         playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0) -> Dict[str, Any]:
+                         playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
+                         forced_playouts_k: float = 0.0) -> Dict[str, Any]:
     """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
     `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
-    tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on."""
-    from .tree_engine import parse_eval_symmetry, playout_cap_on
+    tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on.
+    `forced_playouts_k` (tree backend only; 0 = off): forced playouts and policy target pruning, see
+    tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["forced_playouts"] when on."""
+    from .tree_engine import forced_playouts_on, parse_eval_symmetry, playout_cap_on
+    forced = forced_playouts_on(forced_playouts_k)
+    if forced and str(search_backend).strip().lower() not in ("portable", "tree"):
+        raise ValueError(f"forced playouts need the tree backend, not the root-PUCT search ({search_backend!r})")
     eval_symmetry = parse_eval_symmetry(eval_symmetry)
     cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
     if cap and str(search_backend).strip().lower() not in ("portable", "tree"):
@@ -657,7 +663,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                           seed=rng_seed, collect_timing=os.environ.get("LZ_WORKER_TIMING", "1") != "0", row_log=row_log,
                                           eval_symmetry=eval_symmetry,
                                           playout_cap_fast_simulations=int(playout_cap_fast_simulations) if cap else 0,
-                                          playout_cap_full_prob=float(playout_cap_full_prob) if cap else 1.0, **common)
+                                          playout_cap_full_prob=float(playout_cap_full_prob) if cap else 1.0,
+                                          **({"forced_playouts_k": float(forced_playouts_k)} if forced else {}), **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
                                     sparse_top_k=int(sparse_top_k), row_log=row_log, **common)
@@ -675,7 +682,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        "streamed": bool(stream), **({"stream_fallback": stream_fallback} if stream_fallback else {}),
                        **({"eval_symmetry": eval_symmetry} if eval_symmetry != "none" else {}),
                        **({"playout_cap": {"fast_simulations": int(playout_cap_fast_simulations),
-                                           "full_prob": float(playout_cap_full_prob)}} if cap else {})}
+                                           "full_prob": float(playout_cap_full_prob)}} if cap else {}),
+                       **({"forced_playouts": {"k": float(forced_playouts_k)}} if forced else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

@@ -12,6 +12,7 @@ prepare roots -> evaluate -> complete, then sims x (select -> evaluate -> comple
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import sys
 import time
@@ -51,7 +52,8 @@ class LzTreeDesc(C.Structure):
                [(n, C.c_void_p) for n in ("leaf_sym", "trace_sym", "sym_salt", "sym_game", "sym_ply")] + \
                [("sym_seed", C.c_uint64), ("sym_mode", C.c_int32), ("sym_fixed", C.c_int32)] + \
                [("seg_games", C.c_int64), ("seg_off", C.c_void_p)] + \
-               [(n, C.c_void_p) for n in ("sim_budget", "root_noise")]
+               [(n, C.c_void_p) for n in ("sim_budget", "root_noise")] + \
+               [("forced_k", C.c_double), ("forced_count", C.c_void_p)]
 
 
 def playout_cap_on(fast_simulations: int, full_prob: float, sims: int) -> bool:
@@ -173,6 +175,14 @@ def samples_per_launch_pass(net) -> int:
     return groups * (16 if (ch == 64 and not flags & 1) else 8)
 
 
+def forced_playouts_on(k) -> bool:
+    """Validate `forced_playouts_k`: 0 = off, a positive finite number = on; negative or non-finite is a ValueError."""
+    k = float(k)
+    if not math.isfinite(k) or k < 0.0:
+        raise ValueError(f"forced_playouts_k must be a finite number >= 0 (0 = off), got {k}")
+    return k > 0.0
+
+
 class TreeEngine:
     def __init__(self, num_games: int, max_sims: int, device, exploration_weight: float = 1.0,
                  reuse_factor: float = 0.0, batch_k: int = 1, edge_chunk: int = EDGE_CHUNK,
@@ -285,6 +295,11 @@ class TreeEngine:
         self.desc.eval_count = self.eval_count.data_ptr()
         self.share_count = z((B,), torch.int32)         # leaves that took a transposed twin's evaluation (LzTreeDesc.share_count)
         self.desc.share_count = self.share_count.data_ptr()
+        # forced playouts and policy target pruning (set_forced_playouts; LzTreeDesc.forced_k / forced_count)
+        self.forced_k = 0.0
+        self.forced_count = z((B,), torch.int32)        # descents that took a due root child, summed over the searches
+        self.child_target_visits = z((B, OUT_CAP), torch.int32)   # finish() with forced_k > 0: the pruned visits N' of the target
+        self.pruned_visits = z((B,), torch.int32)       # finish() with forced_k > 0: sum(N - N') of the last search
         self.segment_games = None if segment_games is None else int(segment_games)
         self.num_segments = 1
         if self.segment_games is not None:
@@ -371,6 +386,22 @@ class TreeEngine:
                 raise ValueError(f"{name} must be a contiguous {dt} tensor of {self.B} elements on {self.device}")
             setattr(self.desc, name, None if t is None else t.data_ptr())
         self._cap_arrays = (sim_budget, root_noise)              # keep them alive while the descriptor points at them
+
+    def set_forced_playouts(self, k: float) -> None:
+        """Forced playouts and policy target pruning (LzTreeDesc.forced_k; 0 = off): select() and search() force due root
+        children in the games whose root-noise switch is on, finish() forms the training target from the pruned visits
+        (`child_target_visits`, `pruned_visits`; `forced_count` sums the forced descents).  Must be set before a search is
+        captured into a graph."""
+        on = forced_playouts_on(k)
+        if on and self.batch_k > 1:
+            raise ValueError("forced playouts are not supported by the legacy waves (batch_k > 1)")
+        if on and self.segment_games is not None:
+            raise ValueError("forced playouts are not supported with several networks in one search")
+        self.forced_k = float(k)
+        self.desc.forced_k = self.forced_k
+        self.desc.forced_count = self.forced_count.data_ptr() if on else None
+        if on:
+            self.persistent = False       # the persistent kernel refuses the descriptor: the launch-pair search
 
     _NODE_DT = [("w0", "<u8"), ("w1", "<u8"), ("w2", "<u8"), ("w3", "<u8"), ("edge_begin", "<i4"), ("nedges", "<i4"),
                 ("parent", "<i4"), ("old_begin", "<i4")]
@@ -492,11 +523,24 @@ class TreeEngine:
 
     def finish(self, temperatures: torch.Tensor, uniforms: Optional[torch.Tensor],
                target_temperatures: Optional[torch.Tensor] = None, prior_pseudocount: float = 0.0,
-               force_uniform: Optional[torch.Tensor] = None, sample_moves: Optional[bool] = None) -> None:
-        """`sample_moves` defaults to "sample iff uniforms are given"."""
+               force_uniform: Optional[torch.Tensor] = None, sample_moves: Optional[bool] = None,
+               pruned: Optional[bool] = None) -> None:
+        """`sample_moves` defaults to "sample iff uniforms are given".  `pruned`: go through lz_tree_finish_pruned (default:
+        when forced playouts are on; with forced_k = 0 it writes what lz_tree_finish writes, `child_target_visits` =
+        `child_visits` and `pruned_visits` = 0)."""
         sample = uniforms is not None if sample_moves is None else bool(sample_moves)
         if force_uniform is not None and force_uniform.dtype != torch.uint8:
             force_uniform = force_uniform.to(torch.uint8)
+        if (self.forced_k > 0.0) if pruned is None else bool(pruned):   # policy target pruning: the same outputs + N' / the cut
+            with torch.cuda.device(self.device):
+                L.check(L.lib().lz_tree_finish_pruned(
+                    C.byref(self.desc), L.ptr(temperatures), L.ptr(target_temperatures), C.c_float(float(prior_pseudocount)),
+                    L.ptr(force_uniform), C.c_int(int(sample)), L.ptr(uniforms), L.ptr(self.policy_dense),
+                    L.ptr(self.chosen_index), L.ptr(self.chosen_code), L.ptr(self.chosen_valid), L.ptr(self.terminal_mask),
+                    L.ptr(self.root_value), L.ptr(self.child_count), L.ptr(self.child_action), L.ptr(self.child_visits),
+                    L.ptr(self.child_prior), L.i64(OUT_CAP), L.ptr(self.child_target_visits), L.ptr(self.pruned_visits),
+                    self._stream()), "tree_finish_pruned")
+            return
         with torch.cuda.device(self.device):
             L.check(L.lib().lz_tree_finish(C.byref(self.desc), L.ptr(temperatures), L.ptr(target_temperatures),
                                            C.c_float(float(prior_pseudocount)), L.ptr(force_uniform), C.c_int(int(sample)),
@@ -649,7 +693,7 @@ class PortableTreeMCTS:
                  game_offset: int = 0, game_stride: Optional[int] = None, trace: bool = False,
                  collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none",
                  segment_games: Optional[int] = None, multi_launch: bool = True, fast_simulations: int = 0,
-                 full_prob: float = 1.0) -> None:
+                 full_prob: float = 1.0, forced_playouts_k: float = 0.0) -> None:
         """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
         searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
         FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
@@ -677,9 +721,23 @@ class PortableTreeMCTS:
         search of game g at ply t is full (num_simulations, root noise) when uniform(seed, g, t, purpose 3) < full_prob,
         else fast (fast_simulations, no root noise).  The mask of the last search is `full_search` (uint8[B]); parity
         runs inject one through `injected_full_search`.  Searches then always use the compact lists; not with batch_k > 1,
-        several networks, an external evaluator or the persistent kernel (ValueError)."""
+        several networks, an external evaluator or the persistent kernel (ValueError).
+        `forced_playouts_k` k (0 = off): forced playouts and policy target pruning (Wu 2019, section 3.2) in the searches
+        whose root-noise switch is on (every search without the cap, the full ones with it): a root child with N > 0 and
+        N^2 < k P n is visited before PUCT is asked, and the training target (policy_dense) is formed from the pruned
+        visits; the move pick and the kept subtree use the raw visits.  `forced_counts` (int64[2]): forced descents and
+        pruned visits so far.  Refused where the cap is refused (ValueError)."""
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
+        self.forced = forced_playouts_on(forced_playouts_k)
+        self.forced_playouts_k = float(forced_playouts_k)
+        if self.forced:
+            why = ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
+                   "several networks in one search" if self.multi or len(self.nets) != 1 else
+                   "an external evaluator (split-phase path)" if not isinstance(self.nets[0], FusedNet) else
+                   "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else None)
+            if why is not None:
+                raise ValueError(f"forced playouts are not supported with {why}")
         self.cap = playout_cap_on(fast_simulations, full_prob, num_simulations)
         self.fast_simulations, self.full_prob = int(fast_simulations), float(full_prob)
         if self.cap:
@@ -726,6 +784,9 @@ class PortableTreeMCTS:
                                  segment_games=segment_games if self.fused_multi else None)
         if trace:
             self.engine.enable_trace()
+        if self.forced:
+            self.engine.set_forced_playouts(self.forced_playouts_k)
+        self._pruned_total = torch.zeros((1,), dtype=torch.int64, device=self.engine.device)   # sum of pruned_visits
         if not self.fused:
             if self.batch_k > 1:
                 raise ValueError("an external evaluator supports batch_k = 1 only")
@@ -779,6 +840,11 @@ class PortableTreeMCTS:
     def last_full_search(self) -> Optional[torch.Tensor]:
         """bool[B]: which games' last search was full (None: the playout cap is off)."""
         return self.full_search.bool() if self.cap else None
+
+    @property
+    def forced_counts(self) -> torch.Tensor:
+        """int64[2] on the device: forced descents and pruned visits of the searches so far (zeros when off)."""
+        return torch.cat((self.engine.forced_count.sum(dtype=torch.int64).view(1), self._pruned_total))
 
     def _draw_playout_cap(self, active: Optional[torch.Tensor]) -> None:
         """Full / fast mask of this move on the device (no host synchronisation): u = uniform(seed, game, ply, purpose 3),
@@ -928,9 +994,12 @@ class PortableTreeMCTS:
                 # (an engine with compact lists warms up both launch forms: the other one may be captured later inside a
                 #  continued search, which cannot be preceded by a warm-up of its own)
                 counted = (e.live_total.clone(), e.eval_count.clone(), e.share_count.clone())   # warm-ups are not searches
+                forced_counted = e.forced_count.clone() if self.forced else None
                 for form in ((lists, not lists) if (e.compact_evals and not self.fused_multi) else (lists,)):
                     self._run_search(min(self.sims, 2), noise, False, form)
                 e.live_total.copy_(counted[0]); e.eval_count.copy_(counted[1]); e.share_count.copy_(counted[2])
+                if forced_counted is not None:
+                    e.forced_count.copy_(forced_counted)
             torch.cuda.synchronize(e.device)
             try:
                 g = torch.cuda.CUDAGraph()
@@ -1019,6 +1088,7 @@ class PortableTreeMCTS:
         self.engine.live_total.zero_()
         self.engine.reuse_dropped.zero_()
         self.cap_counts.zero_()
+        self.engine.forced_count.zero_(); self._pruned_total.zero_()
         # refused expansions / fewest free chunks are per run too (a cached engine must not report an earlier run's)
         # (pool_stats[2], the chunks reserved for fresh roots, follows the trees' state and is NOT a per-run statistic)
         self.engine.buf["pool_stats"][:2].copy_(torch.tensor([0, self.engine.pool_chunks], dtype=torch.int32))
@@ -1042,6 +1112,7 @@ class PortableTreeMCTS:
         self.engine.share_count.zero_()
         self.engine.live_total.zero_()
         self.cap_counts.zero_()
+        self.engine.forced_count.zero_(); self._pruned_total.zero_()
         self.get_timing(reset=True)
         if self.batch_k > 1:
             self.engine.wbuf["eval_total"].zero_(); self.engine.wbuf["eval_count"].zero_()
@@ -1117,6 +1188,8 @@ class PortableTreeMCTS:
             temps = temperatures.to(torch.float32).contiguous()
             tt = None if self.target_temperature is None else torch.full_like(temps, self.target_temperature)
             e.finish(temps, uniforms, tt, self.prior_pseudocount, force_uniform_random_mask, self.sample_moves)
+            if self.forced:
+                self._pruned_total.add_(e.pruned_visits.sum(dtype=torch.int64))
             model_input = states_to_model_input(state)
             legal_mask, _ = encode_actions_fast(state)
         return RootSearchBatchOutput(
@@ -1166,6 +1239,7 @@ class DualStreamTreeMCTS:
         self.sims = int(num_simulations)
         # playout cap: one full / fast mask over all games, each part writing its slice (the wave tail reads the whole)
         self.cap = self.parts[0].cap
+        self.forced = self.parts[0].forced
         self.full_search = None
         if self.cap:
             self.full_search = torch.zeros((self.B,), dtype=torch.uint8, device=dev)
@@ -1198,6 +1272,10 @@ class DualStreamTreeMCTS:
     @property
     def cap_counts(self) -> torch.Tensor:
         return sum(p.cap_counts for p in self.parts)
+
+    @property
+    def forced_counts(self) -> torch.Tensor:
+        return sum(p.forced_counts for p in self.parts)
 
     @property
     def last_full_search(self) -> Optional[torch.Tensor]:
@@ -1448,8 +1526,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        reuse_factor: float = -1.0, dual_stream: Optional[bool] = None, continuous_waves: bool = True,
                        device_tail: bool = True, batch_k: int = 1, evaluator: str = "auto", seed: int = 12345,
                        collect_timing: bool = False, row_log=None, eval_symmetry="none",
-                       playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0
-                       ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
+                       playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
+                       forced_playouts_k: float = 0.0) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
     `model` may also be a `PriorEvaluator` (states -> priors over the 220 actions + values, the reference's own
@@ -1465,9 +1543,13 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     mcts_simulations): a move's search is full with probability p (drawn per game and ply) and records a training row,
     otherwise it is a fast search of F simulations without root noise that only advances the game.  `num_positions`
     counts recorded rows, `avg_game_length` plies; mcts_counters gain full_searches / fast_searches /
-    recorded_positions.  Fused network and batch_k = 1 only (ValueError otherwise)."""
+    recorded_positions.  Fused network and batch_k = 1 only (ValueError otherwise).
+    `forced_playouts_k` k (0 = off): forced playouts and policy target pruning (PortableTreeMCTS) in every search that
+    records a row; mcts_counters gain forced_playouts / pruned_visits.  Fused network and batch_k = 1 only (ValueError
+    otherwise)."""
     dev = torch.device(device)
     cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
+    forced = forced_playouts_on(forced_playouts_k)
     eval_symmetry = parse_eval_symmetry(eval_symmetry)
     if eval_symmetry != "none" and int(batch_k) > 1:
         raise ValueError("eval_symmetry is not supported by the legacy waves (batch_k > 1): their wave kernels evaluate "
@@ -1491,6 +1573,11 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     if cap and (not use_fused or int(batch_k) > 1):
         raise ValueError("playout cap randomization needs the fused network search with batch_k = 1 (not the external-"
                          "module evaluator, not legacy waves)")
+    if forced and (not use_fused or int(batch_k) > 1):
+        raise ValueError("forced playouts need the fused network search with batch_k = 1 (not the external-module "
+                         "evaluator, not legacy waves)")
+    if forced and _persistent_default():
+        raise ValueError("forced playouts are not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
     if use_fused and persistent_search_available(net, batch_k) and eval_symmetry == "none":
         if cap:
             raise ValueError("playout cap randomization is not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
@@ -1507,6 +1594,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         kw["eval_symmetry"] = eval_symmetry
     if cap:
         kw.update(fast_simulations=int(playout_cap_fast_simulations), full_prob=float(playout_cap_full_prob))
+    if forced:
+        kw["forced_playouts_k"] = float(forced_playouts_k)
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a
@@ -1681,6 +1770,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                            "plies_launched": int(tail.plies_launched)} if tail is not None else {}),
                        # playout cap: searches of live games by kind, and the rows the full ones recorded
                        **(dict(zip(("full_searches", "fast_searches"), (int(x) for x in mcts.cap_counts.tolist())),
-                               recorded_positions=int(positions)) if cap else {})},
+                               recorded_positions=int(positions)) if cap else {}),
+                       # forced playouts: descents that took a due root child, visits pruned from the training targets
+                       **(dict(zip(("forced_playouts", "pruned_visits"), (int(x) for x in mcts.forced_counts.tolist())))
+                          if forced else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))
     return batch, stats
