@@ -493,6 +493,46 @@ typedef struct LzTreeDesc {
      * persistent searches refuse a descriptor with forced_k > 0 (LZ_ERR_UNSUPPORTED). */
     double   forced_k;
     int32_t* forced_count;         /* [B] optional: += 1 for every descent that took a due child */
+    /* Optional Gumbel root search with Sequential Halving (Danihelka, Guez, Schrittwieser, Silver: "Policy improvement by
+     * planning with Gumbel", ICLR 2022; gumbel_m == 0 = off).  A game's search is a Gumbel search when gumbel_m > 0 and
+     * its root-noise switch is on (root_noise == NULL, or root_noise[g] != 0); such a search never mixes Dirichlet noise
+     * into its root priors (the searches ignore `noise` when gumbel_m > 0).  Notation for a root with ne children in edge
+     * order k: P(k) the stored prior, N(k), W(k) the edge statistics, q(k) the root mover's mean value (N > 0 only).
+     *   Root step (the root expansion of lz_tree_expand(is_root) / lz_tree_search / _continue, fresh and kept roots alike):
+     *     gumbel_gl[g][k]    = gumbel_g[g][k] + logf(P(k)) in fp32 (-inf where P = 0),
+     *     gumbel_base[g][k]  = N0(k) = N(k) at this step, gumbel_root_base[g] = the root's own visit count at this step,
+     *     gumbel_root_value[g] = v0: the network value of a root expanded in this step; for a kept root its mean value
+     *                          root_w / root_visits as it stands (0 without visits).
+     *   These are the only places where a transcendental function or the network touches the rule.  Everything below is
+     *   double arithmetic of + - * / and comparisons on those stored bits.  Sums over the children run in ONE fixed order:
+     *   lane l of 64 adds the terms of children l and l + 64 (a missing term is +0.0), then an xor butterfly over the
+     *   lanes with offsets 32, 16, 8, 4, 2, 1 (x[l] = x[l] + x[l ^ offset]).
+     *     Pv = sum_{N>0} P(k),  Pq = sum_{N>0} P(k) * q(k),  T = sum N(k) (integer),
+     *     vmix = v0 when T == 0 or Pv <= 0, else (v0 + T * (Pq / Pv)) / (1 + T),
+     *     cq(k) = q(k) for N(k) > 0, else vmix,
+     *     sigma(k) = ((gumbel_c_visit + max_k N(k)) * gumbel_c_scale) * (0.5 * cq(k)),
+     *     score(k) = (double)gl(k) + sigma(k).
+     *   Several of these put a product next to a sum: both libraries are built with floating-point contraction off
+     *   (-ffp-contract=off), and the bit-for-bit checks against a host restatement rely on it.
+     *   Selection, root level only: s = root_visits - gumbel_root_base[g] (the simulations this search has started),
+     *   j = min(gumbel_m, ne), cv = gumbel_table[j * gumbel_sims + min(s, gumbel_sims - 1)]; the candidates are the
+     *   children with N(k) - N0(k) == cv, all children if there is none; the descent takes the candidate with the largest
+     *   score, lowest edge index among equals.  No PUCT arithmetic runs on that level; deeper levels are unchanged.
+     * Honoured by lz_tree_select, lz_tree_expand (root step), lz_tree_search / _continue and lz_tree_finish_gumbel; the
+     * wave, multi-network and persistent searches refuse a descriptor with gumbel_m > 0 (LZ_ERR_UNSUPPORTED), and so does
+     * every entry point when forced_k > 0 as well (two rules for the same level). */
+    int32_t  gumbel_m;             /* considered actions m, 0..72 */
+    int32_t  gumbel_sims;          /* n: row length of gumbel_table (the simulations of a search) */
+    double   gumbel_c_visit, gumbel_c_scale;
+    const float* gumbel_g;         /* [B][gumbel_stride] standard Gumbel variates per child rank (lz_rng_gumbel) */
+    const int32_t* gumbel_table;   /* [(gumbel_m + 1)][gumbel_sims] visit count a considered child has at simulation s */
+    float*   gumbel_gl;            /* [B][gumbel_stride] */
+    int32_t* gumbel_base;          /* [B][gumbel_stride] */
+    int32_t* gumbel_root_base;     /* [B] */
+    float*   gumbel_root_value;    /* [B] */
+    int32_t* gumbel_count;         /* [B] optional: += 1 for every search whose root step ran the rule */
+    int64_t  gumbel_stride;        /* row stride of gumbel_g / gumbel_gl / gumbel_base, >= 72; a child at or beyond it has
+                                      gl = -inf and N0 = 0 */
 } LzTreeDesc;
 LZ_API int64_t lz_tree_desc_bytes(void);
 
@@ -581,6 +621,23 @@ LZ_API int lz_tree_finish_pruned(const LzTreeDesc* tree, const float* temperatur
                                  int32_t* child_count, int32_t* child_action, int32_t* child_visits,
                                  float* child_prior, int64_t out_cap, int32_t* child_target_visits,
                                  int32_t* pruned_visits, void* stream);
+/* lz_tree_finish plus the Gumbel rule (LzTreeDesc.gumbel_*).  For a game that is not a Gumbel game (gumbel_m == 0, its
+ * root-noise switch off, a terminal root) it writes byte for byte what lz_tree_finish writes.  For a Gumbel game, with the
+ * completed values and score(k) of LzTreeDesc formed from the statistics as they stand:
+ *   pick:   L(k) = N(k) - N0(k); among the children with L(k) == max L the largest score, lowest index among equals.
+ *           Temperatures, sample_moves and the pick uniform are ignored; force_uniform keeps precedence.
+ *   target: policy_dense[act(k)] = softmax_k(log P(k) + sigma(k)) over all children, in double with the maximum
+ *           subtracted, written as fp32; children with P = 0 get 0 (log P(k): the double logarithm of the stored prior).
+ * child_visits, child_prior, root_value: raw.  gumbel_score double[B,out_cap] (the final score; 0 for other games and
+ * beyond the children) and gumbel_vmix double[B] are optional. */
+LZ_API int lz_tree_finish_gumbel(const LzTreeDesc* tree, const float* temperatures, const float* target_temperatures,
+                                 float prior_pseudocount, const uint8_t* force_uniform, int sample_moves,
+                                 const float* uniforms,
+                                 float* policy_dense /*[B,220]*/, int32_t* chosen_index, int32_t* chosen_code /*[B,4]*/,
+                                 uint8_t* chosen_valid, uint8_t* terminal_mask, float* root_value,
+                                 int32_t* child_count, int32_t* child_action, int32_t* child_visits,
+                                 float* child_prior, int64_t out_cap, double* gumbel_score, double* gumbel_vmix,
+                                 void* stream);
 /* One whole search enqueued from C++: begin, root evaluation + expansion, then `sims` x
  * (select -> planes -> fused network -> expand + backup).  No host synchronisation; capturable. */
 LZ_API int lz_tree_search(const LzTreeDesc* tree, const LzNetDesc* net, int64_t sims, float* planes /*[B,11,36]*/,
@@ -607,11 +664,20 @@ LZ_API int lz_tree_search_multi_continue(const LzTreeDesc* tree, const LzNetDesc
  *                   normalised over a game's legal children these are Dirichlet(alpha) noise.
  *   lz_rng_uniform: out[g] = uniform [0,1) for `purpose` (1 = move pick, 2 = opening move, 3 = full / fast search of
  *                   the playout cap) of game_id[g] at ply[g].
+ *   lz_rng_gumbel:  out[g*stride + k] = standard Gumbel draw for child rank k < count (<= 1023) of game_id[g] at ply[g]:
+ *                   x = first word of the block (purpose 3, index 1 + k, attempt 0), u = ((float)(x >> 9) + 0.5f) * 2^-23,
+ *                   g = -log(-log(u)) with both logarithms in double, rounded to fp32 once (an fp32 inner logarithm
+ *                   would leave g with an absolute error of 6e-8 where g is close to 0).  Purpose 3 is the playout cap's, which uses index 0 only.
  * game_id NULL: g itself; ply NULL: 0. */
 LZ_API int lz_rng_gamma(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t batch, float alpha,
                         int64_t count, float* out, int64_t stride, void* stream);
 LZ_API int lz_rng_uniform(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t batch, int purpose,
                           float* out, void* stream);
+LZ_API int lz_rng_gumbel(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t batch, int64_t count,
+                         float* out, int64_t stride, void* stream);
+/* the uniforms u behind lz_rng_gumbel's variates (tests: they must equal a host restatement bit for bit) */
+LZ_API int lz_rng_gumbel_uniform(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t batch, int64_t count,
+                                 float* out, int64_t stride, void* stream);
 
 /* ---- fused root-PUCT search (variant R) on packed states -------------------------------------------------
  * The host chain of v1/python/mcts_gpu.py:1249-1457 (encode -> project -> root_pack -> noise -> apply -> evaluate

@@ -83,11 +83,22 @@ __global__ __launch_bounds__(kBlock) void pos_clear_kernel(int* __restrict__ tab
 
 // FORCED (here and in the expand + select kernels): forced playouts at the root level (`fa`, tree_select); the default
 // instantiations never read it.
-template <bool FORCED = false>
-__global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t, ForcedArgs fa) {
+// GUMBEL (here and in the expand + select kernels): the Gumbel root search (`ga`, tree_select); likewise never read by the
+// other instantiations.
+template <bool FORCED = false, bool GUMBEL = false>
+__global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t, ForcedArgs fa, GumbelArgs ga) {
     const int g = wave_game();
     if (g >= t.B) return;
-    tree_select<FORCED>(t, g, lane_id(), load_root_info(t, g), -1, -1, nullptr, FORCED ? fa.k : 0.0, fa.count);
+    tree_select<FORCED, GUMBEL>(t, g, lane_id(), load_root_info(t, g), -1, -1, nullptr, FORCED ? fa.k : 0.0, fa.count,
+                                &ga, GUMBEL);
+}
+// the root step's snapshot as a launch of its own (lz_tree_expand with is_root: the step-by-step protocol)
+__global__ __launch_bounds__(kBlock) void gumbel_root_kernel(Tree t, GumbelArgs ga,
+                                                             const uint8_t* __restrict__ root_noise) {
+    const int g = wave_game();
+    if (g >= t.B) return;
+    if (root_noise != nullptr && root_noise[g] == 0) return;
+    gumbel_root_step(t, g, lane_id(), ga);
 }
 
 
@@ -241,14 +252,14 @@ __global__ __launch_bounds__(kScanBlock) void tree_live_scan_seg_kernel(Tree t, 
 // expand + backup of simulation s fused with the selection of simulation s+1 (same wave, same game: the edge
 // records it just touched are still in L1/L2) -- one launch per simulation besides the network kernel.
 // (forcing 8 waves / SIMD -- <= 96 SGPRs, 126 scalar spills -- was measured: no gain at 16 384 games, 1 % slower at C2)
-template <bool IS_ROOT, bool COMPACT = false, bool CAP = false, bool FORCED = false>
+template <bool IS_ROOT, bool COMPACT = false, bool CAP = false, bool FORCED = false, bool GUMBEL = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, const float* __restrict__ lp1,
                                                                     const float* __restrict__ lp2,
                                                                     const float* __restrict__ lpm,
                                                                     const float* __restrict__ values,
                                                                     const float* __restrict__ noise, int noise_stride,
                                                                     float epsilon, int step, CapArrays cap,
-                                                                    ForcedArgs fa) {
+                                                                    ForcedArgs fa, GumbelArgs ga) {
 #ifndef LZ_EXP_NO_TREE_PRIO
     // The kernel is a chain of dependent loads with a few dozen instructions in between; in the two-stream search it
     // shares the SIMDs with the other half's network waves, which always have MFMAs to issue.  Raised wave priority
@@ -269,6 +280,9 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
     tree_expand<IS_ROOT>(t, g, lane, lp1 + o * 36, lp2 + o * 36, lpm + o * 36, nullptr, values + o, noise, noise_stride,
                          epsilon, sc, &root, step, nullptr, nullptr LZ_TSTAMP_PASS);
     __threadfence_block();
+    // Gumbel search: the games whose root-noise switch is on, as with forced playouts; the root step records gl, N0, v0
+    const bool gum_on = GUMBEL && (!CAP || cap_noise(cap, g));
+    if (GUMBEL && IS_ROOT && gum_on) { gumbel_root_step(t, g, lane, ga); __threadfence_block(); }
     if (CAP && cap_spent(cap, g, step)) {                        // budget spent: no further leaf, out of the lists
         if (lane == 0) t.leaf_kind[g] = kLeafInactive;
         return;
@@ -277,7 +291,7 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
     LZ_TSTAMP(g, 7)                                            // fence (+ root reload)
     // forced playouts: the games whose root-noise switch is on (every game without the cap, the full searches with it)
     const double fk = FORCED && (!CAP || cap_noise(cap, g)) ? fa.k : 0.0;
-    tree_select<FORCED>(t, g, lane, root, -1, -1, nullptr, fk, fa.count LZ_TSTAMP_PASS);
+    tree_select<FORCED, GUMBEL>(t, g, lane, root, -1, -1, nullptr, fk, fa.count, &ga, gum_on LZ_TSTAMP_PASS);
 #ifdef LZ_EXP_TREE_STAMPS
     LZ_TADD(g, 19, 1)
 #endif
@@ -295,12 +309,12 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
 // this kernel; LZ_TREE_SPLIT=0 takes the one-wave kernel, tests/test_gpu_tree.py compares the two).  Used for launches of
 // at most kSplitMaxGames games: at 16 384 games the SIMDs are issue-bound and twice the waves buy nothing.
 constexpr int kSplitMaxGames = 8192;
-template <bool COMPACT, bool CAP = false, bool FORCED = false>
+template <bool COMPACT, bool CAP = false, bool FORCED = false, bool GUMBEL = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_select_split_kernel(Tree t, const float* __restrict__ lp1,
                                                                           const float* __restrict__ lp2,
                                                                           const float* __restrict__ lpm,
                                                                           const float* __restrict__ values, int step,
-                                                                          CapArrays cap, ForcedArgs fa) {
+                                                                          CapArrays cap, ForcedArgs fa, GumbelArgs ga) {
     __builtin_amdgcn_s_setprio(3);
     LZ_EXPAND_SCRATCH(sc);
     __shared__ int s_flag[kWavesPerBlock / 2];
@@ -331,7 +345,8 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_split_kernel(Tree t
             return;
         }
         const double fk = FORCED && (!CAP || cap_noise(cap, g)) ? fa.k : 0.0;
-        tree_select<FORCED>(t, g, lane, root, split.wait_edge, split.nolegal_edge, flag, fk, fa.count);
+        const bool gum_on = GUMBEL && (!CAP || cap_noise(cap, g));
+        tree_select<FORCED, GUMBEL>(t, g, lane, root, split.wait_edge, split.nolegal_edge, flag, fk, fa.count, &ga, gum_on);
     }
 }
 
@@ -1118,6 +1133,82 @@ __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float
     }
 }
 
+// The Gumbel games' part of lz_tree_finish_gumbel, launched behind tree_finish_kernel<false> (which has written the row of
+// every game): pick and training target by the rule of LzTreeDesc.gumbel_*, and the final scores / vmix.  A game that is
+// not a Gumbel game, or whose root is terminal, keeps what the plain finish wrote.
+__global__ __launch_bounds__(kBlock) void tree_finish_gumbel_kernel(Tree t, GumbelArgs ga,
+                                                                    const uint8_t* __restrict__ root_noise,
+                                                                    const uint8_t* __restrict__ force_uniform,
+                                                                    const float* __restrict__ uniforms,
+                                                                    float* __restrict__ policy_dense,
+                                                                    int* __restrict__ chosen_index,
+                                                                    int4* __restrict__ chosen_code,
+                                                                    double* __restrict__ score_out,
+                                                                    double* __restrict__ vmix_out, int out_cap) {
+    const int lane = lane_id();
+    const int g = wave_game();
+    if (g >= t.B) return;
+    if (score_out != nullptr)
+        for (int k = lane; k < out_cap; k += kWave) score_out[(size_t)g * out_cap + k] = 0.0;
+    if (vmix_out != nullptr && lane == 0) vmix_out[g] = 0.0;
+    if (ga.m <= 0 || (root_noise != nullptr && root_noise[g] == 0)) return;
+    const Node* nodes = t.nodes + (size_t)g * t.node_cap;
+    const int ne = nodes[0].nedges;
+    if (t.root_terminal[g] != 0 || ne <= 0) return;
+    const State root = unpack(nodes[0].state);
+    const int e0 = nodes[0].edge_begin;
+    int n[2], act[2]; float P[2]; double q[2]; bool ok[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int k = r * kWave + lane;
+        ok[r] = k < ne;
+        const Edge e = t.edges[(size_t)(e0 + (ok[r] ? k : 0))];
+        n[r] = ok[r] ? edge_n(e.n_info) : 0;
+        P[r] = ok[r] ? e.P : 0.f;
+        act[r] = ok[r] ? (int)e.act : 0;
+        q[r] = 0.0;
+        if (n[r] > 0) {
+            const double mv = e.W / (double)n[r];
+            q[r] = ((edge_info(e.n_info) & kInfoWhite) ? -1 : 1) == root.player ? mv : -mv;
+        }
+    }
+    const GumbelLane s = gumbel_scores(ga, g, lane, n, P, q, ok);
+    if (score_out != nullptr) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int k = r * kWave + lane;
+            if (ok[r] && k < out_cap) score_out[(size_t)g * out_cap + k] = s.score[r];
+        }
+    }
+    if (vmix_out != nullptr && lane == 0) vmix_out[g] = s.vmix;
+    // training target: softmax(log P + sigma) in double, the maximum subtracted
+    double lg[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) lg[r] = (ok[r] && P[r] > 0.f) ? log((double)P[r]) + s.sigma[r] : -INFINITY;
+    const double mx = lzw::wave_max(lg[1] > lg[0] ? lg[1] : lg[0]);
+    double ex[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) ex[r] = lg[r] == -INFINITY ? 0.0 : exp(lg[r] - mx);
+    const double sum = gumbel_bfly(ex[0] + ex[1]);
+    float* prow = policy_dense + (size_t)g * 220;
+    if (sum > 0.0 && mx > -INFINITY) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) if (ok[r]) prow[act[r]] = (float)(ex[r] / sum);
+    }
+    if (force_uniform != nullptr && force_uniform[g] && uniforms != nullptr) return;      // opening random move: kept
+    // pick: most visits of THIS search, then the score, then the lowest index
+    const int lmax = (int)lzw::wave_max(fmaxf(ok[0] ? (float)s.L[0] : -16777216.f, ok[1] ? (float)s.L[1] : -16777216.f));
+    const bool cand[2] = {ok[0] && s.L[0] == lmax, ok[1] && s.L[1] == lmax};
+    const int pick = gumbel_argmax(s, cand, lane);
+    if (pick >= 0 && lane == (pick & 63)) {
+        const int a = pick >= kWave ? act[1] : act[0];
+        int kd, p, q2, ex2;
+        index_to_code(root.phase, a, kd, p, q2, ex2);
+        chosen_index[g] = a;
+        chosen_code[g] = make_int4(kd, p, q2, ex2);
+    }
+}
+
 // =================================================================================================================
 // Fused root-PUCT search (variant R, v1/python/mcts_gpu.py:1249-1457) on packed states: the host op chain
 // encode -> project -> root_pack -> noise -> batch_apply_moves -> ... with data-dependent shapes and two host syncs
@@ -1341,6 +1432,18 @@ __global__ __launch_bounds__(kBlock) void rng_gamma_kernel(uint64_t seed, const 
     if (g >= B) return;
     out[g * stride + k] = lzrng::gamma_draw(seed, game ? game[g] : g, ply ? ply[g] : 0, (uint32_t)k, alpha);
 }
+template <bool UNIFORM>       // UNIFORM: the uniform behind the variate instead of the variate (tests)
+__global__ __launch_bounds__(kBlock) void rng_gumbel_kernel(uint64_t seed, const int64_t* __restrict__ game,
+                                                            const int64_t* __restrict__ ply, int64_t B, int count,
+                                                            float* __restrict__ out, int stride) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t g = i / count;
+    const int k = (int)(i - g * count);
+    if (g >= B) return;
+    const int64_t gid = game ? game[g] : g, p = ply ? ply[g] : 0;
+    out[g * stride + k] = UNIFORM ? lzrng::gumbel_u(lzrng::draw(seed, gid, p, lzrng::kPurposeGumbel, 1u + (uint32_t)k, 0u).x)
+                                  : lzrng::gumbel_draw(seed, gid, p, (uint32_t)k);
+}
 __global__ __launch_bounds__(kBlock) void rng_uniform_kernel(uint64_t seed, const int64_t* __restrict__ game,
                                                              const int64_t* __restrict__ ply, int64_t B, int purpose,
                                                              float* __restrict__ out) {
@@ -1417,13 +1520,17 @@ int lz_tree_begin(const LzTreeDesc* d, void* stream) {
 int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (!tree_ok(d)) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: lz_tree_search only
+    if (const int rc = gumbel_check(d)) return rc;
     if (d->num_games == 0) return LZ_OK;
-    if (forced_set(d))
+    if (gumbel_set(d))
+        hipLaunchKernelGGL((tree_select_kernel<false, true>), dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream),
+                           no_share(make_tree(d)), ForcedArgs{}, make_gumbel(d));
+    else if (forced_set(d))
         hipLaunchKernelGGL(tree_select_kernel<true>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream),
-                           no_share(make_tree(d)), make_forced(d));
+                           no_share(make_tree(d)), make_forced(d), GumbelArgs{});
     else
         hipLaunchKernelGGL(tree_select_kernel<false>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream),
-                           no_share(make_tree(d)), ForcedArgs{});
+                           no_share(make_tree(d)), ForcedArgs{}, GumbelArgs{});
     return st();
 }
 
@@ -1433,12 +1540,17 @@ int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const flo
     if (!tree_ok(d) || !values) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
     if (!priors220 && (!lp1 || !lp2 || !lpmc)) return LZ_ERR_ARG;
+    if (const int rc = gumbel_check(d)) return rc;
     if (d->num_games == 0) return LZ_OK;
     const Tree t = no_share(make_tree(d));
-    if (is_root)
+    if (is_root) {
+        if (gumbel_set(d)) noise = nullptr;                        // a Gumbel search never mixes Dirichlet noise in
         hipLaunchKernelGGL(tree_expand_kernel<true>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
                            lpmc, priors220, values, noise, (int)noise_stride, epsilon, -1, CapArrays{});
-    else
+        if (gumbel_set(d))
+            hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, make_gumbel(d),
+                               (const uint8_t*)nullptr);
+    } else
         hipLaunchKernelGGL(tree_expand_kernel<false>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
                            lpmc, priors220, values, nullptr, 0, 0.f, -1, CapArrays{});
     return st();
@@ -1489,6 +1601,26 @@ int lz_tree_finish_pruned(const LzTreeDesc* d, const float* temperatures, const 
                                   uniforms, policy_dense, chosen_index, chosen_code, chosen_valid, terminal_mask,
                                   root_value, child_count, child_action, child_visits, child_prior, out_cap,
                                   child_target_visits, pruned_visits, stream);
+}
+
+int lz_tree_finish_gumbel(const LzTreeDesc* d, const float* temperatures, const float* target_temperatures,
+                          float prior_pseudocount, const uint8_t* force_uniform, int sample_moves, const float* uniforms,
+                          float* policy_dense,
+                          int32_t* chosen_index, int32_t* chosen_code, uint8_t* chosen_valid, uint8_t* terminal_mask,
+                          float* root_value, int32_t* child_count, int32_t* child_action, int32_t* child_visits,
+                          float* child_prior, int64_t out_cap, double* gumbel_score, double* gumbel_vmix, void* stream) {
+    if (!tree_ok(d)) return LZ_ERR_ARG;
+    if (const int grc = gumbel_check(d)) return grc;
+    const int rc = tree_finish_impl<false>(d, temperatures, target_temperatures, prior_pseudocount, force_uniform,
+                                           sample_moves, uniforms, policy_dense, chosen_index, chosen_code, chosen_valid,
+                                           terminal_mask, root_value, child_count, child_action, child_visits,
+                                           child_prior, out_cap, nullptr, nullptr, stream);
+    if (rc || d->num_games == 0) return rc;
+    // the Gumbel games' pick and training target over what the plain finish wrote (same stream: ordered)
+    hipLaunchKernelGGL(tree_finish_gumbel_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
+                       make_gumbel(d), d->root_noise, force_uniform, uniforms, policy_dense, chosen_index,
+                       reinterpret_cast<int4*>(chosen_code), gumbel_score, gumbel_vmix, (int)out_cap);
+    return st();
 }
 
 static long long* g_advance_ticks = nullptr;
@@ -1543,8 +1675,9 @@ int lz_tree_advance(const LzTreeDesc* d, const int32_t* played_action, const uin
 // `continue_trees`: the roots were prepared by lz_tree_advance (kept subtrees or fresh roots), so no begin.
 // CAP: the kernels of the playout cap (LzTreeDesc.sim_budget / root_noise), the same launch sequence.
 // FORCED: the select kernels of forced playouts (LzTreeDesc.forced_k), the same launch sequence.
-extern "C++" template <bool CAP, bool FORCED>
-static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const ForcedArgs& fa, const LzNetDesc* net, int64_t sims, float* lp1,
+// GUMBEL: the kernels of the Gumbel root search (LzTreeDesc.gumbel_*), the same launch sequence.
+extern "C++" template <bool CAP, bool FORCED, bool GUMBEL = false>
+static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const ForcedArgs& fa, const GumbelArgs& ga, const LzNetDesc* net, int64_t sims, float* lp1,
                               float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                               float epsilon, void* stream) {
     const int64_t B = d->num_games;
@@ -1565,22 +1698,24 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                     hipLaunchKernelGGL((tree_expand_kernel<false, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
                                        lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap);
             } else if (s == 0) {
-                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP, FORCED>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa);
+                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP, FORCED, GUMBEL>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga);
             } else {
                 (void)lz_prof_aux_begin(0, stream);
                 if (split_step(t.B))
-                    hipLaunchKernelGGL((tree_expand_select_split_kernel<true, CAP, FORCED>), dim3(gw2(t.B)), dim3(kBlock), 0,
-                                       as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, cap, fa);
+                    hipLaunchKernelGGL((tree_expand_select_split_kernel<true, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), dim3(kBlock), 0,
+                                       as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, cap, fa, ga);
                 else
-                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP, FORCED>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa);
+                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP, FORCED, GUMBEL>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga);
                 (void)lz_prof_aux_end(0, stream, B);
             }
             if (s < sims)                                           // the leaves of simulation s + 1
                 hipLaunchKernelGGL(tree_live_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t,
                                    t.live_count + (s + 1));
         }
+        if (GUMBEL && sims == 0)                                    // a search of the root step alone: its snapshot
+            hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, ga, cap.root_noise);
         return st();
     }
     for (int64_t s = 0; s <= sims; ++s) {
@@ -1594,19 +1729,21 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                 hipLaunchKernelGGL((tree_expand_kernel<false, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
                                    lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap);
         } else if (s == 0) {
-            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP, FORCED>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa);
+            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP, FORCED, GUMBEL>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga);
         } else {
             (void)lz_prof_aux_begin(0, stream);                      // no-ops unless lz_prof_enable(1) (never in a capture)
             if (split_step(t.B))
-                hipLaunchKernelGGL((tree_expand_select_split_kernel<false, CAP, FORCED>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, (int)s, cap, fa);
+                hipLaunchKernelGGL((tree_expand_select_split_kernel<false, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, (int)s, cap, fa, ga);
             else
-                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP, FORCED>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa);
+                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP, FORCED, GUMBEL>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga);
             (void)lz_prof_aux_end(0, stream, B);
         }
     }
+    if (GUMBEL && sims == 0)
+        hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, ga, cap.root_noise);
     return st();
 }
 
@@ -1614,6 +1751,7 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
                             float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                             float epsilon, bool continue_trees, void* stream) {
     if (!tree_ok(d) || !net || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
+    if (const int grc = gumbel_check(d)) return grc;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
@@ -1623,14 +1761,19 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     // function of the packed state alone.  The step-by-step entry points (external evaluators) and the two-wave split
     // step (where the descent runs beside the expansion that inserts into the index) keep the index but do not look it up.
     const Tree t = split_step(B) ? no_share(make_tree(d)) : make_tree(d);
+    if (gumbel_set(d)) {                                           // (a Gumbel search never mixes Dirichlet noise in)
+        if (cap_set(d))
+            return tree_search_launch<true, false, true>(d, t, make_cap(d), ForcedArgs{}, make_gumbel(d), net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
+        return tree_search_launch<false, false, true>(d, t, CapArrays{}, ForcedArgs{}, make_gumbel(d), net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
+    }
     if (forced_set(d)) {
         if (cap_set(d))
-            return tree_search_launch<true, true>(d, t, make_cap(d), make_forced(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-        return tree_search_launch<false, true>(d, t, CapArrays{}, make_forced(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+            return tree_search_launch<true, true>(d, t, make_cap(d), make_forced(d), GumbelArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_launch<false, true>(d, t, CapArrays{}, make_forced(d), GumbelArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
     }
     if (cap_set(d))
-        return tree_search_launch<true, false>(d, t, make_cap(d), ForcedArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    return tree_search_launch<false, false>(d, t, CapArrays{}, ForcedArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_launch<true, false>(d, t, make_cap(d), ForcedArgs{}, GumbelArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    return tree_search_launch<false, false>(d, t, CapArrays{}, ForcedArgs{}, GumbelArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
 }
 
 // lz_net.hip (internal): the checks of lz_net_forward_packed_multi_f16 on its networks
@@ -1645,6 +1788,7 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
     if (!tree_ok(d) || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: one network per search only
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
+    if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
     int rc = lz_net_multi_validate(nets, num_nets);
     if (rc) return rc;
     const int64_t B = d->num_games, G = d->seg_games;
@@ -1673,14 +1817,14 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
                                    lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, CapArrays{});
         } else if (s == 0) {
             hipLaunchKernelGGL((tree_expand_select_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{});
+                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{});
         } else {
             if (split_step(t.B))
                 hipLaunchKernelGGL((tree_expand_select_split_kernel<true>), dim3(gw2(t.B)), dim3(kBlock), 0,
-                                   as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, CapArrays{}, ForcedArgs{});
+                                   as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{});
             else
                 hipLaunchKernelGGL((tree_expand_select_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{});
+                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{});
         }
         if (s < sims) scan(s + 1);                                  // the leaves of simulation s + 1
     }
@@ -1794,6 +1938,26 @@ int lz_rng_gamma(uint64_t seed, const int64_t* game_id, const int64_t* ply, int6
     return st();
 }
 
+int lz_rng_gumbel(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t B, int64_t count, float* out,
+                  int64_t stride, void* stream) {
+    if (B < 0 || count < 0 || count > 1023 || stride < count) return LZ_ERR_ARG;
+    if (B == 0 || count == 0) return LZ_OK;
+    if (!out) return LZ_ERR_ARG;
+    hipLaunchKernelGGL(rng_gumbel_kernel<false>, dim3(gt(B * count)), dim3(kBlock), 0, as_stream(stream), seed, game_id,
+                       ply, B, (int)count, out, (int)stride);
+    return st();
+}
+
+int lz_rng_gumbel_uniform(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t B, int64_t count, float* out,
+                          int64_t stride, void* stream) {
+    if (B < 0 || count < 0 || count > 1023 || stride < count) return LZ_ERR_ARG;
+    if (B == 0 || count == 0) return LZ_OK;
+    if (!out) return LZ_ERR_ARG;
+    hipLaunchKernelGGL(rng_gumbel_kernel<true>, dim3(gt(B * count)), dim3(kBlock), 0, as_stream(stream), seed, game_id,
+                       ply, B, (int)count, out, (int)stride);
+    return st();
+}
+
 int lz_rng_uniform(uint64_t seed, const int64_t* game_id, const int64_t* ply, int64_t B, int purpose, float* out,
                    void* stream) {
     if (B < 0 || purpose < 0 || purpose > 3) return LZ_ERR_ARG;
@@ -1808,6 +1972,7 @@ int lz_tree_wave_select(const LzTreeDesc* d, const LzTreeWaveDesc* w, int64_t si
     if (!tree_ok(d) || !wave_ok(w) || sims < 0) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
+    if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
     if (d->num_games == 0) return LZ_OK;
     const Tree t = make_tree(d);
     const WaveArrays a = make_wave(w);
@@ -1835,7 +2000,7 @@ int lz_tree_search_waves(const LzTreeDesc* d, const LzTreeWaveDesc* w, const LzN
                          float* lp1, float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                          float epsilon, int continue_trees, int skip_roots, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || !net || sims < 0 || waves < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
-    if (forced_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (forced_set(d) || gumbel_set(d)) return LZ_ERR_UNSUPPORTED;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = LZ_OK;

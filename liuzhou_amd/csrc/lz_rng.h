@@ -89,4 +89,17 @@ LZ_RNG_HD float uniform_draw(uint64_t seed, int64_t game, int64_t ply, uint32_t 
     return u01(draw(seed, game, ply, purpose, 0u, 0u).x);
 }
 
+// Standard Gumbel draw for child rank k of (seed, game, ply): the root variates of the Gumbel search (Danihelka et al.,
+// ICLR 2022).  Purpose 3 is the playout cap's, which uses index 0 only, and the two purpose bits are all taken: the index
+// field separates the streams (index 1 + k, k < 1023).  23 random bits -> u strictly inside (0, 1), exact in fp32, so both
+// logarithms are finite.  Both logarithms run in double and the result is rounded to fp32 once: where -log u is close to 1
+// the variate is close to 0, and one fp32 rounding of the inner logarithm (6e-8) would be an error of that absolute size
+// in g whatever g is -- implementations of logf that differ in the last bit then disagree by parts in a thousand there.
+// The kernel draws 72 variates per game and ply, so the double rate does not matter.
+constexpr uint32_t kPurposeGumbel = 3;
+LZ_RNG_HD float gumbel_u(uint32_t x) { return ((float)(x >> 9) + 0.5f) * (1.0f / 8388608.0f); }
+LZ_RNG_HD float gumbel_draw(uint64_t seed, int64_t game, int64_t ply, uint32_t k) {
+    return (float)(-log(-log((double)gumbel_u(draw(seed, game, ply, kPurposeGumbel, 1u + k, 0u).x))));
+}
+
 }  // namespace lzrng

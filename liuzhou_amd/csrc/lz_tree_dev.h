@@ -99,6 +99,15 @@ struct CapArrays { const int* sim_budget; const uint8_t* root_noise; };
 // Optional forced playouts (LzTreeDesc.forced_k / forced_count): handed over the same way, read only by the FORCED
 // instantiations of the select / expand + select kernels.
 struct ForcedArgs { double k; int* count; };
+// Optional Gumbel root search (LzTreeDesc.gumbel_*): handed over the same way, read only by the GUMBEL instantiations of
+// the select / expand + select kernels, by the root-step snapshot and by the Gumbel finish.  FORCED and GUMBEL exclude
+// each other (two rules for the same level).
+struct GumbelArgs {
+    double c_visit, c_scale;
+    const float* g; const int* table;
+    float* gl; int* base; int* root_base; float* root_value; int* count;
+    int m, sims, stride;
+};
 
 // Edge / node records are read with plain (L1 + L2 cached, normal retention) 16-byte loads.  This is safe next to the
 // device-scope atomics of the backup because a launch never loads an edge line before its own atomics on it have
@@ -312,13 +321,98 @@ __device__ __forceinline__ void split_wait(volatile int* flag, int phase) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// ---- Gumbel root search: the arithmetic that selection and finish share (formulas: LzTreeDesc in liuzhou_hip.h) ----------
+// Sum over the wave in the documented order: offsets 32, 16, 8, 4, 2, 1, x[l] = x[l] + x[l ^ offset]; both partners of a
+// pair add the same two numbers, so every lane ends with the same bits.  (ds_bpermute round trips: this runs once per
+// simulation, on the root level only.)
+__device__ __forceinline__ double gumbel_bfly(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// Per lane, for its children k = lane and lane + 64 (ok[r]: the child exists; n, P, q its statistics, q only read for
+// n > 0): score, sigma, L = N - N0 and the root's vmix.  Everything in double on the stored bits; products and sums stay
+// separate roundings (the libraries are built with -ffp-contract=off, which the bit-for-bit checks rely on).
+struct GumbelLane { double score[2], sigma[2], vmix; int L[2]; };
+__device__ __forceinline__ GumbelLane gumbel_scores(const GumbelArgs& ga, int g, int lane, const int (&n)[2],
+                                                    const float (&P)[2], const double (&q)[2], const bool (&ok)[2]) {
+    const bool vis0 = ok[0] && n[0] > 0, vis1 = ok[1] && n[1] > 0;
+    const double p0 = vis0 ? (double)P[0] : 0.0, p1 = vis1 ? (double)P[1] : 0.0;
+    const double pq0 = vis0 ? (double)P[0] * q[0] : 0.0, pq1 = vis1 ? (double)P[1] * q[1] : 0.0;
+    const double Pv = gumbel_bfly(p0 + p1), Pq = gumbel_bfly(pq0 + pq1);
+    const int T = lzw::lane_bcast(lzw::wave_incl_scan((ok[0] ? n[0] : 0) + (ok[1] ? n[1] : 0)), kWave - 1);
+    const int nl = ok[1] && n[1] > n[0] ? n[1] : (ok[0] ? n[0] : 0);
+    const double nmax = (double)lzw::wave_max((float)nl);         // visit counts are below 2^24: exact in fp32
+    const double v0 = (double)ga.root_value[g];
+    const double tm = (double)T;
+    GumbelLane o;
+    o.vmix = (T == 0 || Pv <= 0.0) ? v0 : (v0 + tm * (Pq / Pv)) / (1.0 + tm);
+    const double scale = (ga.c_visit + nmax) * ga.c_scale;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int k = r * kWave + lane;
+        const bool in = ok[r] && k < ga.stride;
+        const float gl = in ? ga.gl[(size_t)g * ga.stride + k] : -INFINITY;
+        const int n0 = in ? ga.base[(size_t)g * ga.stride + k] : 0;
+        const double cq = (ok[r] && n[r] > 0) ? q[r] : o.vmix;
+        o.sigma[r] = scale * (0.5 * cq);
+        o.score[r] = (double)gl + o.sigma[r];
+        o.L[r] = (ok[r] ? n[r] : 0) - n0;
+    }
+    return o;
+}
+// The candidate with the largest score, lowest edge index among equals (-1: none, or every score NaN)
+__device__ __forceinline__ int gumbel_argmax(const GumbelLane& s, const bool (&cand)[2], int lane) {
+    double best = -INFINITY;
+    int best_k = -1;
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+        if (cand[r] && (best_k < 0 || s.score[r] > best)) { best = s.score[r]; best_k = r * kWave + lane; }
+    const double mx = lzw::wave_max(best_k >= 0 ? best : -INFINITY);
+    const uint64_t lo = __ballot(best_k >= 0 && best_k < kWave && best == mx);
+    if (lo) return __ffsll((unsigned long long)lo) - 1;
+    const uint64_t hi = __ballot(best_k >= kWave && best == mx);
+    return hi ? kWave + __ffsll((unsigned long long)hi) - 1 : -1;
+}
+// The root step's snapshot for a Gumbel game (after the IS_ROOT expansion: fresh and kept roots alike): gl = g + log P,
+// N0 = N, the root's visit count and its value v0.  leaf_kind still says which kind of root the step saw.
+__device__ __forceinline__ void gumbel_root_step(const Tree& t, int g, int lane, const GumbelArgs& ga) {
+    if (t.root_terminal[g]) return;
+    const int kind = t.leaf_kind[g];
+    if (kind != kLeafExpand && kind != kLeafReusedRoot) return;
+    const Node* root = t.nodes + (size_t)g * t.node_cap;
+    const int ne = root->nedges, e0 = root->edge_begin;
+    if (ne <= 0) return;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int k = r * kWave + lane;
+        if (k < ne && k < ga.stride) {
+            const Edge e = load_edge(&t.edges[(size_t)e0 + k]);
+            ga.gl[(size_t)g * ga.stride + k] = ga.g[(size_t)g * ga.stride + k] + logf(e.P);
+            ga.base[(size_t)g * ga.stride + k] = edge_n(e.n_info);
+        }
+    }
+    if (lane == 0) {
+        const int rv = t.root_visits[g];
+        ga.root_base[g] = rv;
+        ga.root_value[g] = kind == kLeafReusedRoot ? (rv > 0 ? (float)(t.root_W[g] / (double)rv) : 0.f)
+                                                   : t.root_init_value[g];
+        if (ga.count != nullptr) ga.count[g] += 1;                // this game's wave is the only writer
+    }
+}
+
 // FORCED (forced playouts, root level only): with forced_k > 0 a root child that has visits but fewer than
 // sqrt(forced_k * P * root visits) is "due"; the descent takes the due child with the lowest edge index and skips the score
 // arithmetic of that level.  The test is on squares, all in double: N * N < (k * P) * n.
-template <bool FORCED = false>
+// GUMBEL (Gumbel root search, root level only; `gum_on`: this game's search is one, `gum` its arguments): Sequential
+// Halving over the children whose visits of this search equal the schedule's entry, by g + log P + sigma(completed Q);
+// no PUCT arithmetic on that level.  One pass over the mine[] registers: two double wave sums, an integer sum and maximum, one argmax, plus
+// three coalesced reads (gumbel_gl, gumbel_base, the table entry).
+template <bool FORCED = false, bool GUMBEL = false>
 __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, const RootInfo& root, int wait_edge = -1,
                                             int nolegal_edge = -1, volatile int* flag = nullptr, double forced_k = 0.0,
-                                            int* forced_count = nullptr LZ_TSTAMP_ARG) {
+                                            int* forced_count = nullptr, const GumbelArgs* gum = nullptr,
+                                            bool gum_on = false LZ_TSTAMP_ARG) {
     if (t.root_terminal[g]) { if (lane == 0) t.leaf_kind[g] = kLeafInactive; return; }
     const Node* nodes = t.nodes + (size_t)g * t.node_cap;
     const Edge* edges = t.edges;                               // pool indices
@@ -379,7 +473,30 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
         // as before; so does a level on which some |W / n| exceeds 1 (an external evaluator with another value scale: the
         // bound above assumes values in [-1, 1]).  The double arithmetic of a level (sqrt, two divisions, a 64-bit wave
         // maximum) was the largest single item of the step (profiles/r05_pmc_sq_tree.md: 1.76 k of ~2.6 k cycles per level).
-        if ((!FORCED || chosen < 0) && t.fast_select) {
+        if (GUMBEL && depth == 0 && gum_on) {
+            int n[2]; float P[2]; double q[2]; bool ok[2];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                ok[r] = (r == 0 || ne > kWave) && r * kWave + lane < ne;
+                n[r] = ok[r] ? edge_n(mine[r].n_info) : 0;
+                P[r] = ok[r] ? mine[r].P : 0.f;
+                q[r] = 0.0;
+                if (n[r] > 0) {
+                    const double mv = mine[r].W / (double)n[r];
+                    const int child_player = (edge_info(mine[r].n_info) & kInfoWhite) ? -1 : 1;
+                    q[r] = child_player == node_player ? mv : -mv;
+                }
+            }
+            const GumbelLane s = gumbel_scores(*gum, g, lane, n, P, q, ok);
+            const int started = parent_n - gum->root_base[g];     // simulations this search has started before this one
+            const int col = started < 0 ? 0 : (started < gum->sims ? started : gum->sims - 1);
+            const int cv = gum->table[(size_t)(gum->m < ne ? gum->m : ne) * gum->sims + col];
+            bool cand[2] = {ok[0] && s.L[0] == cv, ok[1] && s.L[1] == cv};
+            if (__ballot(cand[0] || cand[1]) == 0ull) { cand[0] = ok[0]; cand[1] = ok[1]; }   // (a refused expansion can)
+            chosen = gumbel_argmax(s, cand, lane);
+            if (chosen < 0) break;                                 // every score NaN
+        }
+        if ((!FORCED || chosen < 0) && (!GUMBEL || chosen < 0) && t.fast_select) {
             const float sqf = sqrtf((float)(parent_n > 1 ? parent_n : 1));
             const float cf = (float)t.c_puct;
             float fs[2] = {-INFINITY, -INFINITY};
@@ -896,6 +1013,22 @@ inline bool cap_set(const LzTreeDesc* d) { return d->sim_budget != nullptr || d-
 inline CapArrays make_cap(const LzTreeDesc* d) { return CapArrays{d->sim_budget, d->root_noise}; }
 inline bool forced_set(const LzTreeDesc* d) { return d->forced_k > 0.0; }
 inline ForcedArgs make_forced(const LzTreeDesc* d) { return ForcedArgs{d->forced_k, d->forced_count}; }
+inline bool gumbel_set(const LzTreeDesc* d) { return d->gumbel_m != 0; }
+// LZ_OK, LZ_ERR_ARG (fields out of range / missing arrays) or LZ_ERR_UNSUPPORTED (with forced playouts)
+inline int gumbel_check(const LzTreeDesc* d) {
+    if (!gumbel_set(d)) return LZ_OK;
+    if (d->gumbel_m < 0 || d->gumbel_m > kMaxChildren || d->gumbel_sims < 1 || d->gumbel_stride < kMaxChildren ||
+        d->gumbel_stride > (1 << 20) || !(d->gumbel_c_visit >= 0.0) || !(d->gumbel_c_scale >= 0.0) ||
+        !isfinite(d->gumbel_c_visit) || !isfinite(d->gumbel_c_scale) || !d->gumbel_g || !d->gumbel_table ||
+        !d->gumbel_gl || !d->gumbel_base || !d->gumbel_root_base || !d->gumbel_root_value)
+        return LZ_ERR_ARG;
+    return forced_set(d) ? LZ_ERR_UNSUPPORTED : LZ_OK;
+}
+inline GumbelArgs make_gumbel(const LzTreeDesc* d) {
+    return GumbelArgs{d->gumbel_c_visit, d->gumbel_c_scale, d->gumbel_g, d->gumbel_table, d->gumbel_gl, d->gumbel_base,
+                      d->gumbel_root_base, d->gumbel_root_value, d->gumbel_count, d->gumbel_m, d->gumbel_sims,
+                      (int)d->gumbel_stride};
+}
 bool tree_ok(const LzTreeDesc* d) {
     return d && d->num_games >= 0 && d->node_cap >= 2 && d->path_cap >= 3 &&
            d->edge_chunk >= 128 && (d->edge_chunk & (d->edge_chunk - 1)) == 0 && d->chunk_cap >= 1 &&

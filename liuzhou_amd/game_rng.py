@@ -59,6 +59,15 @@ class GameRng:
                                          C.c_float(float(alpha)), L.i64(count), L.ptr(out), L.i64(int(out.stride(0))),
                                          L.stream_ptr(self.device)), "rng_gamma")
 
+    def gumbel_into(self, out: torch.Tensor, count: int, uniforms: bool = False) -> None:
+        """out[g, k] = standard Gumbel draw for child rank k < count of slot g's (game, ply): the root variates of the
+        Gumbel search (purpose 3 with index 1 + k; the playout cap's uniform is index 0 of that purpose).  `uniforms`: the
+        uniforms behind the variates instead (tests)."""
+        fn = L.lib().lz_rng_gumbel_uniform if uniforms else L.lib().lz_rng_gumbel
+        with torch.cuda.device(self.device):
+            L.check(fn(C.c_uint64(self.seed), L.ptr(self.game), L.ptr(self.ply), L.i64(self.B),
+                     L.i64(count), L.ptr(out), L.i64(int(out.stride(0))), L.stream_ptr(self.device)), "rng_gumbel")
+
     def uniform_into(self, out: torch.Tensor, purpose: int = PURPOSE_PICK) -> None:
         with torch.cuda.device(self.device):
             L.check(L.lib().lz_rng_uniform(C.c_uint64(self.seed), L.ptr(self.game), L.ptr(self.ply), L.i64(self.B),

@@ -80,6 +80,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     bps_num = bps_den = 0
     cap_meta: Optional[Dict[str, Any]] = None
     forced_meta: Optional[Dict[str, Any]] = None
+    gumbel_meta: Optional[Dict[str, Any]] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -100,6 +101,10 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         wforced = (wm.get("metadata") or {}).get("forced_playouts")
         if isinstance(wforced, dict) and forced_meta is None:
             forced_meta = {"k": float(wforced.get("k", 0.0))}
+        wgumbel = (wm.get("metadata") or {}).get("gumbel")
+        if isinstance(wgumbel, dict) and gumbel_meta is None:
+            gumbel_meta = {"considered": int(wgumbel.get("considered", 0)), "c_visit": float(wgumbel.get("c_visit", 50.0)),
+                           "c_scale": float(wgumbel.get("c_scale", 1.0))}
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -120,6 +125,8 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     if forced_meta is not None:         # forced playouts: k, forced descents and pruned visits over all workers
         meta["forced_playouts"] = {**forced_meta, **{k: int(merged.mcts_counters.get(k, 0))
                                                      for k in ("forced_playouts", "pruned_visits")}}
+    if gumbel_meta is not None:         # Gumbel root search: its settings and the searches that ran the rule, all workers
+        meta["gumbel"] = {**gumbel_meta, "gumbel_searches": int(merged.mcts_counters.get("gumbel_searches", 0))}
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -142,15 +149,27 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         policy_target_prior_pseudocount: float = 0.0, sample_moves: bool = True,
                         eval_symmetry: Any = "none", worker_fn: Optional[Callable[..., Dict[str, Any]]] = None,
                         in_process: bool = False, playout_cap_fast_simulations: int = 0,
-                        playout_cap_full_prob: float = 1.0, forced_playouts_k: float = 0.0
+                        playout_cap_full_prob: float = 1.0, forced_playouts_k: float = 0.0,
+                        gumbel_considered: int = 0, gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0
                         ) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
     "random" or a fixed id 0..7) reaches the workers only when it is not "none"; so do `playout_cap_fast_simulations` /
     `playout_cap_full_prob` (tree backend, playout cap randomization) only when the cap is on, and `forced_playouts_k`
-    (tree backend, forced playouts and policy target pruning) only when it is > 0."""
-    from .tree_engine import forced_playouts_on, playout_cap_on
+    (tree backend, forced playouts and policy target pruning) only when it is > 0, and `gumbel_considered` /
+    `gumbel_c_visit` / `gumbel_c_scale` (tree backend, Gumbel root search with Sequential Halving; a Gumbel search never
+    mixes Dirichlet noise into the root priors, whatever `add_dirichlet_noise` says) only when gumbel_considered > 0."""
+    from .gumbel import gumbel_on
+    from .tree_engine import forced_playouts_on, gumbel_refusal, playout_cap_on
+    gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
+    if gumbel:
+        if str(search_backend).strip().lower() not in ("portable", "tree"):
+            raise ValueError(f"the Gumbel root search needs the tree backend, not the root-PUCT search ({search_backend!r})")
+        why = gumbel_refusal(forced_playouts_k=forced_playouts_k, policy_target_temperature=policy_target_temperature,
+                             policy_target_prior_pseudocount=policy_target_prior_pseudocount)
+        if why is not None:
+            raise ValueError(f"the Gumbel root search is not supported with {why}")
     forced = forced_playouts_on(forced_playouts_k)
     if forced and str(search_backend).strip().lower() not in ("portable", "tree"):
         raise ValueError(f"forced playouts need the tree backend, not the root-PUCT search ({search_backend!r})")
@@ -193,7 +212,9 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             **({} if eval_symmetry == "none" else {"eval_symmetry": eval_symmetry}),
             **({"playout_cap_fast_simulations": int(playout_cap_fast_simulations),
                 "playout_cap_full_prob": float(playout_cap_full_prob)} if cap else {}),
-            **({"forced_playouts_k": float(forced_playouts_k)} if forced else {}))
+            **({"forced_playouts_k": float(forced_playouts_k)} if forced else {}),
+            **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
+                "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}))
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

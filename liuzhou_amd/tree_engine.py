@@ -25,6 +25,7 @@ from contextlib import contextmanager
 from . import _lib as L
 from . import v0_core
 from .game_rng import GameRng, PURPOSE_PICK, PURPOSE_PLAYOUT_CAP
+from .gumbel import considered_table, gumbel_on
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput, TOTAL_ACTION_DIM, states_to_model_input, \
     encode_actions_fast
 from .net_hip import DescArray, FusedNet, LzNetDesc, MAX_MULTI_NETS, multi_compatible
@@ -53,7 +54,11 @@ class LzTreeDesc(C.Structure):
                [("sym_seed", C.c_uint64), ("sym_mode", C.c_int32), ("sym_fixed", C.c_int32)] + \
                [("seg_games", C.c_int64), ("seg_off", C.c_void_p)] + \
                [(n, C.c_void_p) for n in ("sim_budget", "root_noise")] + \
-               [("forced_k", C.c_double), ("forced_count", C.c_void_p)]
+               [("forced_k", C.c_double), ("forced_count", C.c_void_p)] + \
+               [("gumbel_m", C.c_int32), ("gumbel_sims", C.c_int32), ("gumbel_c_visit", C.c_double),
+                ("gumbel_c_scale", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("gumbel_g", "gumbel_table", "gumbel_gl", "gumbel_base", "gumbel_root_base",
+                                          "gumbel_root_value", "gumbel_count")] + [("gumbel_stride", C.c_int64)]
 
 
 def playout_cap_on(fast_simulations: int, full_prob: float, sims: int) -> bool:
@@ -173,6 +178,22 @@ def samples_per_launch_pass(net) -> int:
     ch, flags = int(net.desc.channels), int(net.desc.flags)
     groups = int(net.desc.max_blocks) if int(net.desc.max_blocks) > 0 else (512 if (ch == 64 and flags & 1) else 256)
     return groups * (16 if (ch == 64 and not flags & 1) else 8)
+
+
+def gumbel_refusal(*, batch_k=1, several_networks=False, fused=True, forced_playouts_k=0.0,
+                   policy_target_temperature=None, policy_target_prior_pseudocount=0.0) -> Optional[str]:
+    """Why a configuration cannot run the Gumbel root search (None: it can).  What the cap and the forced playouts refuse,
+    plus the forced playouts themselves (two rules for the same root level) and the visit-count target options (the
+    target is not made of visits any more)."""
+    return ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
+            "several networks in one search" if several_networks else
+            "an external evaluator (split-phase path)" if not fused else
+            "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else
+            "forced playouts (two rules for the same root level)" if float(forced_playouts_k) > 0.0 else
+            "policy_target_temperature (the training target is not made of visit counts)"
+            if policy_target_temperature is not None else
+            "policy_target_prior_pseudocount > 0 (the training target is not made of visit counts)"
+            if float(policy_target_prior_pseudocount) > 0.0 else None)
 
 
 def forced_playouts_on(k) -> bool:
@@ -300,6 +321,9 @@ class TreeEngine:
         self.forced_count = z((B,), torch.int32)        # descents that took a due root child, summed over the searches
         self.child_target_visits = z((B, OUT_CAP), torch.int32)   # finish() with forced_k > 0: the pruned visits N' of the target
         self.pruned_visits = z((B,), torch.int32)       # finish() with forced_k > 0: sum(N - N') of the last search
+        # Gumbel root search (set_gumbel; LzTreeDesc.gumbel_*): the buffers exist only once it is switched on
+        self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale = 0, 50.0, 1.0
+        self.gumbel: Dict[str, torch.Tensor] = {}
         self.segment_games = None if segment_games is None else int(segment_games)
         self.num_segments = 1
         if self.segment_games is not None:
@@ -393,6 +417,8 @@ class TreeEngine:
         (`child_target_visits`, `pruned_visits`; `forced_count` sums the forced descents).  Must be set before a search is
         captured into a graph."""
         on = forced_playouts_on(k)
+        if on and self.gumbel_m > 0:
+            raise ValueError("forced playouts and the Gumbel root search are two rules for the same root level")
         if on and self.batch_k > 1:
             raise ValueError("forced playouts are not supported by the legacy waves (batch_k > 1)")
         if on and self.segment_games is not None:
@@ -402,6 +428,44 @@ class TreeEngine:
         self.desc.forced_count = self.forced_count.data_ptr() if on else None
         if on:
             self.persistent = False       # the persistent kernel refuses the descriptor: the launch-pair search
+
+    def set_gumbel(self, considered: int, c_visit: float = 50.0, c_scale: float = 1.0,
+                   sims: Optional[int] = None) -> None:
+        """Gumbel root search with Sequential Halving (LzTreeDesc.gumbel_*; considered = 0: off).  In the games whose
+        root-noise switch is on, select() / search() pick the root child by the Sequential Halving schedule of
+        `gumbel.considered_table(considered, sims)` (`sims`: the simulations of a search, default max_sims) and
+        g + log P + sigma(completed Q); the root step records `gumbel["gl"]`, `["base"]`, `["root_base"]`, `["root_value"]`,
+        and finish() picks the move and forms the training target by the same rule (`gumbel["score"]`, `["vmix"]`).  Such a
+        search never mixes Dirichlet noise into its root priors.  The variates are read from `gumbel["g"]` (float32[B,
+        OUT_CAP]) at every launch: refresh them in place (GameRng.gumbel_into).  `gumbel["count"]` sums the searches whose
+        root step ran the rule.  Must be set before a search is captured into a graph."""
+        on = gumbel_on(considered, c_visit, c_scale)
+        if on and self.batch_k > 1:
+            raise ValueError("the Gumbel root search is not supported by the legacy waves (batch_k > 1)")
+        if on and self.segment_games is not None:
+            raise ValueError("the Gumbel root search is not supported with several networks in one search")
+        if on and self.forced_k > 0.0:
+            raise ValueError("the Gumbel root search and forced playouts are two rules for the same root level")
+        d = self.desc
+        self.gumbel_m = int(considered)
+        self.gumbel_c_visit, self.gumbel_c_scale = float(c_visit), float(c_scale)
+        d.gumbel_m = self.gumbel_m
+        if not on:
+            return
+        n = max(1, self.max_sims if sims is None else int(sims))
+        B, dev = self.B, self.device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        if not self.gumbel:
+            self.gumbel = {"g": z((B, OUT_CAP), torch.float32), "gl": z((B, OUT_CAP), torch.float32),
+                           "base": z((B, OUT_CAP), torch.int32), "root_base": z((B,), torch.int32),
+                           "root_value": z((B,), torch.float32), "count": z((B,), torch.int32),
+                           "score": z((B, OUT_CAP), torch.float64), "vmix": z((B,), torch.float64)}
+        self.gumbel["table"] = torch.from_numpy(considered_table(self.gumbel_m, n)).to(dev).contiguous()
+        d.gumbel_sims, d.gumbel_stride = n, OUT_CAP
+        d.gumbel_c_visit, d.gumbel_c_scale = self.gumbel_c_visit, self.gumbel_c_scale
+        for name in ("g", "table", "gl", "base", "root_base", "root_value", "count"):
+            setattr(d, "gumbel_" + name, self.gumbel[name].data_ptr())
+        self.persistent = False           # the persistent kernel refuses the descriptor: the launch-pair search
 
     _NODE_DT = [("w0", "<u8"), ("w1", "<u8"), ("w2", "<u8"), ("w3", "<u8"), ("edge_begin", "<i4"), ("nedges", "<i4"),
                 ("parent", "<i4"), ("old_begin", "<i4")]
@@ -531,6 +595,16 @@ class TreeEngine:
         sample = uniforms is not None if sample_moves is None else bool(sample_moves)
         if force_uniform is not None and force_uniform.dtype != torch.uint8:
             force_uniform = force_uniform.to(torch.uint8)
+        if self.gumbel_m > 0:               # Gumbel root search: the plain finish, then pick and target of the Gumbel games
+            with torch.cuda.device(self.device):
+                L.check(L.lib().lz_tree_finish_gumbel(
+                    C.byref(self.desc), L.ptr(temperatures), L.ptr(target_temperatures), C.c_float(float(prior_pseudocount)),
+                    L.ptr(force_uniform), C.c_int(int(sample)), L.ptr(uniforms), L.ptr(self.policy_dense),
+                    L.ptr(self.chosen_index), L.ptr(self.chosen_code), L.ptr(self.chosen_valid), L.ptr(self.terminal_mask),
+                    L.ptr(self.root_value), L.ptr(self.child_count), L.ptr(self.child_action), L.ptr(self.child_visits),
+                    L.ptr(self.child_prior), L.i64(OUT_CAP), L.ptr(self.gumbel["score"]), L.ptr(self.gumbel["vmix"]),
+                    self._stream()), "tree_finish_gumbel")
+            return
         if (self.forced_k > 0.0) if pruned is None else bool(pruned):   # policy target pruning: the same outputs + N' / the cut
             with torch.cuda.device(self.device):
                 L.check(L.lib().lz_tree_finish_pruned(
@@ -693,7 +767,8 @@ class PortableTreeMCTS:
                  game_offset: int = 0, game_stride: Optional[int] = None, trace: bool = False,
                  collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none",
                  segment_games: Optional[int] = None, multi_launch: bool = True, fast_simulations: int = 0,
-                 full_prob: float = 1.0, forced_playouts_k: float = 0.0) -> None:
+                 full_prob: float = 1.0, forced_playouts_k: float = 0.0, gumbel_considered: int = 0,
+                 gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0) -> None:
         """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
         searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
         FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
@@ -726,9 +801,30 @@ class PortableTreeMCTS:
         whose root-noise switch is on (every search without the cap, the full ones with it): a root child with N > 0 and
         N^2 < k P n is visited before PUCT is asked, and the training target (policy_dense) is formed from the pruned
         visits; the move pick and the kept subtree use the raw visits.  `forced_counts` (int64[2]): forced descents and
-        pruned visits so far.  Refused where the cap is refused (ValueError)."""
+        pruned visits so far.  Refused where the cap is refused (ValueError).
+        `gumbel_considered` m (0 = off; the paper uses 16), `gumbel_c_visit`, `gumbel_c_scale`: Gumbel root search with
+        Sequential Halving (Danihelka et al., ICLR 2022; gumbel.py) in the searches whose root-noise
+        switch is on (every search without the cap, the full ones with it).  The root samples m children without
+        replacement by g + log P (Gumbel-top-k), spends the simulations on them by Sequential Halving with
+        g + log P + sigma(completed Q), plays the winner and trains on softmax(log P + sigma(completed Q)); below the
+        root nothing changes.  A Gumbel search never mixes Dirichlet noise into the root priors, whatever
+        `add_dirichlet_noise` says: the Gumbel variates are its exploration; temperatures, `sample_moves` and the pick
+        uniform do not apply to it either (opening random moves keep precedence).  The variates come from the per-game
+        RNG (GameRng.gumbel_into); parity runs inject their own through `injected_gumbel` ([B, <= OUT_CAP]).
+        `gumbel_searches` counts the searches that ran the rule.  Refused where the cap is refused, and with
+        forced playouts, `policy_target_temperature` and `policy_target_prior_pseudocount` > 0 (ValueError)."""
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
+        self.gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
+        self.gumbel_considered = int(gumbel_considered)
+        self.gumbel_c_visit, self.gumbel_c_scale = float(gumbel_c_visit), float(gumbel_c_scale)
+        if self.gumbel:
+            why = gumbel_refusal(batch_k=batch_k, several_networks=self.multi or len(self.nets) != 1,
+                                 fused=isinstance(self.nets[0], FusedNet), forced_playouts_k=forced_playouts_k,
+                                 policy_target_temperature=policy_target_temperature,
+                                 policy_target_prior_pseudocount=policy_target_prior_pseudocount)
+            if why is not None:
+                raise ValueError(f"the Gumbel root search is not supported with {why}")
         self.forced = forced_playouts_on(forced_playouts_k)
         self.forced_playouts_k = float(forced_playouts_k)
         if self.forced:
@@ -787,6 +883,9 @@ class PortableTreeMCTS:
         if self.forced:
             self.engine.set_forced_playouts(self.forced_playouts_k)
         self._pruned_total = torch.zeros((1,), dtype=torch.int64, device=self.engine.device)   # sum of pruned_visits
+        self.injected_gumbel: Optional[torch.Tensor] = None      # parity runs: [B, <= OUT_CAP] instead of the RNG's draws
+        if self.gumbel:
+            self.engine.set_gumbel(self.gumbel_considered, self.gumbel_c_visit, self.gumbel_c_scale, int(num_simulations))
         if not self.fused:
             if self.batch_k > 1:
                 raise ValueError("an external evaluator supports batch_k = 1 only")
@@ -845,6 +944,13 @@ class PortableTreeMCTS:
     def forced_counts(self) -> torch.Tensor:
         """int64[2] on the device: forced descents and pruned visits of the searches so far (zeros when off)."""
         return torch.cat((self.engine.forced_count.sum(dtype=torch.int64).view(1), self._pruned_total))
+
+    @property
+    def gumbel_searches(self) -> torch.Tensor:
+        """int64[1] on the device: searches of live games that ran the Gumbel rule so far (zero when off)."""
+        if not self.gumbel:
+            return torch.zeros((1,), dtype=torch.int64, device=self.engine.device)
+        return self.engine.gumbel["count"].sum(dtype=torch.int64).view(1)
 
     def _draw_playout_cap(self, active: Optional[torch.Tensor]) -> None:
         """Full / fast mask of this move on the device (no host synchronisation): u = uniform(seed, game, ply, purpose 3),
@@ -995,11 +1101,14 @@ class PortableTreeMCTS:
                 #  continued search, which cannot be preceded by a warm-up of its own)
                 counted = (e.live_total.clone(), e.eval_count.clone(), e.share_count.clone())   # warm-ups are not searches
                 forced_counted = e.forced_count.clone() if self.forced else None
+                gumbel_counted = e.gumbel["count"].clone() if self.gumbel else None
                 for form in ((lists, not lists) if (e.compact_evals and not self.fused_multi) else (lists,)):
                     self._run_search(min(self.sims, 2), noise, False, form)
                 e.live_total.copy_(counted[0]); e.eval_count.copy_(counted[1]); e.share_count.copy_(counted[2])
                 if forced_counted is not None:
                     e.forced_count.copy_(forced_counted)
+                if gumbel_counted is not None:
+                    e.gumbel["count"].copy_(gumbel_counted)
             torch.cuda.synchronize(e.device)
             try:
                 g = torch.cuda.CUDAGraph()
@@ -1089,6 +1198,8 @@ class PortableTreeMCTS:
         self.engine.reuse_dropped.zero_()
         self.cap_counts.zero_()
         self.engine.forced_count.zero_(); self._pruned_total.zero_()
+        if self.gumbel:
+            self.engine.gumbel["count"].zero_()
         # refused expansions / fewest free chunks are per run too (a cached engine must not report an earlier run's)
         # (pool_stats[2], the chunks reserved for fresh roots, follows the trees' state and is NOT a per-run statistic)
         self.engine.buf["pool_stats"][:2].copy_(torch.tensor([0, self.engine.pool_chunks], dtype=torch.int32))
@@ -1113,6 +1224,8 @@ class PortableTreeMCTS:
         self.engine.live_total.zero_()
         self.cap_counts.zero_()
         self.engine.forced_count.zero_(); self._pruned_total.zero_()
+        if self.gumbel:
+            self.engine.gumbel["count"].zero_()
         self.get_timing(reset=True)
         if self.batch_k > 1:
             self.engine.wbuf["eval_total"].zero_(); self.engine.wbuf["eval_count"].zero_()
@@ -1145,6 +1258,8 @@ class PortableTreeMCTS:
         # the number of live games: the lists pay once a launch gets at least one network pass per CU shorter)
         self.compact_now = self.compact_default if (compact is None or self.cap) else bool(compact)
         add_noise = self.add_noise if add_dirichlet_noise is None else bool(add_dirichlet_noise)
+        if self.gumbel:
+            add_noise = False             # the Gumbel variates are the exploration: no Dirichlet mix, no noise draws
         e.set_roots(state, active)
         continue_trees = self.reuse_tree and self._have_trees
         self.rng.begin_move(reset if self._have_trees else None, rng_game_ids, rng_plies)
@@ -1160,6 +1275,13 @@ class PortableTreeMCTS:
                     self._noise_buf[:, : int(self.injected_noise.shape[1])].copy_(self.injected_noise.to(torch.float32))
                 else:
                     self.rng.gamma_into(self._noise_buf, self.alpha, MAX_CHILDREN)
+            if self.gumbel:               # refreshed in place: the captured graph reads this buffer at every replay
+                gbuf = e.gumbel["g"]
+                if self.injected_gumbel is not None:
+                    gbuf.zero_()
+                    gbuf[:, : int(self.injected_gumbel.shape[1])].copy_(self.injected_gumbel.to(torch.float32))
+                else:
+                    self.rng.gumbel_into(gbuf, MAX_CHILDREN)
             self._search(add_noise, continue_trees)
         self._have_trees = True
 
@@ -1240,6 +1362,7 @@ class DualStreamTreeMCTS:
         # playout cap: one full / fast mask over all games, each part writing its slice (the wave tail reads the whole)
         self.cap = self.parts[0].cap
         self.forced = self.parts[0].forced
+        self.gumbel = self.parts[0].gumbel
         self.full_search = None
         if self.cap:
             self.full_search = torch.zeros((self.B,), dtype=torch.uint8, device=dev)
@@ -1272,6 +1395,10 @@ class DualStreamTreeMCTS:
     @property
     def cap_counts(self) -> torch.Tensor:
         return sum(p.cap_counts for p in self.parts)
+
+    @property
+    def gumbel_searches(self) -> torch.Tensor:
+        return sum(p.gumbel_searches for p in self.parts)
 
     @property
     def forced_counts(self) -> torch.Tensor:
@@ -1527,7 +1654,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        device_tail: bool = True, batch_k: int = 1, evaluator: str = "auto", seed: int = 12345,
                        collect_timing: bool = False, row_log=None, eval_symmetry="none",
                        playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
-                       forced_playouts_k: float = 0.0) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
+                       forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
+                       gumbel_c_scale: float = 1.0) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
     `model` may also be a `PriorEvaluator` (states -> priors over the 220 actions + values, the reference's own
@@ -1546,10 +1674,17 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     recorded_positions.  Fused network and batch_k = 1 only (ValueError otherwise).
     `forced_playouts_k` k (0 = off): forced playouts and policy target pruning (PortableTreeMCTS) in every search that
     records a row; mcts_counters gain forced_playouts / pruned_visits.  Fused network and batch_k = 1 only (ValueError
-    otherwise)."""
+    otherwise).
+    `gumbel_considered` m (0 = off; the paper uses 16), `gumbel_c_visit`, `gumbel_c_scale`: Gumbel root search with
+    Sequential Halving (PortableTreeMCTS) in every search that records a row: the move is the Sequential Halving winner
+    and the row's policy is softmax(log P + sigma(completed Q)).  Such a search never mixes Dirichlet noise into the root
+    priors, whatever `add_dirichlet_noise` says: the Gumbel variates are its exploration.  mcts_counters gain
+    gumbel_searches.  Fused network and batch_k = 1 only; not with forced playouts, `policy_target_temperature` or
+    `policy_target_prior_pseudocount` > 0 (ValueError)."""
     dev = torch.device(device)
     cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
     forced = forced_playouts_on(forced_playouts_k)
+    gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
     eval_symmetry = parse_eval_symmetry(eval_symmetry)
     if eval_symmetry != "none" and int(batch_k) > 1:
         raise ValueError("eval_symmetry is not supported by the legacy waves (batch_k > 1): their wave kernels evaluate "
@@ -1578,6 +1713,12 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                          "evaluator, not legacy waves)")
     if forced and _persistent_default():
         raise ValueError("forced playouts are not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
+    if gumbel:
+        why = gumbel_refusal(batch_k=batch_k, fused=use_fused, forced_playouts_k=forced_playouts_k,
+                             policy_target_temperature=policy_target_temperature,
+                             policy_target_prior_pseudocount=policy_target_prior_pseudocount)
+        if why is not None:
+            raise ValueError(f"the Gumbel root search is not supported with {why}")
     if use_fused and persistent_search_available(net, batch_k) and eval_symmetry == "none":
         if cap:
             raise ValueError("playout cap randomization is not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
@@ -1596,6 +1737,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         kw.update(fast_simulations=int(playout_cap_fast_simulations), full_prob=float(playout_cap_full_prob))
     if forced:
         kw["forced_playouts_k"] = float(forced_playouts_k)
+    if gumbel:
+        kw.update(gumbel_considered=int(gumbel_considered), gumbel_c_visit=float(gumbel_c_visit),
+                  gumbel_c_scale=float(gumbel_c_scale))
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a
@@ -1773,6 +1917,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                                recorded_positions=int(positions)) if cap else {}),
                        # forced playouts: descents that took a due root child, visits pruned from the training targets
                        **(dict(zip(("forced_playouts", "pruned_visits"), (int(x) for x in mcts.forced_counts.tolist())))
-                          if forced else {})},
+                          if forced else {}),
+                       # Gumbel root search: searches of live games that ran the rule
+                       **({"gumbel_searches": int(mcts.gumbel_searches.item())} if gumbel else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))
     return batch, stats

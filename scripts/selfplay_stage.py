@@ -52,6 +52,11 @@ def parse(argv=None):
                     help="playout cap randomization: probability that a move gets a full search and a training row")
     ap.add_argument("--forced_playouts_k", type=float, default=0.0,
                     help="forced playouts and policy target pruning (tree backend): k of sqrt(k * prior * root visits), 0 = off")
+    ap.add_argument("--gumbel_considered", type=int, default=0,
+                    help="Gumbel root search with Sequential Halving (tree backend): considered root actions m, 0 = off "
+                         "(the paper uses 16)")
+    ap.add_argument("--gumbel_c_visit", type=float, default=50.0, help="Gumbel root search: c_visit of sigma")
+    ap.add_argument("--gumbel_c_scale", type=float, default=1.0, help="Gumbel root search: c_scale of sigma")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -112,7 +117,8 @@ def main(argv=None) -> int:
         policy_target_temperature=args.policy_target_temperature,
         policy_target_prior_pseudocount=args.policy_target_prior_pseudocount,
         playout_cap_fast_simulations=args.playout_cap_fast_simulations, playout_cap_full_prob=args.playout_cap_full_prob,
-        forced_playouts_k=args.forced_playouts_k)
+        forced_playouts_k=args.forced_playouts_k, gumbel_considered=args.gumbel_considered,
+        gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale)
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
