@@ -259,6 +259,32 @@ LZ_API int lz_wave_step_finish(const LzStateSoA* states, int64_t num_slots, int6
                                int64_t* outcome, int64_t* delta_hist, int64_t* lengths, const int64_t* slot_game,
                                int64_t* finished, uint8_t* reseated, int reseat, int64_t* game_plies, void* stream);
 
+/* TD(lambda) value targets from the searches' root values (off in the reference: every row gets the final result).
+ * For the searched plies t = 0..L-1 of a game, Q_t = current_player_t * root_value_t (Black's frame), y_L = z (the
+ * result lz_wave_step_finish books), y_t = (1 - lambda) Q_t + lambda y_{t+1}; the row recorded at ply t gets
+ * value = sign * y_t.  The recurrence runs in double (as a chunked suffix scan, so not bit-equal to a sequential
+ * evaluation except for lambda = 0 and 1) and every y_t is rounded to float32 once.
+ *
+ * lz_wave_note_value: between lz_wave_record and lz_wave_step_finish.  A live slot at ply p = plies[g] gets
+ * q_hist[g, p] = current_player * root_value, hist_len[g] = p + 1, was_live[g] = 1 and, if it recorded a row this ply
+ * (rows[g] >= 0, as lz_wave_record left it), step_ply[g, step_counts[g] - 1] = p; a finished slot gets was_live[g] = 0.
+ * q_hist float32[num_slots, max_plies], step_ply int32[num_slots, max_plies], hist_len int32[num_slots], was_live
+ * uint8[num_slots].  A ply >= max_plies writes nothing and bumps *overflow.  A re-seated slot needs no reset.
+ *
+ * lz_wave_td_targets: after lz_wave_step_finish (reseat == 0) and before lz_wave_log_finished.  For every slot whose
+ * game ended this ply (was_live[g] && done[g]) with step_counts[g] > 0 rows: z is read back from the game's first row
+ * (sign * value, exact) and value_targets[row_j] = sign[row_j] * y[step_ply[g, j]] for its rows, row_j =
+ * step_index_matrix[g, j], or g * max_steps + j when step_index_matrix == NULL.  Nothing else is touched. */
+LZ_API int lz_wave_note_value(const uint8_t* done, int64_t num_slots, const int64_t* plies, const int64_t* rows,
+                              const int64_t* step_counts, const float* root_value, const int64_t* current_player,
+                              float* q_hist, int32_t* step_ply, int32_t* hist_len, uint8_t* was_live,
+                              int64_t max_plies, int32_t* overflow, void* stream);
+LZ_API int lz_wave_td_targets(const uint8_t* done, const uint8_t* was_live, int64_t num_slots, double lambda,
+                              const float* q_hist, const int32_t* step_ply, const int32_t* hist_len,
+                              int64_t max_plies, float* value_targets, const int8_t* player_signs,
+                              const int64_t* step_index_matrix, const int64_t* step_counts, int64_t max_steps,
+                              void* stream);
+
 /* lz_wave_reseat: the wave loop of self_play_gpu_runner.py:84-90 starts the next `concurrent_games` games only when the
  * whole wave has finished; here finished slots (done[g] != 0, ascending g) restart from the empty board at once while
  * *budget (games not yet started) lasts: slot_game[g] = (*next_game)++, plies / step_counts = 0, done[g] = 0,

@@ -1359,6 +1359,87 @@ __global__ __launch_bounds__(kBlock) void wave_step_finish_kernel(
     }
 }
 
+// ---- TD(lambda) value targets: y_L = z, y_t = (1 - lambda) Q_t + lambda y_{t+1}, Q_t = the search's root value of ply t
+// from Black's frame.  Every search of a game notes its Q (the fast searches of the playout cap too); when the game
+// ends the value column of its rows is rewritten from z (wave_step_finish_kernel) to sign * y_t.
+// one lane per slot, between wave_record_kernel and wave_step_finish_kernel (plies[g] is still this search's ply)
+__global__ __launch_bounds__(kBlock) void wave_note_value_kernel(
+    const uint8_t* __restrict__ done, int64_t G, const int64_t* __restrict__ plies, const int64_t* __restrict__ rows,
+    const int64_t* __restrict__ step_counts, const float* __restrict__ root_value, const int64_t* __restrict__ player,
+    float* __restrict__ q_hist, int32_t* __restrict__ step_ply, int32_t* __restrict__ hist_len,
+    uint8_t* __restrict__ was_live, int64_t Tmax, int32_t* __restrict__ overflow) {
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= G) return;
+    if (done[g] != 0) { was_live[g] = 0; return; }
+    was_live[g] = 1;
+    const int64_t p = plies[g];
+    if (p < 0 || p >= Tmax) { atomicAdd(overflow, 1); return; }
+    const float rv = root_value[g];
+    q_hist[g * Tmax + p] = player[g] >= 0 ? rv : -rv;
+    hist_len[g] = (int32_t)(p + 1);
+    if (rows[g] >= 0) {
+        const int64_t n = step_counts[g];               // wave_rows*_kernel has counted this ply's row already
+        if (n < 1 || n > Tmax) atomicAdd(overflow, 1);
+        else step_ply[g * Tmax + n - 1] = (int32_t)p;
+    }
+}
+
+// one wave per slot whose game ended this ply, after wave_step_finish_kernel.  The recurrence is a first-order linear
+// suffix scan: 64 plies per pass (one per lane) from the game's last chunk backwards, each pass a Kogge-Stone scan
+// s_l += lambda^(2^i) s_(l + 2^i) over the terms (1 - lambda) Q, then + lambda^(n - l) carry with the carry = y of the
+// chunk above (z for the last chunk).  All in double, one rounding to fp32 per y.  z is read back from the game's first
+// row, which holds sign * z exactly.  step_ply is ascending in the step, so the rows of a chunk are the topmost ones not
+// yet written: lane l takes the l-th of them from the top and fetches y from the lane that owns its ply.
+__global__ __launch_bounds__(kBlock) void wave_td_targets_kernel(
+    const uint8_t* __restrict__ done, const uint8_t* __restrict__ was_live, int64_t G, double lam,
+    const float* __restrict__ q_hist, const int32_t* __restrict__ step_ply, const int32_t* __restrict__ hist_len,
+    int64_t Tmax, float* __restrict__ value_t, const int8_t* __restrict__ signs,
+    const int64_t* __restrict__ step_index, const int64_t* __restrict__ step_counts, int64_t max_steps) {
+    const int lane = lane_id();
+    const int64_t g = wave_item();
+    if (g >= G) return;
+    if (was_live[g] == 0 || done[g] == 0) return;
+    int64_t n = step_counts[g];
+    if (n > max_steps) n = max_steps;
+    if (n > Tmax) n = Tmax;
+    int64_t len = hist_len[g];
+    if (len > Tmax) len = Tmax;
+    if (n <= 0 || len <= 0) return;                     // no recorded row: nothing to write
+    const int64_t first = step_index ? step_index[g * max_steps] : g * max_steps;
+    double carry = (double)((float)signs[first] * value_t[first]);
+    double pw[7];                                       // lambda^(2^i), formed once by squaring (constant indices only)
+    pw[0] = lam;
+#pragma unroll
+    for (int i = 1; i < 7; ++i) pw[i] = pw[i - 1] * pw[i - 1];
+    const double om = 1.0 - lam;
+    int64_t top = n;                                    // rows [top, n) are written
+    for (int64_t base = ((len - 1) / kWave) * kWave; base >= 0; base -= kWave) {
+        const int cn = (int)(len - base < kWave ? len - base : kWave);
+        double s = lane < cn ? om * (double)q_hist[g * Tmax + base + lane] : 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const double up = __shfl_down(s, 1u << i, kWave);
+            if (lane + (1 << i) < kWave) s += pw[i] * up;
+        }
+        const int e = cn - lane;                        // 1..64 for the lanes that hold a ply
+        double cp = 1.0;
+#pragma unroll
+        for (int i = 0; i < 7; ++i)
+            if ((e >> i) & 1) cp *= pw[i];
+        const double y = s + cp * carry;
+        carry = __shfl(y, 0, kWave);
+        const int64_t j = top - 1 - lane;
+        const int64_t p = j >= 0 ? (int64_t)step_ply[g * Tmax + j] : -1;
+        const bool mine = p >= base && p < base + cn;
+        const float yp = (float)__shfl(y, mine ? (int)(p - base) : 0, kWave);
+        if (mine) {
+            const int64_t idx = step_index ? step_index[g * max_steps + j] : g * max_steps + j;
+            value_t[idx] = (float)signs[idx] * yp;
+        }
+        top -= __popcll(__ballot(mine));
+    }
+}
+
 // ---- finished-row log: the rows of a game leave the slot-major live arena for a game-major log the moment the game
 // has ended, so that a consumer can take finished samples away WHILE the wave goes on playing (the worker streams
 // them to the host; v1/python/self_play_worker.py:430-546 only sees its rows after a whole wave has drained).
@@ -1873,6 +1954,33 @@ int lz_wave_step_finish(const LzStateSoA* s, int64_t G, int64_t* plies, uint8_t*
                        signs, step_index, step_counts, Tmax, reinterpret_cast<unsigned long long*>(outcome),
                        reinterpret_cast<unsigned long long*>(delta_hist), lengths, slot_game,
                        reinterpret_cast<unsigned long long*>(finished), reseated, reseat, game_plies);
+    return launch_status();
+}
+
+int lz_wave_note_value(const uint8_t* done, int64_t G, const int64_t* plies, const int64_t* rows,
+                       const int64_t* step_counts, const float* root_value, const int64_t* current_player, float* q_hist,
+                       int32_t* step_ply, int32_t* hist_len, uint8_t* was_live, int64_t Tmax, int32_t* overflow,
+                       void* stream) {
+    if (G < 0 || Tmax <= 0 || Tmax > INT32_MAX) return LZ_ERR_ARG;
+    if (G == 0) return LZ_OK;
+    if (!done || !plies || !rows || !step_counts || !root_value || !current_player || !q_hist || !step_ply ||
+        !hist_len || !was_live || !overflow)
+        return LZ_ERR_ARG;
+    hipLaunchKernelGGL(wave_note_value_kernel, dim3(grid_threads(G)), dim3(kBlock), 0, as_stream(stream), done, G, plies,
+                       rows, step_counts, root_value, current_player, q_hist, step_ply, hist_len, was_live, Tmax,
+                       overflow);
+    return launch_status();
+}
+
+int lz_wave_td_targets(const uint8_t* done, const uint8_t* was_live, int64_t G, double lambda, const float* q_hist,
+                       const int32_t* step_ply, const int32_t* hist_len, int64_t Tmax, float* value_t,
+                       const int8_t* signs, const int64_t* step_index, const int64_t* step_counts, int64_t max_steps,
+                       void* stream) {
+    if (G < 0 || Tmax <= 0 || Tmax > INT32_MAX || max_steps <= 0 || !(lambda >= 0.0 && lambda <= 1.0)) return LZ_ERR_ARG;
+    if (G == 0) return LZ_OK;
+    if (!done || !was_live || !q_hist || !step_ply || !hist_len || !value_t || !signs || !step_counts) return LZ_ERR_ARG;
+    hipLaunchKernelGGL(wave_td_targets_kernel, dim3(grid_waves(G)), dim3(kBlock), 0, as_stream(stream), done, was_live, G,
+                       lambda, q_hist, step_ply, hist_len, Tmax, value_t, signs, step_index, step_counts, max_steps);
     return launch_status();
 }
 

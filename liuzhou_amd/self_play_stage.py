@@ -81,6 +81,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     cap_meta: Optional[Dict[str, Any]] = None
     forced_meta: Optional[Dict[str, Any]] = None
     gumbel_meta: Optional[Dict[str, Any]] = None
+    td_meta: Optional[Dict[str, Any]] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -105,6 +106,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         if isinstance(wgumbel, dict) and gumbel_meta is None:
             gumbel_meta = {"considered": int(wgumbel.get("considered", 0)), "c_visit": float(wgumbel.get("c_visit", 50.0)),
                            "c_scale": float(wgumbel.get("c_scale", 1.0))}
+        wtd = (wm.get("metadata") or {}).get("value_target")
+        if isinstance(wtd, dict) and td_meta is None:
+            td_meta = {"td_lambda": float(wtd.get("td_lambda", 1.0))}
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -127,6 +131,8 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
                                                      for k in ("forced_playouts", "pruned_visits")}}
     if gumbel_meta is not None:         # Gumbel root search: its settings and the searches that ran the rule, all workers
         meta["gumbel"] = {**gumbel_meta, "gumbel_searches": int(merged.mcts_counters.get("gumbel_searches", 0))}
+    if td_meta is not None:             # TD(lambda) value targets: the lambda the rows' value_targets were blended with
+        meta["value_target"] = td_meta
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -150,8 +156,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         eval_symmetry: Any = "none", worker_fn: Optional[Callable[..., Dict[str, Any]]] = None,
                         in_process: bool = False, playout_cap_fast_simulations: int = 0,
                         playout_cap_full_prob: float = 1.0, forced_playouts_k: float = 0.0,
-                        gumbel_considered: int = 0, gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0
-                        ) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        gumbel_considered: int = 0, gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0,
+                        value_target_lambda: float = 1.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
@@ -159,9 +165,15 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
     `playout_cap_full_prob` (tree backend, playout cap randomization) only when the cap is on, and `forced_playouts_k`
     (tree backend, forced playouts and policy target pruning) only when it is > 0, and `gumbel_considered` /
     `gumbel_c_visit` / `gumbel_c_scale` (tree backend, Gumbel root search with Sequential Halving; a Gumbel search never
-    mixes Dirichlet noise into the root priors, whatever `add_dirichlet_noise` says) only when gumbel_considered > 0."""
+    mixes Dirichlet noise into the root priors, whatever `add_dirichlet_noise` says) only when gumbel_considered > 0, and
+    `value_target_lambda` (tree backend, TD(lambda) value targets from the searches' root values; 1 = off) only when < 1."""
     from .gumbel import gumbel_on
     from .tree_engine import forced_playouts_on, gumbel_refusal, playout_cap_on
+    from .value_target import td_lambda_on
+    td = td_lambda_on(value_target_lambda)
+    if td and str(search_backend).strip().lower() not in ("portable", "tree"):
+        raise ValueError(f"TD(lambda) value targets need the tree backend, not the root-PUCT search ({search_backend!r}): "
+                         "they blend the tree search's root values")
     gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
     if gumbel:
         if str(search_backend).strip().lower() not in ("portable", "tree"):
@@ -214,7 +226,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                 "playout_cap_full_prob": float(playout_cap_full_prob)} if cap else {}),
             **({"forced_playouts_k": float(forced_playouts_k)} if forced else {}),
             **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
-                "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}))
+                "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
+            **({"value_target_lambda": float(value_target_lambda)} if td else {}))
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

@@ -32,6 +32,7 @@ from .net_hip import DescArray, FusedNet, LzNetDesc, MAX_MULTI_NETS, multi_compa
 from .self_play_types import SelfPlayV1Stats
 from .streams import CAPTURE_MODE
 from .trajectory_buffer import TensorSelfPlayBatch, TensorTrajectoryBuffer
+from .value_target import td_lambda_on
 
 MAX_CHILDREN = 72
 OUT_CAP = 80
@@ -1655,7 +1656,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        collect_timing: bool = False, row_log=None, eval_symmetry="none",
                        playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
                        forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
-                       gumbel_c_scale: float = 1.0) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
+                       gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0
+                       ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
     `model` may also be a `PriorEvaluator` (states -> priors over the 220 actions + values, the reference's own
@@ -1680,8 +1682,17 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     and the row's policy is softmax(log P + sigma(completed Q)).  Such a search never mixes Dirichlet noise into the root
     priors, whatever `add_dirichlet_noise` says: the Gumbel variates are its exploration.  mcts_counters gain
     gumbel_searches.  Fused network and batch_k = 1 only; not with forced playouts, `policy_target_temperature` or
-    `policy_target_prior_pseudocount` > 0 (ValueError)."""
+    `policy_target_prior_pseudocount` > 0 (ValueError).
+    `value_target_lambda` (1 = off): TD(lambda) value targets (value_target.py).  With Q_t = the root value of the game's
+    t-th search from Black's frame (every search counts, the playout cap's fast ones and a terminal root's too), y_L = the
+    result and y_t = (1 - lambda) Q_t + lambda y_{t+1}, the row recorded at ply t gets value_target = sign * y_t instead of
+    sign * result; `soft_value_targets` stay as they are.  Needs `device_tail` (ValueError otherwise: the host loop keeps
+    the reference's finalisation); composes with everything else."""
     dev = torch.device(device)
+    td = td_lambda_on(value_target_lambda)
+    if td and not device_tail:
+        raise ValueError("value_target_lambda < 1 needs device_tail: the host loop keeps the reference's finalisation "
+                         "(every row gets the final result)")
     cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
     forced = forced_playouts_on(forced_playouts_k)
     gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
@@ -1776,7 +1787,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     delta_hist = None
     if device_tail:
         from .wave_tail import WaveTail
-        tail = WaveTail(buffer, wave, int(max_game_plies), dev, soft_value_k=float(soft_value_k), row_log=row_log)
+        tail = WaveTail(buffer, wave, int(max_game_plies), dev, soft_value_k=float(soft_value_k), row_log=row_log,
+                        **({"value_target_lambda": float(value_target_lambda)} if td else {}))
         tail.collect_timing = bool(collect_timing)
         outcome, delta_hist = tail.outcome, tail.delta_hist
         if cap:

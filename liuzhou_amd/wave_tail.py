@@ -1,5 +1,6 @@
 """Device-side tail of one ply of the v1 wave loop for a fixed wave of slots: trajectory rows, the move and the
-finalisation of finished games without a host round trip (`lz_wave_record`, `lz_wave_step_finish`).
+finalisation of finished games without a host round trip (`lz_wave_record`, `lz_wave_step_finish`), and optionally the
+TD(lambda) value targets from the searches' root values (`lz_wave_note_value`, `lz_wave_td_targets`; value_target.py).
 
 It replaces, for whole waves, the sequence `append_steps` -> `step_index[...] = rows` -> `self_play_step_inplace` ->
 `finalize_games_inplace` of v1/python/self_play_gpu_runner.py:205-247, whose `nonzero`-shaped outputs force one host
@@ -15,13 +16,19 @@ import torch
 from . import _lib as L
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput
 from .trajectory_buffer import TensorTrajectoryBuffer
+from .value_target import td_lambda_on
 
 DELTA_BINS = 37
 
 
 class WaveTail:
     def __init__(self, buffer: TensorTrajectoryBuffer, num_slots: int, max_game_plies: int, device,
-                 soft_value_k: float = 2.0, reseat: bool = False, row_log=None) -> None:
+                 soft_value_k: float = 2.0, reseat: bool = False, row_log=None, value_target_lambda: float = 1.0) -> None:
+        # TD(lambda) value targets (value_target.py; 1 = off: every row gets the game's result, nothing below exists)
+        self.td_lambda = float(value_target_lambda) if td_lambda_on(value_target_lambda) else None
+        if self.td_lambda is not None and reseat:
+            raise ValueError("WaveTail: value_target_lambda < 1 is not supported with the in-kernel re-seat (reseat=True): "
+                             "it clears step_counts inside the step kernel, before the targets of the game are formed")
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("WaveTail needs a HIP device (no CPU path)")
@@ -47,6 +54,14 @@ class WaveTail:
         # finished_log.FinishedRowLog: the live rows are slot-major (row = slot * max_plies + step, no step_index matrix)
         # and the rows of a game move to the log when the game ends (the streaming worker)
         self.row_log = row_log
+        # TD(lambda): the root value of every searched ply from Black's frame, the ply of every recorded step, the searched
+        # plies of the game in each slot and the slots that were live when the ply began (8 B per slot and ply + 5 B per slot)
+        self.q_hist = self.step_ply = self.hist_len = self.was_live = None
+        if self.td_lambda is not None:
+            self.q_hist = torch.zeros((self.G, self.max_plies), dtype=torch.float32, device=dev)
+            self.step_ply = torch.zeros((self.G, self.max_plies), dtype=torch.int32, device=dev)
+            self.hist_len = z(self.G, torch.int32)
+            self.was_live = z(self.G, torch.uint8)
         if row_log is not None:
             if reseat:
                 raise ValueError("WaveTail: the finished-row log needs run()'s re-seating (reseat=False)")
@@ -123,6 +138,31 @@ class WaveTail:
                 L.ptr(self.delta_hist), L.ptr(lengths), L.ptr(slot_game), L.ptr(self.finished), L.ptr(reseated),
                 C.c_int(1 if self.reseat else 0), L.ptr(self.game_plies), L.stream_ptr(self.device)), "wave_step_finish")
 
+    def note_value(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, step_counts: torch.Tensor,
+                   search: RootSearchBatchOutput) -> None:
+        """TD(lambda): keep this ply's root value of every live slot (between `record` and `step_finish`)."""
+        rv = search.root_value.contiguous()
+        if rv.dtype != torch.float32 or int(rv.numel()) != self.G:
+            raise RuntimeError("WaveTail.note_value: root_value must be float32[num_slots]")
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_wave_note_value(
+                L.ptr(done), L.i64(self.G), L.ptr(plies), L.ptr(self.rows), L.ptr(step_counts), L.ptr(rv),
+                L.ptr(states.current_player), L.ptr(self.q_hist), L.ptr(self.step_ply), L.ptr(self.hist_len),
+                L.ptr(self.was_live), L.i64(self.max_plies), L.ptr(self.overflow), L.stream_ptr(self.device)),
+                "wave_note_value")
+
+    def td_targets(self, done: torch.Tensor, step_index: torch.Tensor, step_counts: torch.Tensor) -> None:
+        """TD(lambda): rewrite the value targets of the games that ended this ply (after `step_finish`, before their rows
+        leave for a finished-row log)."""
+        _, _, _, a_value, _, a_sign = self.buffer.arena()
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_wave_td_targets(
+                L.ptr(done), L.ptr(self.was_live), L.i64(self.G), C.c_double(self.td_lambda), L.ptr(self.q_hist),
+                L.ptr(self.step_ply), L.ptr(self.hist_len), L.i64(self.max_plies), L.ptr(a_value), L.ptr(a_sign),
+                L.ptr(step_index), L.ptr(step_counts),
+                L.i64(self.max_plies if step_index is None else int(step_index.shape[1])), L.stream_ptr(self.device)),
+                "wave_td_targets")
+
     def start_next_games(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, step_counts: torch.Tensor,
                          budget: torch.Tensor, next_game: torch.Tensor, slot_game: torch.Tensor,
                          reseated: Optional[torch.Tensor] = None) -> None:
@@ -144,7 +184,9 @@ class WaveTail:
         pinned memory behind an event), so the host stays one ply ahead of the device; the price is exactly one
         extra, fully masked ply at the end.  Returns the number of plies launched (including that one).
         With a finished-row log (`row_log`) `step_index` is None, the rows of the games that have ended move to the log
-        after every ply, and the loop ends when every game has ended AND is in a log (which the caller then closes)."""
+        after every ply, and the loop ends when every game has ended AND is in a log (which the caller then closes).
+        With TD(lambda) value targets (`value_target_lambda` < 1) the order per ply is record -> note_value -> step_finish
+        -> td_targets -> the log: the rows of a game that ends carry their final targets before they leave."""
         dev, g = self.device, self.G
         log = self.row_log
         if (log is None) == (step_index is None):
@@ -178,8 +220,13 @@ class WaveTail:
             reseated.zero_()
             with self._bracket("finalize_ms"):
                 self.record(states, done, step_index, step_counts, search)
+                if self.td_lambda is not None:
+                    self.note_value(states, plies, done, step_counts, search)
             with self._bracket("self_play_step_ms"):
                 self.step_finish(states, plies, done, step_index, step_counts, search, lengths=lengths, slot_game=slot_game)
+            if self.td_lambda is not None:
+                with self._bracket("finalize_ms"):
+                    self.td_targets(done, step_index, step_counts)
             # all finished and nothing left to start (a finished slot restarts at the top of the next ply otherwise)
             if log is not None:
                 if ply == 0:

@@ -57,6 +57,9 @@ def parse(argv=None):
                          "(the paper uses 16)")
     ap.add_argument("--gumbel_c_visit", type=float, default=50.0, help="Gumbel root search: c_visit of sigma")
     ap.add_argument("--gumbel_c_scale", type=float, default=1.0, help="Gumbel root search: c_scale of sigma")
+    ap.add_argument("--value_target_lambda", type=float, default=1.0,
+                    help="TD(lambda) value targets (tree backend): lambda of y_t = (1 - lambda) Q_t + lambda y_(t+1) over the "
+                         "searches' root values, 1 = off (every row gets the final result)")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -118,7 +121,8 @@ def main(argv=None) -> int:
         policy_target_prior_pseudocount=args.policy_target_prior_pseudocount,
         playout_cap_fast_simulations=args.playout_cap_fast_simulations, playout_cap_full_prob=args.playout_cap_full_prob,
         forced_playouts_k=args.forced_playouts_k, gumbel_considered=args.gumbel_considered,
-        gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale)
+        gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale,
+        value_target_lambda=args.value_target_lambda)
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
