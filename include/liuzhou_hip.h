@@ -469,9 +469,14 @@ typedef struct LzTreeDesc {
      * launch runs ceil(live / samples-per-pass) network passes instead of one per slot: the cost of a wave that is
      * draining follows its live games (the reference's PortableMCTS.evaluate_states gets exactly the pending leaves,
      * v1/python/portable_mcts.py:337-378).  live_row[g] = row of game g's leaf in the list; live_count[s] = number
-     * of leaves of simulation s.  Results are bit-identical to the dense launch. */
-    void*    live_state;           /* [num_games] 32-byte packed states */
-    int32_t* live_row;             /* [num_games] */
+     * of leaves of simulation s.  Results are bit-identical to the dense launch.
+     * Where the network has a gathering launch (lz_net_forward_packed_gather_f16) and a full launch is more network
+     * passes than workgroups, the search evaluates the live leaves in place instead -- the network kernel picks them out
+     * of leaf_state by their leaf_kind and writes live_count[s] itself: live_state and live_row are then UNUSED (they
+     * must still be set: the scan path, env LZ_TREE_GATHER=0, the multi-network search and the parity networks use
+     * them); live_count[s] holds the same numbers on both paths. */
+    void*    live_state;           /* [num_games] 32-byte packed states (scan path) */
+    int32_t* live_row;             /* [num_games] (scan path) */
     int64_t* live_count;           /* [live_count_cap] */
     int64_t  live_count_cap;
     /* Optional position index (all four arrays and pos_slots, or none): a leaf whose 32-byte state another node (not
@@ -848,6 +853,18 @@ LZ_API int lz_symmetry_transform_states(const LzStateSoA* in, const void* sym, i
  * kept.  The device build runs the wave function of the tree search's symmetric leaf evaluation. */
 LZ_API int lz_symmetry_transform_packed(const int64_t* in /*[B,4]*/, const void* sym, int32_t sym_width,
                                         int64_t* out /*[B,4]*/, int64_t batch, void* stream);
+
+/* The packed forward on the slots of a batch that are LIVE: slot g of packed_states[num_slots] is evaluated iff
+ * leaf_kind[g] == 1 (device int32[num_slots]; the tree search's "leaf to expand"), and its outputs go to row g of the
+ * output arrays, bit-identical to lz_net_forward_packed_f16 of that slot; rows of other slots are not written.
+ * *count_out (device int64) = the number of live slots.  The launch costs ceil(live / samples-per-pass) network passes:
+ * every workgroup reads the flags for itself and takes its share of the live slots in ascending order.
+ * LZ_ERR_UNSUPPORTED: fp32-operand and split-fp16 networks (flags bits 2-3), or more slots than the kernel's LDS has
+ * room for (12 bytes per 64 slots: about 11 000 slots for the two-per-CU 64-channel shape, which has to stay under 80 KB,
+ * more than 90 000 for the others). */
+LZ_API int lz_net_forward_packed_gather_f16(const LzNetDesc* net, const void* packed_states, const int32_t* leaf_kind,
+                                            int64_t num_slots, int64_t* count_out, float* log_p1, float* log_p2,
+                                            float* log_pmc, float* value_logits, float* value, void* stream);
 
 #ifdef __cplusplus
 }

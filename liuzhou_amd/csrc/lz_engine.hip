@@ -1670,6 +1670,25 @@ int lz_tree_advance(const LzTreeDesc* d, const int32_t* played_action, const uin
     return st();
 }
 
+int lz_net_gather_supported(const LzNetDesc* d, int64_t num_slots);    // lz_net.hip
+void lz_net_launch_shape(const LzNetDesc* d, int* max_blocks, int* samples);
+
+// A list search (LzTreeDesc.live_*) evaluates its live leaves in place with the gathering network launch, without the
+// scan kernel, when the network has that launch for B slots and the gate admits the launch shape: a full launch is more
+// network passes than workgroups (the head of the gathering kernel costs a few us, which a launch of one pass per
+// workgroup does not win back: DESIGN.md section 5) and the step is the one-wave kernel.  Env LZ_TREE_GATHER: 0 = never,
+// 1 = wherever the network has the launch, past the gate (tests), unset = the gate.  Read once per search: the choice is
+// frozen into a captured graph.
+static bool tree_gather_path(const LzNetDesc* net, int64_t B) {
+    const char* e = getenv("LZ_TREE_GATHER");
+    if (e && e[0] == '0') return false;
+    if (!lz_net_gather_supported(net, B)) return false;
+    if (e && e[0] == '1') return true;
+    int max_blocks = 0, samples = 1;
+    lz_net_launch_shape(net, &max_blocks, &samples);
+    return (B + samples - 1) / samples > max_blocks && !split_step(B);
+}
+
 // Whole search of one move, enqueued from C++ (no Python in the simulation loop, hipGraph-capturable):
 //   begin -> [net -> expand_root + select] -> (sims-1) x [net -> expand+backup + select] -> net -> expand+backup
 // `continue_trees`: the roots were prepared by lz_tree_advance (kept subtrees or fresh roots), so no begin.
@@ -1682,9 +1701,12 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                               float epsilon, void* stream) {
     const int64_t B = d->num_games;
     int rc = LZ_OK;
-    if (t.live_count != nullptr) {
+    if (t.live_count != nullptr && d->live_count_cap < sims + 2) return LZ_ERR_ARG;
+    // gathering launch: the network kernel takes simulation s's live leaves out of leaf_state by their leaf_kind and writes
+    // live_count[s]; outputs lie at the game's own row, so the step kernels are the dense branch's and nothing scans
+    const bool gather = t.live_count != nullptr && tree_gather_path(net, B);
+    if (t.live_count != nullptr && !gather) {
         // compact evaluation lists: simulation s evaluates live_count[s] leaves (see LzTreeDesc.live_*)
-        if (d->live_count_cap < sims + 2) return LZ_ERR_ARG;
         hipLaunchKernelGGL(tree_live_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t, t.live_count);   // the roots
         for (int64_t s = 0; s <= sims; ++s) {
             rc = lz_net_forward_packed_counted_f16(net, d->live_state, B, d->live_count + s, lp1, lp2, lpmc, nullptr, values,
@@ -1719,7 +1741,9 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
         return st();
     }
     for (int64_t s = 0; s <= sims; ++s) {
-        rc = lz_net_forward_packed_f16(net, d->leaf_state, B, lp1, lp2, lpmc, nullptr, values, stream);
+        rc = gather ? lz_net_forward_packed_gather_f16(net, d->leaf_state, t.leaf_kind, B, d->live_count + s, lp1, lp2, lpmc,
+                                                       nullptr, values, stream)
+                    : lz_net_forward_packed_f16(net, d->leaf_state, B, lp1, lp2, lpmc, nullptr, values, stream);
         if (rc) return rc;
         if (s == sims) {   // last simulation: nothing left to select
             if (s == 0)

@@ -25,6 +25,7 @@
 
 #include "../../include/liuzhou_hip.h"
 #include "lz_net_dev.h"
+#include "lz_live_index.h"
 
 namespace {
 
@@ -130,6 +131,118 @@ int launch_net_multi(const NetParams& P, const MultiNets& M, int num_nets, const
     hipLaunchKernelGGL((net_forward_multi_kernel<C, S, W>), dim3(grid), dim3(K::THREADS), K::LDS_BYTES, st, P, M, num_nets,
                        packed, capacity, reinterpret_cast<const long long*>(seg_off), lp1, lp2, lpm, vlogits, value);
     return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
+}
+
+// ---- the gathering launch (lz_net_forward_packed_gather_f16) ---------------------------------------------------------------
+// The batch is not a list but the slots g of `packed` whose leaf_kind[g] == kLiveKind, evaluated in place: slot g's
+// outputs go to row g.  Every workgroup finds the live slots for itself (no communication between workgroups): it reads
+// all B flags (coalesced rounds of THREADS games, the loads of a group of rounds in flight together), each wave ballots
+// its 64 games into one mask word in LDS, and one wave turns the popcounts of the words into an exclusive prefix.  Row r
+// of the launch is then the r-th live slot in ascending order (lz_live_index.h); the pass loop is the plain kernel's
+// over those rows: before each pass S lanes look its S slots up and write them to a table of S ints (one workgroup
+// barrier; a look-up is ~10 dependent LDS reads, 0.7 us against the ~220 us of a pass).  Extra LDS behind
+// Cfg::LDS_BYTES: two slot tables (alternating, so that the stores at the end of a pass may still read theirs while the
+// next pass's is written), the live count, the masks, the prefix.
+constexpr int kLiveKind = 1;                        // lz_tree_dev.h: kLeafExpand
+constexpr int kGatherUnroll = 8;                    // rounds of flag loads in flight together, as in tree_live_scan_kernel
+template <int S> constexpr int gather_head_bytes() { return ((2 * S + 1) * 4 + 15) & ~15; }
+template <int C, int S, int W> constexpr int gather_lds_limit() { return (C == 64 && W == 4) ? 80 * 1024 : 160 * 1024; }
+template <int C, int S, int W>
+int64_t gather_lds_bytes(int64_t B) {                // whole dynamic LDS of a launch over B slots
+    const int64_t words = (B + 63) >> 6;
+    return Cfg<C, S, W>::LDS_BYTES + gather_head_bytes<S>() + words * 12;
+}
+
+template <int C, int S, int W>
+__global__ __launch_bounds__(W * 64, (C == 128 && W == 4) ? 1 : 2) void net_forward_gather_kernel(
+        NetParams P, const uint64_t* __restrict__ packed, const int* __restrict__ leaf_kind, int B,
+        unsigned long long* __restrict__ count_out, int even_rounds, float* __restrict__ lp1, float* __restrict__ lp2,
+        float* __restrict__ lpm, float* __restrict__ vlogits, float* __restrict__ value) {
+    using K = Cfg<C, S, W>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    NetCtx<C, S, W> ctx;
+    net_setup<C, S, W>(P, lds, ctx);
+    const int words = (B + 63) >> 6;
+    int* tab = reinterpret_cast<int*>(lds + K::LDS_BYTES);                 // [2][S] slots, then the live count
+    uint64_t* masks = reinterpret_cast<uint64_t*>(lds + K::LDS_BYTES + gather_head_bytes<S>());
+    int* prefix = reinterpret_cast<int*>(masks + words);
+    const int tid = ctx.tid, lane = ctx.lane, wave = ctx.wave;
+    const int rounds = (B + K::THREADS - 1) / K::THREADS;
+    for (int r0 = 0; r0 < rounds; r0 += kGatherUnroll) {
+        int kind[kGatherUnroll];
+#pragma unroll
+        for (int u = 0; u < kGatherUnroll; ++u) {
+            const int g = (r0 + u) * K::THREADS + tid;
+            kind[u] = g < B ? leaf_kind[g] : kLiveKind - 1;
+        }
+#pragma unroll
+        for (int u = 0; u < kGatherUnroll; ++u) {
+            const unsigned long long m = __ballot(kind[u] == kLiveKind);
+            const int w = (r0 + u) * W + wave;                             // games w * 64 .. w * 64 + 63
+            if (lane == 0 && w < words) masks[w] = m;
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {                                                       // exclusive prefix of the popcounts, 64 words a step
+        int run = 0;
+        for (int w0 = 0; w0 < words; w0 += 64) {
+            const int w = w0 + lane;
+            const int c = w < words ? lzlive::popc64(masks[w]) : 0;
+            int incl = c;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int v = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += v;
+            }
+            if (w < words) prefix[w] = run + incl - c;
+            run += __shfl(incl, 63, 64);
+        }
+        if (lane == 0) tab[2 * S] = run;
+    }
+    __syncthreads();
+    const int n = __builtin_amdgcn_readfirstlane(tab[2 * S]);
+    if (blockIdx.x == 0 && tid == 0) *count_out = (unsigned long long)n;
+    const int n_pass = (n + S - 1) / S;
+    // even rounds: the same number of rounds on the fewest workgroups that need no round more -- the CUs of a partial
+    // last round would idle anyway, and the chip at its power limit runs the others faster without them (n = 12 337:
+    // 1 543 passes are seven rounds of 221 workgroups instead of six of 256 and one of 7)
+    int stride = gridDim.x;
+    if (even_rounds && n_pass > 0) {
+        const int r = (n_pass + stride - 1) / stride;
+        stride = (n_pass + r - 1) / r;
+    }
+    if ((int)blockIdx.x >= stride) return;
+    int par = 0;
+    for (int pass = blockIdx.x; pass < n_pass; pass += stride, par ^= 1) {
+        const int n0 = pass * S;
+        const int nvalid = (n - n0) < S ? (n - n0) : S;
+        int* slot_tab = tab + par * S;
+        if (tid < S) slot_tab[tid] = tid < nvalid ? lzlive::row_to_game(masks, prefix, words, n0 + tid) : 0;
+        __syncthreads();
+        net_pass<C, S, W, true>(P, lds, ctx, nullptr, packed, 0, nvalid, lp1, lp2, lpm, vlogits, value, nullptr, slot_tab);
+    }
+}
+
+template <int C, int S, int W>
+int launch_net_gather(const NetParams& P, const uint64_t* packed, const int* leaf_kind, int64_t B,
+                      unsigned long long* count_out, int even_rounds, float* lp1, float* lp2, float* lpm, float* vlogits,
+                      float* value, int max_blocks, hipStream_t st) {
+    using K = Cfg<C, S, W>;
+    const int64_t lds = gather_lds_bytes<C, S, W>(B);
+    if (lds > gather_lds_limit<C, S, W>()) return LZ_ERR_UNSUPPORTED;
+    const int64_t n_pass = (B + S - 1) / S;
+    int grid = (int)(n_pass < max_blocks ? n_pass : max_blocks);
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL((net_forward_gather_kernel<C, S, W>), dim3(grid), dim3(K::THREADS), (size_t)lds, st, P, packed,
+                       leaf_kind, (int)B, count_out, even_rounds, lp1, lp2, lpm, vlogits, value);
+    return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
+}
+
+template <int C, int S, int W>
+int configure_net_gather() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(net_forward_gather_kernel<C, S, W>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, gather_lds_limit<C, S, W>()) == hipSuccess
+               ? LZ_OK : LZ_ERR_LAUNCH;
 }
 
 template <int C, int S, int W>
@@ -287,7 +400,9 @@ int lz_net_configure(void) {
               e = configure_net<128, 8, 4>();
     const int ma = configure_net_multi<64, 16, 8>(), mb = configure_net_multi<128, 8, 8>(),
               mc = configure_net_multi<64, 8, 4>(), me = configure_net_multi<128, 8, 4>();
-    for (int rc : {a, b, c, e, ma, mb, mc, me})
+    const int ga = configure_net_gather<64, 16, 8>(), gb = configure_net_gather<128, 8, 8>(),
+              gc = configure_net_gather<64, 8, 4>(), ge = configure_net_gather<128, 8, 4>();
+    for (int rc : {a, b, c, e, ma, mb, mc, me, ga, gb, gc, ge})
         if (rc != LZ_OK) return rc;
     return LZ_OK;
 }
@@ -357,6 +472,65 @@ int lz_net_forward_packed_counted_f16(const LzNetDesc* d, const void* packed_sta
     if (!count) return LZ_ERR_ARG;
     return net_forward_impl(d, nullptr, reinterpret_cast<const uint64_t*>(packed_states), capacity, lp1, lp2, lpmc,
                             value_logits, value, stream, count);
+}
+
+// Does a launch of num_slots slots of this network fit the gathering kernel?  (internal: lz_tree_search asks before it
+// chooses its path)
+static int net_gather_shape(const LzNetDesc* d, int64_t num_slots) {
+    if (d->flags & (4 | 8)) return LZ_ERR_UNSUPPORTED;
+    if (d->channels != 64 && d->channels != 128) return LZ_ERR_UNSUPPORTED;
+    if (num_slots > (int64_t)INT32_MAX - 1024) return LZ_ERR_UNSUPPORTED;
+    const bool half_wg = d->channels == 64 && (d->flags & 1), wide = d->channels == 128 && (d->flags & 2);
+    const int64_t need = d->channels == 64 ? (half_wg ? gather_lds_bytes<64, 8, 4>(num_slots) : gather_lds_bytes<64, 16, 8>(num_slots))
+                                           : (wide ? gather_lds_bytes<128, 8, 4>(num_slots) : gather_lds_bytes<128, 8, 8>(num_slots));
+    const int64_t limit = half_wg ? gather_lds_limit<64, 8, 4>() : gather_lds_limit<128, 8, 8>();
+    return need <= limit ? LZ_OK : LZ_ERR_UNSUPPORTED;
+}
+int lz_net_gather_supported(const LzNetDesc* d, int64_t num_slots) {
+    return d && num_slots > 0 && net_gather_shape(d, num_slots) == LZ_OK;
+}
+/* internal: workgroups and samples per pass of a launch of this network (the gate of lz_tree_search) */
+void lz_net_launch_shape(const LzNetDesc* d, int* max_blocks, int* samples) {
+    const bool half_wg = d->channels == 64 && (d->flags & 1);
+    *max_blocks = d->max_blocks > 0 ? d->max_blocks : (half_wg ? 512 : 256);
+    *samples = d->channels == 64 && !half_wg ? 16 : 8;
+}
+
+int lz_net_forward_packed_gather_f16(const LzNetDesc* d, const void* packed_states, const int32_t* leaf_kind,
+                                     int64_t num_slots, int64_t* count_out, float* lp1, float* lp2, float* lpmc,
+                                     float* value_logits, float* value, void* stream) {
+    if (!d || num_slots < 0) return LZ_ERR_ARG;
+    if (num_slots == 0) return LZ_OK;
+    if (!d->wfrag || !d->fparams || !packed_states || !leaf_kind || !count_out) return LZ_ERR_ARG;
+    const bool heads = lp1 && lp2 && lpmc;
+    if (!heads && (lp1 || lp2 || lpmc || !value)) return LZ_ERR_ARG;     // all three policy outputs, or values only
+    if (d->blocks < 0 || d->blocks > (LZ_NET_MAX_LAYERS - 2) / 2 || d->num_layers != 2 + 2 * d->blocks) return LZ_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d->wfrag) & 15) || (reinterpret_cast<uintptr_t>(d->fparams) & 15)) return LZ_ERR_ALIGN;
+    const int src = net_gather_shape(d, num_slots);
+    if (src) return src;
+    NetParams P = make_net_params(d);
+    P.debug_stop = getenv("LZ_NET_DEBUG_STOP") ? atoi(getenv("LZ_NET_DEBUG_STOP")) : 0;
+    const char* ev = getenv("LZ_NET_EVEN_ROUNDS");                       // on unless 0 (A/B runs)
+    const int even_rounds = ev && ev[0] == '0' ? 0 : 1;
+    const bool half_wg = d->channels == 64 && (d->flags & 1);
+    const bool wide = d->channels == 128 && (d->flags & 2);
+    const int max_blocks = d->max_blocks > 0 ? d->max_blocks : (half_wg ? 512 : 256);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t* packed = reinterpret_cast<const uint64_t*>(packed_states);
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(count_out);
+    const bool prof = g_prof.on && g_prof.used < NetProf::kMax;
+    if (prof) (void)hipEventRecord(g_prof.ev[2 * g_prof.used], st);
+    const int rc = d->channels == 64
+                       ? (half_wg ? launch_net_gather<64, 8, 4>(P, packed, leaf_kind, num_slots, cnt, even_rounds, lp1, lp2, lpmc,
+                                                                value_logits, value, max_blocks, st)
+                                  : launch_net_gather<64, 16, 8>(P, packed, leaf_kind, num_slots, cnt, even_rounds, lp1, lp2, lpmc,
+                                                                 value_logits, value, max_blocks, st))
+                       : (wide ? launch_net_gather<128, 8, 4>(P, packed, leaf_kind, num_slots, cnt, even_rounds, lp1, lp2, lpmc,
+                                                              value_logits, value, max_blocks, st)
+                               : launch_net_gather<128, 8, 8>(P, packed, leaf_kind, num_slots, cnt, even_rounds, lp1, lp2, lpmc,
+                                                              value_logits, value, max_blocks, st));
+    if (prof) { (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], st); g_prof.used += 1; g_prof.evals += num_slots; }
+    return rc;
 }
 
 // Networks that may share one launch: the same kernel shape and the same layout of both buffers -- everything but the

@@ -588,10 +588,16 @@ __device__ __forceinline__ void net_use_weights(const NetParams& P, NetCtx<C, S,
 // kernel -- the leaf states the tree step wrote are visible); ends without one.  Outputs go to global memory.
 // `fp_net` (multi-network launch): this pass's float parameters instead of P.fp; ctx.rw / ctx.rf are then that network's
 // descriptors too (net_use_weights).  nullptr everywhere else, which folds away.
-template <int C, int S, int W>
+// GATHER (net_forward_gather_kernel): sample s is not row n0 + s but slot slot_tab[s] of the caller's arrays, for the
+// record it reads and for every output it writes; slot_tab is a table of S ints in LDS, filled (and made visible by a
+// workgroup barrier) before the call and left alone until the pass after the next one begins (a pass ends without a
+// barrier: its last stores still read the table).  The slot is re-read from LDS at each use: nothing of it is kept in
+// registers across the trunk.  n0 is unused then.
+template <int C, int S, int W, bool GATHER = false>
 __device__ __forceinline__ void net_pass(const NetParams& P, unsigned char* lds, NetCtx<C, S, W>& ctx, const float* planes,
                                          const uint64_t* packed, int64_t n0, int nvalid, float* lp1, float* lp2,
-                                         float* lpm, float* vlogits, float* value, const float* fp_net = nullptr) {
+                                         float* lpm, float* vlogits, float* value, const float* fp_net = nullptr,
+                                         const int* slot_tab = nullptr) {
     using K = Cfg<C, S, W>;
     constexpr int NW = K::CTW;
     using Acc = AccT<NW>;
@@ -615,7 +621,7 @@ __device__ __forceinline__ void net_pass(const NetParams& P, unsigned char* lds,
     const int st_s = tid_s >> 5, st_p = tid_s & 31;
     uint64_t rec0 = 0, rec1 = 0, rec2 = 0, rec3 = 0;
     if (packed != nullptr && st_s < nvalid) {
-        const uint64_t* rec = packed + (n0 + st_s) * 4;
+        const uint64_t* rec = packed + (GATHER ? (int64_t)slot_tab[st_s] : n0 + st_s) * 4;
         rec0 = rec[0]; rec1 = rec[1]; rec2 = rec[2]; rec3 = rec[3];
     }
 #ifdef LZ_EXP_HEAD_STAMPS
@@ -881,7 +887,7 @@ __device__ __forceinline__ void net_pass(const NetParams& P, unsigned char* lds,
             const int s = row / 3, h = row - s * 3;
             if (on && s < nvalid) {
                 const float lse = mx + logf(e);
-                float* dst = (h == 0 ? lp1 : h == 1 ? lp2 : lpm) + (n0 + s) * 36 + 4 * k4;
+                float* dst = (h == 0 ? lp1 : h == 1 ? lp2 : lpm) + (GATHER ? (int64_t)slot_tab[s] : n0 + s) * 36 + 4 * k4;
                 dst[0] = v[0] - lse; dst[1] = v[1] - lse; dst[2] = v[2] - lse; dst[3] = v[3] - lse;
             }
         }
@@ -967,10 +973,19 @@ __device__ __forceinline__ void net_pass(const NetParams& P, unsigned char* lds,
         for (int i = 0; i < SPW; ++i) {
             const int s = wave + i * K::WAVES;
             if (s < nvalid) {
+                if constexpr (GATHER) {
+                    const int64_t r = slot_tab[s];
+                    if (lane_h == 0 && value != nullptr) value[r] = ex[i] / sum[i];
+                    if (vlogits != nullptr) {
+                        vlogits[r * kBins + lane_h] = v0[i];
+                        if (lane_h + 64 < kBins) vlogits[r * kBins + lane_h + 64] = v1[i];
+                    }
+                } else {
                 if (lane_h == 0 && value != nullptr) value[n0 + s] = ex[i] / sum[i];
                 if (vlogits != nullptr) {
                     vlogits[(n0 + s) * kBins + lane_h] = v0[i];
                     if (lane_h + 64 < kBins) vlogits[(n0 + s) * kBins + lane_h + 64] = v1[i];
+                }
                 }
             }
         }
