@@ -43,18 +43,8 @@ def _frag_conv(w: torch.Tensor, k_pad: int, lo: bool = False) -> torch.Tensor:
     wp = torch.zeros((co, k_pad, kh, kw), dtype=torch.float64)
     wp[:, :ci] = w
     kb_n, ct_n = k_pad // 32, co // 16
-    lane = torch.arange(64)
-    row = lane & 15
-    kbase = 8 * (lane >> 4)
-    j = torch.arange(8)
-    out = torch.empty((taps, kb_n, ct_n, 64, 8), dtype=torch.float64)
-    for t in range(taps):
-        ky, kx = divmod(t, kw)
-        for kb in range(kb_n):
-            for ct in range(ct_n):
-                cos = (16 * ct + row).view(64, 1).expand(64, 8)
-                cis = (32 * kb + kbase.view(64, 1) + j.view(1, 8))
-                out[t, kb, ct] = wp[cos, cis, ky, kx]
+    # lane l = 16 * q + row holds W[16 * ct + row][32 * kb + 8 * q + j]: one permutation of the axes per layer
+    out = wp.reshape(ct_n, 16, kb_n, 4, 8, taps).permute(5, 2, 0, 3, 1, 4).reshape(taps, kb_n, ct_n, 64, 8)
     if lo:
         return ((out - out.to(torch.float16).to(torch.float64)) * float(1 << LO_SHIFT)).to(torch.float16)
     return out.to(torch.float16)
@@ -67,13 +57,8 @@ def _frag_conv_f32(w: torch.Tensor, k_pad: int) -> torch.Tensor:
     co, ci, kh, kw = w.shape
     wp = torch.zeros((co, k_pad, kh, kw), dtype=torch.float64)
     wp[:, :ci] = w
-    lane = torch.arange(64)
-    out = torch.empty((kh * kw, k_pad // 4, co // 16, 64), dtype=torch.float64)
-    for t in range(kh * kw):
-        ky, kx = divmod(t, kw)
-        for kb in range(k_pad // 4):
-            for ct in range(co // 16):
-                out[t, kb, ct] = wp[16 * ct + (lane & 15), 4 * kb + (lane >> 4), ky, kx]
+    taps = kh * kw
+    out = wp.reshape(co // 16, 16, k_pad // 4, 4, taps).permute(4, 2, 0, 3, 1).reshape(taps, k_pad // 4, co // 16, 64)
     return out.to(torch.float32)
 
 

@@ -18,6 +18,20 @@ def states(z, prefix):
     return {f: z[f"{prefix}_{f}"] for f in FIELDS}
 
 
+def perturb_bn(m, seed):
+    """Non-trivial BatchNorm statistics and affine parameters, drawn from `seed`, for every BatchNorm2d of `m` (as in
+    test_fused_net_matches_fp32_model): folding is exercised at every layer.  Returns `m`."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    for mod in m.modules():
+        if isinstance(mod, torch.nn.BatchNorm2d):
+            mod.running_mean.copy_(torch.randn(mod.running_mean.shape, generator=g) * 0.1)
+            mod.running_var.copy_(torch.rand(mod.running_var.shape, generator=g) * 0.5 + 0.75)
+            mod.weight.data.copy_(torch.rand(mod.weight.shape, generator=g) * 0.5 + 0.75)
+            mod.bias.data.copy_(torch.randn(mod.bias.shape, generator=g) * 0.1)
+    return m
+
+
 def unpack_mask(packed, width):
     return np.unpackbits(packed, axis=1)[:, :width].astype(bool)
 

@@ -1,10 +1,13 @@
 """CPU: BN folding + MFMA fragment packing of the network (liuzhou_amd/net_pack.py) reproduce the model."""
+import copy
+
 import numpy as np
+import pytest
 import torch
 
 from liuzhou_amd.net import ChessNet, MODEL_CONFIGS, bucket_logits_to_scalar
 from liuzhou_amd.net_pack import pack_model, emulate
-from tests.golden_utils import load
+from tests.golden_utils import load, perturb_bn
 
 
 def _model(name, seed):
@@ -35,6 +38,27 @@ def test_pack_emulation_matches_model_b6c64():
     assert float((out[4] - val_ref).abs().max()) < 5e-3
     # and golden outputs of the reference's ChessNet for the same seed
     np.testing.assert_allclose(out[0].numpy(), z["b6c64_lp1"], atol=2e-2, rtol=0)
+
+
+@pytest.mark.parametrize("blocks", [0, 1, 47])
+def test_pack_emulation_matches_float64_model_at_the_depth_limits(blocks):
+    """No residual block, one, and the 47 that fill the descriptor's 96 layer offsets: folding + fragment order + the layer
+    offsets reproduce the module in float64 (fp32 activations; the weights are fp16-rounded, hence the file's 2e-2:
+    observed 2.4e-5, 2.5e-5 and 1.3e-4 on the log-probs)."""
+    torch.manual_seed(11)
+    m = perturb_bn(ChessNet(trunk_channels=64, num_blocks=blocks), 100 + blocks).eval()
+    pack = pack_model(m)
+    assert len(pack.layer_offsets) == 2 + 2 * blocks == {0: 2, 1: 4, 47: 96}[blocks]
+    assert ("b0_a1" in pack.foff) == (blocks > 0)
+    x = torch.from_numpy(load("g9_net.npz")["inputs"].astype(np.float32))[:24]
+    with torch.inference_mode():
+        ref = copy.deepcopy(m).double()(x.double())
+        val_ref = bucket_logits_to_scalar(ref[3])
+    out = emulate(pack, x, half_activations=False)
+    errs = [float((got.double() - want).abs().max()) for got, want in zip(out[:3], ref[:3])]
+    print(f"64 x {blocks}: emulation vs float64 module, max |dlog-prob| {max(errs):.2e}")
+    assert max(errs) < 2e-2
+    assert float((out[4].double() - val_ref).abs().max()) < 5e-3
 
 
 def test_pack_layout_sizes():
