@@ -564,6 +564,36 @@ typedef struct LzTreeDesc {
     int32_t* gumbel_count;         /* [B] optional: += 1 for every search whose root step ran the rule */
     int64_t  gumbel_stride;        /* row stride of gumbel_g / gumbel_gl / gumbel_base, >= 72; a child at or beyond it has
                                       gl = -inf and N0 = 0 */
+    /* Optional MCTS-Solver (Winands, Bjornsson, Saito 2008; solver == 0 = off: nothing below is read or written).  Exact
+     * results are marked on the edges and carried up the tree as far as they decide the parent.
+     *   An edge e from node X (mover mX) to a child state with mover mc is DECIDED when it is terminal (info bit 1: the game
+     *   is over there, or the child has no legal move) or PROVEN (info bit 4).  Either way info bits 2..3 hold d(e) + 1 with
+     *   d(e) in {-1, 0, +1} from mc's view; x(e) = d(e) if mc == mX, else -d(e) (the mover may stay the same along an edge).
+     *   Node rule R(X) over X's edges: a decided edge with x = +1 -> X is proven +1; otherwise, every edge decided -> X is
+     *   proven max x (0 or -1); otherwise X is undecided.
+     *   Marking (the expand + backup step; the value a simulation backs up does not change, only later descents see the
+     *   marks): a leaf expanded into a node X -- shared leaves included, a refused expansion not -- evaluates R(X) on the
+     *   edge records it has just written; a proven X gets the proven bit and its value on its incoming edge (one atomic OR on
+     *   n_info: the value bits of a non-terminal edge are 0).  That, or a leaf marked terminal -1 because it has no legal
+     *   move, is a new decision on path entry j; the node that owns that edge (the root for j == 0, else the child node of
+     *   path entry j - 1) is then evaluated with R, and if it is proven, path entry j - 1 -- or root_proven for j == 0 -- is
+     *   marked and the climb repeats one level up.  Two dependent loads per level, only in simulations that decide something.
+     *   root_proven[g]: 0 unknown, 1 lost, 2 drawn, 3 won for the root's mover.  Set from R(root) at the root step (a fresh
+     *   root's expansion, a kept root's existing edges) and by the climb; lz_tree_begin and lz_tree_advance clear it.
+     *   lz_tree_advance moves n_info whole: proofs survive it, also on an edge whose subtree was pruned away.
+     *   Selection, on the levels PUCT decides (a root level under the forced-playout or Gumbel rule keeps that rule): a child
+     *   decided with x = +1 is taken, lowest index first, without score arithmetic; otherwise the candidates are the children
+     *   not decided with x = -1 (all children if there is none), scored as always but with q(k) = x(k) for a decided child at
+     *   any visit count, in double, lowest index among equals.  A descent that takes a decided edge, on any level, ends there
+     *   as a terminal leaf with the value of bits 2..3: it needs no evaluation and leaves the compact and gathering lists.
+     *   With the solver on a search runs the one-wave step whatever the launch size (the two-waves-per-game step is not used).
+     * Honoured by lz_tree_select, lz_tree_expand, lz_tree_search / _continue (dense, list and gathering launches) and
+     * lz_tree_solver_pick; the wave, multi-network and persistent searches refuse a descriptor with solver != 0
+     * (LZ_ERR_UNSUPPORTED). */
+    int32_t  solver;               /* 0 = off */
+    int32_t* root_proven;          /* [B] required when solver != 0 */
+    int32_t* solver_count;         /* [B] optional: += 1 for every edge the expand step marks (proven, or terminal for want of
+                                      a legal move) and every root result it sets */
 } LzTreeDesc;
 LZ_API int64_t lz_tree_desc_bytes(void);
 
@@ -669,6 +699,15 @@ LZ_API int lz_tree_finish_gumbel(const LzTreeDesc* tree, const float* temperatur
                                  int32_t* child_count, int32_t* child_action, int32_t* child_visits,
                                  float* child_prior, int64_t out_cap, double* gumbel_score, double* gumbel_vmix,
                                  void* stream);
+/* MCTS-Solver pick (LzTreeDesc.solver != 0; launched after whichever lz_tree_finish* ran, same stream).  For a game with a
+ * non-terminal root and force_uniform[g] == 0 (or force_uniform == NULL), with x(k) of the root's decided children:
+ *   children with x = +1 exist: the pick becomes the one with the most visits, lowest edge index among equals;
+ *   otherwise, if the finish picked a child decided with x = -1 and a child not so decided exists: the most visited of
+ *   those, lowest edge index among equals.
+ * Touches only chosen_index, chosen_code and chosen_valid; overrides [B] (optional) += 1 where the pick changed.  With
+ * solver == 0 it launches nothing. */
+LZ_API int lz_tree_solver_pick(const LzTreeDesc* tree, const uint8_t* force_uniform, int32_t* chosen_index,
+                               int32_t* chosen_code /*[B,4]*/, uint8_t* chosen_valid, int32_t* overrides, void* stream);
 /* One whole search enqueued from C++: begin, root evaluation + expansion, then `sims` x
  * (select -> planes -> fused network -> expand + backup).  No host synchronisation; capturable. */
 LZ_API int lz_tree_search(const LzTreeDesc* tree, const LzNetDesc* net, int64_t sims, float* planes /*[B,11,36]*/,

@@ -85,11 +85,12 @@ __global__ __launch_bounds__(kBlock) void pos_clear_kernel(int* __restrict__ tab
 // instantiations never read it.
 // GUMBEL (here and in the expand + select kernels): the Gumbel root search (`ga`, tree_select); likewise never read by the
 // other instantiations.
-template <bool FORCED = false, bool GUMBEL = false>
+// SOLVER (here and in the expand / expand + select kernels): the MCTS-Solver (`sv`, tree_select / tree_expand); likewise.
+template <bool FORCED = false, bool GUMBEL = false, bool SOLVER = false>
 __global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t, ForcedArgs fa, GumbelArgs ga) {
     const int g = wave_game();
     if (g >= t.B) return;
-    tree_select<FORCED, GUMBEL>(t, g, lane_id(), load_root_info(t, g), -1, -1, nullptr, FORCED ? fa.k : 0.0, fa.count,
+    tree_select<FORCED, GUMBEL, SOLVER>(t, g, lane_id(), load_root_info(t, g), -1, -1, nullptr, FORCED ? fa.k : 0.0, fa.count,
                                 &ga, GUMBEL);
 }
 // the root step's snapshot as a launch of its own (lz_tree_expand with is_root: the step-by-step protocol)
@@ -107,23 +108,23 @@ __global__ __launch_bounds__(kBlock) void gumbel_root_kernel(Tree t, GumbelArgs 
 // CAP (here and in the expand + select kernels): the playout cap's per-game budgets and root noise switch (`cap`); the
 // default instantiations never read them.  A fast search (root_noise[g] == 0) gets no mix at all: neither on a fresh
 // root nor on a kept one.
-template <bool IS_ROOT, bool COMPACT = false, bool CAP = false>
+template <bool IS_ROOT, bool COMPACT = false, bool CAP = false, bool SOLVER = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_kernel(Tree t, const float* __restrict__ lp1,
                                                              const float* __restrict__ lp2,
                                                              const float* __restrict__ lpm,
                                                              const float* __restrict__ priors220,
                                                              const float* __restrict__ values,
                                                              const float* __restrict__ noise, int noise_stride,
-                                                             float epsilon, int step, CapArrays cap) {
+                                                             float epsilon, int step, CapArrays cap, SolverArgs sv) {
     LZ_EXPAND_SCRATCH(sc);
     const int g = wave_game();
     if (g >= t.B) return;
     ptrdiff_t o = 0;
     if (COMPACT) o = (ptrdiff_t)(t.leaf_kind[g] == kLeafExpand ? t.live_row[g] : 0) - g;
     if (CAP && IS_ROOT && !cap_noise(cap, g)) noise = nullptr;
-    tree_expand<IS_ROOT>(t, g, lane_id(), lp1 ? lp1 + o * 36 : nullptr, lp2 ? lp2 + o * 36 : nullptr,
-                         lpm ? lpm + o * 36 : nullptr, priors220 ? priors220 + o * 220 : nullptr, values + o, noise,
-                         noise_stride, epsilon, sc, nullptr, step);
+    tree_expand<IS_ROOT, 0, SOLVER>(t, g, lane_id(), lp1 ? lp1 + o * 36 : nullptr, lp2 ? lp2 + o * 36 : nullptr,
+                                    lpm ? lpm + o * 36 : nullptr, priors220 ? priors220 + o * 220 : nullptr, values + o,
+                                    noise, noise_stride, epsilon, sc, nullptr, step, nullptr, nullptr, &sv);
 }
 
 // The leaves that need the network (leaf_kind == kLeafExpand: fresh roots, leaves to expand -- not terminal leaves, kept
@@ -252,14 +253,15 @@ __global__ __launch_bounds__(kScanBlock) void tree_live_scan_seg_kernel(Tree t, 
 // expand + backup of simulation s fused with the selection of simulation s+1 (same wave, same game: the edge
 // records it just touched are still in L1/L2) -- one launch per simulation besides the network kernel.
 // (forcing 8 waves / SIMD -- <= 96 SGPRs, 126 scalar spills -- was measured: no gain at 16 384 games, 1 % slower at C2)
-template <bool IS_ROOT, bool COMPACT = false, bool CAP = false, bool FORCED = false, bool GUMBEL = false>
+template <bool IS_ROOT, bool COMPACT = false, bool CAP = false, bool FORCED = false, bool GUMBEL = false,
+          bool SOLVER = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, const float* __restrict__ lp1,
                                                                     const float* __restrict__ lp2,
                                                                     const float* __restrict__ lpm,
                                                                     const float* __restrict__ values,
                                                                     const float* __restrict__ noise, int noise_stride,
                                                                     float epsilon, int step, CapArrays cap,
-                                                                    ForcedArgs fa, GumbelArgs ga) {
+                                                                    ForcedArgs fa, GumbelArgs ga, SolverArgs sv) {
 #ifndef LZ_EXP_NO_TREE_PRIO
     // The kernel is a chain of dependent loads with a few dozen instructions in between; in the two-stream search it
     // shares the SIMDs with the other half's network waves, which always have MFMAs to issue.  Raised wave priority
@@ -277,8 +279,8 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
     const unsigned long long lz_t0 = __builtin_readcyclecounter();
 #endif
     if (CAP && IS_ROOT && !cap_noise(cap, g)) noise = nullptr;
-    tree_expand<IS_ROOT>(t, g, lane, lp1 + o * 36, lp2 + o * 36, lpm + o * 36, nullptr, values + o, noise, noise_stride,
-                         epsilon, sc, &root, step, nullptr, nullptr LZ_TSTAMP_PASS);
+    tree_expand<IS_ROOT, 0, SOLVER>(t, g, lane, lp1 + o * 36, lp2 + o * 36, lpm + o * 36, nullptr, values + o, noise,
+                                    noise_stride, epsilon, sc, &root, step, nullptr, nullptr, &sv LZ_TSTAMP_PASS);
     __threadfence_block();
     // Gumbel search: the games whose root-noise switch is on, as with forced playouts; the root step records gl, N0, v0
     const bool gum_on = GUMBEL && (!CAP || cap_noise(cap, g));
@@ -291,7 +293,7 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
     LZ_TSTAMP(g, 7)                                            // fence (+ root reload)
     // forced playouts: the games whose root-noise switch is on (every game without the cap, the full searches with it)
     const double fk = FORCED && (!CAP || cap_noise(cap, g)) ? fa.k : 0.0;
-    tree_select<FORCED, GUMBEL>(t, g, lane, root, -1, -1, nullptr, fk, fa.count, &ga, gum_on LZ_TSTAMP_PASS);
+    tree_select<FORCED, GUMBEL, SOLVER>(t, g, lane, root, -1, -1, nullptr, fk, fa.count, &ga, gum_on LZ_TSTAMP_PASS);
 #ifdef LZ_EXP_TREE_STAMPS
     LZ_TADD(g, 19, 1)
 #endif
@@ -1209,6 +1211,61 @@ __global__ __launch_bounds__(kBlock) void tree_finish_gumbel_kernel(Tree t, Gumb
     }
 }
 
+// MCTS-Solver pick (lz_tree_solver_pick), launched behind whichever finish kernel ran: a proven win is played, a proven loss
+// is not while another move exists.  One wave per game; only chosen_index / chosen_code / chosen_valid are touched.
+__global__ __launch_bounds__(kBlock) void tree_solver_pick_kernel(Tree t, const uint8_t* __restrict__ force_uniform,
+                                                                  int* __restrict__ chosen_index,
+                                                                  int4* __restrict__ chosen_code,
+                                                                  uint8_t* __restrict__ chosen_valid,
+                                                                  int* __restrict__ overrides) {
+    const int lane = lane_id();
+    const int g = wave_game();
+    if (g >= t.B) return;
+    if (force_uniform != nullptr && force_uniform[g] != 0) return;   // opening random move: kept
+    const RootInfo root = load_root_info(t, g);
+    if (t.root_terminal[g] != 0 || root.ne <= 0) return;
+    const int picked = chosen_index[g];
+    int n[2], act[2]; bool ok[2], win[2], lose[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int k = r * kWave + lane;
+        ok[r] = k < root.ne;
+        const Edge e = load_edge(&t.edges[(size_t)(root.e0 + (ok[r] ? k : 0))]);
+        const uint8_t inf = edge_info(e.n_info);
+        const bool dec = ok[r] && (inf & kInfoDecided) != 0;
+        const int x = solver_x(inf, root.player);
+        n[r] = ok[r] ? edge_n(e.n_info) : -1;
+        act[r] = ok[r] ? (int)e.act : -1;
+        win[r] = dec && x > 0;
+        lose[r] = dec && x < 0;
+    }
+    bool cand[2];
+    if (__ballot(win[0] || win[1]) != 0ull) { cand[0] = win[0]; cand[1] = win[1]; }
+    else {
+        const bool picked_lost = (ok[0] && act[0] == picked && lose[0]) || (ok[1] && act[1] == picked && lose[1]);
+        cand[0] = ok[0] && !lose[0]; cand[1] = ok[1] && !lose[1];
+        if (__ballot(picked_lost) == 0ull || __ballot(cand[0] || cand[1]) == 0ull) return;
+    }
+    // most visits among the candidates (counts are below 2^24: exact in fp32), lowest edge index among equals
+    const float nmax = lzw::wave_max(fmaxf(cand[0] ? (float)n[0] : -1.f, cand[1] ? (float)n[1] : -1.f));
+    const uint64_t lo = __ballot(cand[0] && (float)n[0] == nmax);
+    int pick = -1;
+    if (lo) pick = __ffsll((unsigned long long)lo) - 1;
+    else { const uint64_t hi = __ballot(cand[1] && (float)n[1] == nmax); if (hi) pick = kWave + __ffsll((unsigned long long)hi) - 1; }
+    if (pick >= 0 && lane == (pick & 63)) {
+        const int a = pick >= kWave ? act[1] : act[0];
+        if (a != picked) {
+            const State rs = unpack(root.state);
+            int kd, p, q2, ex;
+            index_to_code(rs.phase, a, kd, p, q2, ex);
+            chosen_index[g] = a;
+            chosen_code[g] = make_int4(kd, p, q2, ex);
+            chosen_valid[g] = 1;
+            if (overrides != nullptr) overrides[g] += 1;            // this game's wave is the only writer
+        }
+    }
+}
+
 // =================================================================================================================
 // Fused root-PUCT search (variant R, v1/python/mcts_gpu.py:1249-1457) on packed states: the host op chain
 // encode -> project -> root_pack -> noise -> batch_apply_moves -> ... with data-dependent shapes and two host syncs
@@ -1514,24 +1571,47 @@ int lz_tree_begin(const LzTreeDesc* d, void* stream) {
         hipLaunchKernelGGL(pos_clear_kernel, dim3(1024), dim3(kBlock), 0, as_stream(stream), t.pos_index,
                            (int64_t)t.B * t.pos_slots);
     hipLaunchKernelGGL(tree_begin_kernel, dim3(gt(d->num_games)), dim3(kBlock), 0, as_stream(stream), t);
+    if (solver_set(d) && d->root_proven &&                          // MCTS-Solver: a fresh tree has no root result
+        hipMemsetAsync(d->root_proven, 0, (size_t)d->num_games * sizeof(int32_t), as_stream(stream)) != hipSuccess)
+        return LZ_ERR_LAUNCH;
     return st();
+}
+
+// the select kernel of the descriptor's root-level rule (forced playouts, Gumbel or neither), with or without the solver
+extern "C++" template <bool SOLVER>
+static void tree_select_launch(const LzTreeDesc* d, void* stream) {
+    const Tree t = no_share(make_tree(d));
+    const dim3 grid(gw(d->num_games)), block(kBlock);
+    if (gumbel_set(d))
+        hipLaunchKernelGGL((tree_select_kernel<false, true, SOLVER>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, make_gumbel(d));
+    else if (forced_set(d))
+        hipLaunchKernelGGL((tree_select_kernel<true, false, SOLVER>), grid, block, 0, as_stream(stream), t, make_forced(d), GumbelArgs{});
+    else
+        hipLaunchKernelGGL((tree_select_kernel<false, false, SOLVER>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, GumbelArgs{});
 }
 
 int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (!tree_ok(d)) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: lz_tree_search only
     if (const int rc = gumbel_check(d)) return rc;
+    if (const int rc = solver_check(d)) return rc;
     if (d->num_games == 0) return LZ_OK;
-    if (gumbel_set(d))
-        hipLaunchKernelGGL((tree_select_kernel<false, true>), dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream),
-                           no_share(make_tree(d)), ForcedArgs{}, make_gumbel(d));
-    else if (forced_set(d))
-        hipLaunchKernelGGL(tree_select_kernel<true>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream),
-                           no_share(make_tree(d)), make_forced(d), GumbelArgs{});
-    else
-        hipLaunchKernelGGL(tree_select_kernel<false>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream),
-                           no_share(make_tree(d)), ForcedArgs{}, GumbelArgs{});
+    if (solver_set(d)) tree_select_launch<true>(d, stream);
+    else tree_select_launch<false>(d, stream);
     return st();
+}
+
+// the stand-alone expand (+ backup) kernel of a step, with or without the solver
+extern "C++" template <bool SOLVER>
+static void tree_expand_launch(const Tree& t, int is_root, const float* lp1, const float* lp2, const float* lpmc,
+                               const float* priors220, const float* values, const float* noise, int64_t noise_stride,
+                               float epsilon, const SolverArgs& sv, void* stream) {
+    if (is_root)
+        hipLaunchKernelGGL((tree_expand_kernel<true, false, false, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                           t, lp1, lp2, lpmc, priors220, values, noise, (int)noise_stride, epsilon, -1, CapArrays{}, sv);
+    else
+        hipLaunchKernelGGL((tree_expand_kernel<false, false, false, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                           t, lp1, lp2, lpmc, priors220, values, (const float*)nullptr, 0, 0.f, -1, CapArrays{}, sv);
 }
 
 int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const float* lp2, const float* lpmc,
@@ -1541,18 +1621,17 @@ int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const flo
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
     if (!priors220 && (!lp1 || !lp2 || !lpmc)) return LZ_ERR_ARG;
     if (const int rc = gumbel_check(d)) return rc;
+    if (const int rc = solver_check(d)) return rc;
     if (d->num_games == 0) return LZ_OK;
     const Tree t = no_share(make_tree(d));
-    if (is_root) {
-        if (gumbel_set(d)) noise = nullptr;                        // a Gumbel search never mixes Dirichlet noise in
-        hipLaunchKernelGGL(tree_expand_kernel<true>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                           lpmc, priors220, values, noise, (int)noise_stride, epsilon, -1, CapArrays{});
-        if (gumbel_set(d))
-            hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, make_gumbel(d),
-                               (const uint8_t*)nullptr);
-    } else
-        hipLaunchKernelGGL(tree_expand_kernel<false>, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                           lpmc, priors220, values, nullptr, 0, 0.f, -1, CapArrays{});
+    if (is_root && gumbel_set(d)) noise = nullptr;                 // a Gumbel search never mixes Dirichlet noise in
+    if (solver_set(d))
+        tree_expand_launch<true>(t, is_root, lp1, lp2, lpmc, priors220, values, noise, noise_stride, epsilon, make_solver(d), stream);
+    else
+        tree_expand_launch<false>(t, is_root, lp1, lp2, lpmc, priors220, values, noise, noise_stride, epsilon, SolverArgs{}, stream);
+    if (is_root && gumbel_set(d))
+        hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, make_gumbel(d),
+                           (const uint8_t*)nullptr);
     return st();
 }
 
@@ -1623,6 +1702,15 @@ int lz_tree_finish_gumbel(const LzTreeDesc* d, const float* temperatures, const 
     return st();
 }
 
+int lz_tree_solver_pick(const LzTreeDesc* d, const uint8_t* force_uniform, int32_t* chosen_index, int32_t* chosen_code,
+                        uint8_t* chosen_valid, int32_t* overrides, void* stream) {
+    if (!tree_ok(d) || !chosen_index || !chosen_code || !chosen_valid) return LZ_ERR_ARG;
+    if (!solver_set(d) || d->num_games == 0) return LZ_OK;
+    hipLaunchKernelGGL(tree_solver_pick_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
+                       force_uniform, chosen_index, reinterpret_cast<int4*>(chosen_code), chosen_valid, overrides);
+    return st();
+}
+
 static long long* g_advance_ticks = nullptr;
 int lz_debug_advance_ticks(int64_t* ticks) { g_advance_ticks = reinterpret_cast<long long*>(ticks); return LZ_OK; }
 
@@ -1667,6 +1755,9 @@ int lz_tree_advance(const LzTreeDesc* d, const int32_t* played_action, const uin
         hipLaunchKernelGGL(tree_advance_kernel<kWavesPerBlock>, dim3(gw(d->num_games)), dim3(kBlock), lds, as_stream(stream),
                            make_tree(d), played_action, reset, (int)rn, words, dropped, pruned, g_advance_ticks);
     (void)lz_prof_aux_end(1, stream, d->num_games);
+    if (solver_set(d) && d->root_proven &&                          // MCTS-Solver: the new root's result is set by its root step
+        hipMemsetAsync(d->root_proven, 0, (size_t)d->num_games * sizeof(int32_t), as_stream(stream)) != hipSuccess)
+        return LZ_ERR_LAUNCH;
     return st();
 }
 
@@ -1695,8 +1786,9 @@ static bool tree_gather_path(const LzNetDesc* net, int64_t B) {
 // CAP: the kernels of the playout cap (LzTreeDesc.sim_budget / root_noise), the same launch sequence.
 // FORCED: the select kernels of forced playouts (LzTreeDesc.forced_k), the same launch sequence.
 // GUMBEL: the kernels of the Gumbel root search (LzTreeDesc.gumbel_*), the same launch sequence.
-extern "C++" template <bool CAP, bool FORCED, bool GUMBEL = false>
-static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const ForcedArgs& fa, const GumbelArgs& ga, const LzNetDesc* net, int64_t sims, float* lp1,
+// SOLVER: the kernels of the MCTS-Solver (LzTreeDesc.solver), the same launch sequence with the one-wave step throughout.
+extern "C++" template <bool CAP, bool FORCED, bool GUMBEL = false, bool SOLVER = false>
+static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const ForcedArgs& fa, const GumbelArgs& ga, const SolverArgs& sv, const LzNetDesc* net, int64_t sims, float* lp1,
                               float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                               float epsilon, void* stream) {
     const int64_t B = d->num_games;
@@ -1714,22 +1806,22 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
             if (rc) return rc;
             if (s == sims) {
                 if (s == 0)
-                    hipLaunchKernelGGL((tree_expand_kernel<true, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                       lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, cap);
+                    hipLaunchKernelGGL((tree_expand_kernel<true, true, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
+                                       lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, cap, sv);
                 else
-                    hipLaunchKernelGGL((tree_expand_kernel<false, true, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                       lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap);
+                    hipLaunchKernelGGL((tree_expand_kernel<false, true, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
+                                       lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap, sv);
             } else if (s == 0) {
-                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP, FORCED, GUMBEL>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga);
+                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP, FORCED, GUMBEL, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga, sv);
             } else {
                 (void)lz_prof_aux_begin(0, stream);
-                if (split_step(t.B))
+                if (!SOLVER && split_step(t.B))
                     hipLaunchKernelGGL((tree_expand_select_split_kernel<true, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), dim3(kBlock), 0,
                                        as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, cap, fa, ga);
                 else
-                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP, FORCED, GUMBEL>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga);
+                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP, FORCED, GUMBEL, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv);
                 (void)lz_prof_aux_end(0, stream, B);
             }
             if (s < sims)                                           // the leaves of simulation s + 1
@@ -1747,22 +1839,22 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
         if (rc) return rc;
         if (s == sims) {   // last simulation: nothing left to select
             if (s == 0)
-                hipLaunchKernelGGL((tree_expand_kernel<true, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                                   lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, cap);
+                hipLaunchKernelGGL((tree_expand_kernel<true, false, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
+                                   lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, cap, sv);
             else
-                hipLaunchKernelGGL((tree_expand_kernel<false, false, CAP>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                                   lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap);
+                hipLaunchKernelGGL((tree_expand_kernel<false, false, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
+                                   lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap, sv);
         } else if (s == 0) {
-            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP, FORCED, GUMBEL>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga);
+            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP, FORCED, GUMBEL, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga, sv);
         } else {
             (void)lz_prof_aux_begin(0, stream);                      // no-ops unless lz_prof_enable(1) (never in a capture)
-            if (split_step(t.B))
+            if (!SOLVER && split_step(t.B))
                 hipLaunchKernelGGL((tree_expand_select_split_kernel<false, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
                                    t, lp1, lp2, lpmc, values, (int)s, cap, fa, ga);
             else
-                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP, FORCED, GUMBEL>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga);
+                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP, FORCED, GUMBEL, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv);
             (void)lz_prof_aux_end(0, stream, B);
         }
     }
@@ -1771,11 +1863,32 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
     return st();
 }
 
+// tree_search_launch for the descriptor's options: cap x (forced | Gumbel | neither), with or without the solver
+extern "C++" template <bool SOLVER>
+static int tree_search_dispatch(const LzTreeDesc* d, const Tree& t, const SolverArgs& sv, const LzNetDesc* net, int64_t sims,
+                                float* lp1, float* lp2, float* lpmc, float* values, const float* noise,
+                                int64_t noise_stride, float epsilon, void* stream) {
+    if (gumbel_set(d)) {                                           // (a Gumbel search never mixes Dirichlet noise in)
+        if (cap_set(d))
+            return tree_search_launch<true, false, true, SOLVER>(d, t, make_cap(d), ForcedArgs{}, make_gumbel(d), sv, net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
+        return tree_search_launch<false, false, true, SOLVER>(d, t, CapArrays{}, ForcedArgs{}, make_gumbel(d), sv, net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
+    }
+    if (forced_set(d)) {
+        if (cap_set(d))
+            return tree_search_launch<true, true, false, SOLVER>(d, t, make_cap(d), make_forced(d), GumbelArgs{}, sv, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_launch<false, true, false, SOLVER>(d, t, CapArrays{}, make_forced(d), GumbelArgs{}, sv, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    }
+    if (cap_set(d))
+        return tree_search_launch<true, false, false, SOLVER>(d, t, make_cap(d), ForcedArgs{}, GumbelArgs{}, sv, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    return tree_search_launch<false, false, false, SOLVER>(d, t, CapArrays{}, ForcedArgs{}, GumbelArgs{}, sv, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+}
+
 static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t sims, float* planes, float* lp1,
                             float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                             float epsilon, bool continue_trees, void* stream) {
     if (!tree_ok(d) || !net || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
     if (const int grc = gumbel_check(d)) return grc;
+    if (const int src = solver_check(d)) return src;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
@@ -1784,20 +1897,10 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     // Shared leaves (position index) only in the one-wave step, whose evaluator is this network: its outputs are a
     // function of the packed state alone.  The step-by-step entry points (external evaluators) and the two-wave split
     // step (where the descent runs beside the expansion that inserts into the index) keep the index but do not look it up.
-    const Tree t = split_step(B) ? no_share(make_tree(d)) : make_tree(d);
-    if (gumbel_set(d)) {                                           // (a Gumbel search never mixes Dirichlet noise in)
-        if (cap_set(d))
-            return tree_search_launch<true, false, true>(d, t, make_cap(d), ForcedArgs{}, make_gumbel(d), net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
-        return tree_search_launch<false, false, true>(d, t, CapArrays{}, ForcedArgs{}, make_gumbel(d), net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
-    }
-    if (forced_set(d)) {
-        if (cap_set(d))
-            return tree_search_launch<true, true>(d, t, make_cap(d), make_forced(d), GumbelArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-        return tree_search_launch<false, true>(d, t, CapArrays{}, make_forced(d), GumbelArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    }
-    if (cap_set(d))
-        return tree_search_launch<true, false>(d, t, make_cap(d), ForcedArgs{}, GumbelArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    return tree_search_launch<false, false>(d, t, CapArrays{}, ForcedArgs{}, GumbelArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    // with the solver always the one-wave step (so the position index is looked up at every launch size)
+    if (solver_set(d))
+        return tree_search_dispatch<true>(d, make_tree(d), make_solver(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    return tree_search_dispatch<false>(d, split_step(B) ? no_share(make_tree(d)) : make_tree(d), SolverArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
 }
 
 // lz_net.hip (internal): the checks of lz_net_forward_packed_multi_f16 on its networks
@@ -1813,6 +1916,7 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: one network per search only
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
+    if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: likewise
     int rc = lz_net_multi_validate(nets, num_nets);
     if (rc) return rc;
     const int64_t B = d->num_games, G = d->seg_games;
@@ -1835,20 +1939,20 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
         if (s == sims) {
             if (s == 0)
                 hipLaunchKernelGGL((tree_expand_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                   lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{});
+                                   lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, SolverArgs{});
             else
                 hipLaunchKernelGGL((tree_expand_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                   lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, CapArrays{});
+                                   lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, CapArrays{}, SolverArgs{});
         } else if (s == 0) {
             hipLaunchKernelGGL((tree_expand_select_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{});
+                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{});
         } else {
             if (split_step(t.B))
                 hipLaunchKernelGGL((tree_expand_select_split_kernel<true>), dim3(gw2(t.B)), dim3(kBlock), 0,
                                    as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{});
             else
                 hipLaunchKernelGGL((tree_expand_select_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{});
+                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{});
         }
         if (s < sims) scan(s + 1);                                  // the leaves of simulation s + 1
     }
@@ -1997,6 +2101,7 @@ int lz_tree_wave_select(const LzTreeDesc* d, const LzTreeWaveDesc* w, int64_t si
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
+    if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: likewise
     if (d->num_games == 0) return LZ_OK;
     const Tree t = make_tree(d);
     const WaveArrays a = make_wave(w);
@@ -2009,6 +2114,7 @@ int lz_tree_wave_expand(const LzTreeDesc* d, const LzTreeWaveDesc* w, const floa
                         const float* lpmc, const float* priors220, const float* values, int slot_major, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || !values) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver marks in lz_tree_expand / lz_tree_search only
     if (!priors220 && (!lp1 || !lp2 || !lpmc)) return LZ_ERR_ARG;
     if (d->num_games == 0) return LZ_OK;
     hipLaunchKernelGGL(tree_expand_wave_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
@@ -2024,7 +2130,7 @@ int lz_tree_search_waves(const LzTreeDesc* d, const LzTreeWaveDesc* w, const LzN
                          float* lp1, float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                          float epsilon, int continue_trees, int skip_roots, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || !net || sims < 0 || waves < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
-    if (forced_set(d) || gumbel_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (forced_set(d) || gumbel_set(d) || solver_set(d)) return LZ_ERR_UNSUPPORTED;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = LZ_OK;

@@ -30,6 +30,8 @@ enum LeafKind : int { kLeafInactive = 0, kLeafExpand = 1, kLeafTerminal = 2, kLe
 constexpr uint8_t kInfoWhite = 1;       // child mover is white
 constexpr uint8_t kInfoTerminal = 2;    // child is terminal (game over, or found to have no legal move)
 // bits 2..3: terminal value + 1  (0 => -1, 1 => 0, 2 => +1), from the child's mover's perspective
+constexpr uint8_t kInfoProven = 16;     // MCTS-Solver (LzTreeDesc.solver): the child's value is proven, bits 2..3 hold it the same way
+constexpr uint8_t kInfoDecided = kInfoTerminal | kInfoProven;
 
 // 32-byte edge record: one load brings everything the descent needs for a child, including where the child's
 // own edges live -- select never touches node records until it has found the leaf's parent.
@@ -99,6 +101,9 @@ struct CapArrays { const int* sim_budget; const uint8_t* root_noise; };
 // Optional forced playouts (LzTreeDesc.forced_k / forced_count): handed over the same way, read only by the FORCED
 // instantiations of the select / expand + select kernels.
 struct ForcedArgs { double k; int* count; };
+// Optional MCTS-Solver (LzTreeDesc.solver / root_proven / solver_count): handed over the same way, read only by the SOLVER
+// instantiations of the select / expand kernels.
+struct SolverArgs { int* root_proven; int* count; };
 // Optional Gumbel root search (LzTreeDesc.gumbel_*): handed over the same way, read only by the GUMBEL instantiations of
 // the select / expand + select kernels, by the root-step snapshot and by the Gumbel finish.  FORCED and GUMBEL exclude
 // each other (two rules for the same level).
@@ -401,6 +406,87 @@ __device__ __forceinline__ void gumbel_root_step(const Tree& t, int g, int lane,
     }
 }
 
+// ---- MCTS-Solver: the node rule that selection, marking and the pick share (LzTreeDesc.solver in liuzhou_hip.h) -----------
+// value of a decided edge for the mover of the node that owns it (`owner_player`)
+__device__ __forceinline__ int solver_x(uint8_t info, int owner_player) {
+    const int d = (int)((info >> 2) & 3) - 1;
+    return ((info & kInfoWhite) ? -1 : 1) == owner_player ? d : -d;
+}
+// R(X) over the info bytes of X's edges, two per lane (ok[r]: the edge exists; at least one does): 0 = undecided, else the
+// proven value for X's mover + 2 (1 lost, 2 drawn, 3 won)
+__device__ __forceinline__ int solver_rule(const uint8_t (&info)[2], const bool (&ok)[2], int owner_player) {
+    bool win = false, open = false, draw = false;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (!ok[r]) continue;
+        const bool dec = (info[r] & kInfoDecided) != 0;
+        const int x = solver_x(info[r], owner_player);
+        win = win || (dec && x > 0);
+        draw = draw || (dec && x == 0);
+        open = open || !dec;
+    }
+    if (__ballot(win)) return 3;
+    if (__ballot(open)) return 0;
+    return __ballot(draw) ? 2 : 1;
+}
+// R(root) over the root's edges as they stand in memory (the root step of a kept root)
+__device__ __forceinline__ int solver_root_rule(const Tree& t, const RootInfo& root, int lane) {
+    uint8_t inf[2]; bool ok[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int k = r * kWave + lane;
+        ok[r] = k < root.ne;
+        inf[r] = ok[r] ? edge_info(t.edges[(size_t)(root.e0 + k)].n_info) : (uint8_t)0;
+    }
+    return solver_rule(inf, ok, root.player);
+}
+// The climb of the expand step.  Path entry j (edge `e_j`) has just been decided; `info_j` is its info byte as it now
+// stands (taken from registers: the mark is a returnless atomic that a load may overtake).  As long as the node that owns
+// the decided edge becomes proven, its own incoming edge -- or the root result -- is marked and the climb goes one level up:
+// two dependent loads per level (the incoming edge record, the owner's run).  Returns the number of marks it made.
+// The loads leave edge lines in L1 while the backup's atomics are in flight, so the caller fences at agent scope
+// afterwards (wait for the atomics, invalidate L1) before anything selects again.
+__device__ __forceinline__ int solver_climb(const Tree& t, int g, int lane, const SolverArgs& sv, const int* path, int j,
+                                            int e_j, uint8_t info_j, const RootInfo& root) {
+    Edge* edges = t.edges;
+    int marks = 0;
+    while (true) {
+        int ye0, yne, yplayer, e_up = -1;
+        uint8_t in_info = 0;
+        if (j == 0) { ye0 = root.e0; yne = root.ne; yplayer = root.player; }
+        else {
+            e_up = (int)((uint32_t)path[j - 1] & ~kPathFlip);
+            const Edge up = load_edge(&edges[(size_t)e_up]);
+            in_info = edge_info(up.n_info);
+            if ((in_info & kInfoDecided) || up.child < 0) break;   // (descents end at a decided edge: never on a path)
+            ye0 = up.cbegin; yne = up.cn; yplayer = (in_info & kInfoWhite) ? -1 : 1;
+        }
+        uint8_t inf[2]; bool ok[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int k = r * kWave + lane;
+            ok[r] = k < yne;
+            inf[r] = ok[r] ? edge_info(edges[(size_t)(ye0 + k)].n_info) : (uint8_t)0;
+            if (ok[r] && ye0 + k == e_j) inf[r] = info_j;
+        }
+        const int p = solver_rule(inf, ok, yplayer);
+        if (p == 0) break;
+        if (j == 0) {
+            int fresh = 0;
+            if (lane == 0 && sv.root_proven[g] == 0) { sv.root_proven[g] = p; fresh = 1; }   // this game's wave is the only writer
+            marks += __builtin_amdgcn_readfirstlane(fresh);
+            break;
+        }
+        const uint8_t mark = (uint8_t)(kInfoProven | ((p - 1) << 2));
+        if (lane == 0) atomicOr(&edges[(size_t)e_up].n_info, (uint32_t)mark << 24);
+        info_j = (uint8_t)(in_info | mark);
+        e_j = e_up;
+        ++marks;
+        --j;
+    }
+    return marks;
+}
+
 // FORCED (forced playouts, root level only): with forced_k > 0 a root child that has visits but fewer than
 // sqrt(forced_k * P * root visits) is "due"; the descent takes the due child with the lowest edge index and skips the score
 // arithmetic of that level.  The test is on squares, all in double: N * N < (k * P) * n.
@@ -408,7 +494,11 @@ __device__ __forceinline__ void gumbel_root_step(const Tree& t, int g, int lane,
 // Halving over the children whose visits of this search equal the schedule's entry, by g + log P + sigma(completed Q);
 // no PUCT arithmetic on that level.  One pass over the mine[] registers: two double wave sums, an integer sum and maximum, one argmax, plus
 // three coalesced reads (gumbel_gl, gumbel_base, the table entry).
-template <bool FORCED = false, bool GUMBEL = false>
+// SOLVER (MCTS-Solver, every level that PUCT decides): a child decided with x = +1 is taken outright (lowest index); otherwise
+// the children decided with x = -1 are no candidates (unless all are), a decided child scores with q = x at any visit count,
+// and the descent ends at a decided edge -- terminal or proven -- with the value in its info bits.  These levels always take
+// the double arithmetic (the single-precision argmax's bound is derived for q = W / N only).
+template <bool FORCED = false, bool GUMBEL = false, bool SOLVER = false>
 __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, const RootInfo& root, int wait_edge = -1,
                                             int nolegal_edge = -1, volatile int* flag = nullptr, double forced_k = 0.0,
                                             int* forced_count = nullptr, const GumbelArgs* gum = nullptr,
@@ -496,7 +586,7 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
             chosen = gumbel_argmax(s, cand, lane);
             if (chosen < 0) break;                                 // every score NaN
         }
-        if ((!FORCED || chosen < 0) && (!GUMBEL || chosen < 0) && t.fast_select) {
+        if (!SOLVER && (!FORCED || chosen < 0) && (!GUMBEL || chosen < 0) && t.fast_select) {
             const float sqf = sqrtf((float)(parent_n > 1 ? parent_n : 1));
             const float cf = (float)t.c_puct;
             float fs[2] = {-INFINITY, -INFINITY};
@@ -527,6 +617,28 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
                 if (m1 - m2 > 1e-4f * (1.0f + fabsf(m1))) chosen = c;        // m2 = -inf (a single child): +inf
             }
         }
+        bool cand[2] = {true, true};
+        if (SOLVER && chosen < 0) {
+            bool win[2] = {false, false}, lose[2] = {false, false};
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                if (r == 1 && ne <= kWave) break;
+                const uint8_t inf = edge_info(mine[r].n_info);
+                if (r * kWave + lane < ne && (inf & kInfoDecided)) {
+                    const int x = solver_x(inf, node_player);
+                    win[r] = x > 0; lose[r] = x < 0;
+                }
+            }
+            const uint64_t wl = __ballot(win[0]);
+            if (wl) chosen = __ffsll((unsigned long long)wl) - 1;
+            else if (ne > kWave) {
+                const uint64_t wh = __ballot(win[1]);
+                if (wh) chosen = kWave + __ffsll((unsigned long long)wh) - 1;
+            }
+            if (chosen < 0 && __ballot((lane < ne && !lose[0]) || (kWave + lane < ne && !lose[1])) != 0ull) {
+                cand[0] = !lose[0]; cand[1] = !lose[1];
+            }
+        }
         if (chosen < 0) {
             const double sq = sqrt((double)(parent_n > 1 ? parent_n : 1));
             double best = -INFINITY;
@@ -535,10 +647,12 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
             for (int r = 0; r < 2; ++r) {
                 if (r == 1 && ne <= kWave) break;
                 const int k = r * kWave + lane;
-                if (k < ne) {
+                if (k < ne && (!SOLVER || cand[r])) {
                     const int n = edge_n(mine[r].n_info);
                     double q = 0.0;
-                    if (n > 0) {
+                    if (SOLVER && (edge_info(mine[r].n_info) & kInfoDecided)) {
+                        q = (double)solver_x(edge_info(mine[r].n_info), node_player);
+                    } else if (n > 0) {
                         const double mv = mine[r].W / (double)n;
                         const int child_player = (edge_info(mine[r].n_info) & kInfoWhite) ? -1 : 1;
                         q = child_player == node_player ? mv : -mv;
@@ -579,7 +693,7 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
         leaf_edge = e0 + chosen;
         if (lane == 0) path[depth] = leaf_edge | (child_player != node_player ? (int)kPathFlip : 0);
         ++depth;
-        if (info & kInfoTerminal) {
+        if (info & (SOLVER ? kInfoDecided : kInfoTerminal)) {
             kind = kLeafTerminal;
             term_value = (float)((int)((info >> 2) & 3) - 1);
             break;
@@ -644,15 +758,20 @@ constexpr int kExpandScratchBytes = 80 * 8;
 // ROLE 0: the whole step on one wave.  Split step (two waves per game): ROLE 1 = the expansion only (signals `flag`: its inputs
 // are in registers / its node and edges are written), ROLE 2 = the backup only (+ what the descent must know about the
 // leaf, `split`: the edge a node is being hung on, or the edge of a leaf without a legal move).
+// SOLVER (MCTS-Solver, `sv`): the node rule R on the edge records a new node has just got (info bytes from registers), the
+// mark on its incoming edge and the climb (solver_climb); the root result at the root step, fresh and kept roots alike.  The
+// value the simulation backs up is what it is without the switch.
 struct SplitInfo { int wait_edge, nolegal_edge; };
-template <bool IS_ROOT, int ROLE = 0>
+template <bool IS_ROOT, int ROLE = 0, bool SOLVER = false>
 __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, const float* __restrict__ lp1,
                                             const float* __restrict__ lp2, const float* __restrict__ lpm,
                                             const float* __restrict__ priors220, const float* __restrict__ values,
                                             const float* __restrict__ noise, int noise_stride, float epsilon,
                                             ExpandScratch sc, RootInfo* root_after = nullptr, int step = -1,
-                                            volatile int* flag = nullptr, SplitInfo* split = nullptr LZ_TSTAMP_ARG) {
+                                            volatile int* flag = nullptr, SplitInfo* split = nullptr,
+                                            const SolverArgs* sv = nullptr LZ_TSTAMP_ARG) {
     static_assert(ROLE == 0 || !IS_ROOT, "the root step is never split");
+    static_assert(ROLE == 0 || !SOLVER, "the solver runs on the one-wave step");
     LZ_TSTAMP(g, 0)
     const int kind = t.leaf_kind[g];
     Node* nodes = t.nodes + (size_t)g * t.node_cap;
@@ -740,10 +859,21 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
                     if (ok[r]) edges[(size_t)(e0 + r * kWave + lane)].P = pr[r] / denom;
             }
         }
+        if (SOLVER && IS_ROOT) {                              // R(root) over the kept root's edges (advance cleared the result)
+            const RootInfo kept = load_root_info(t, g);
+            const int p = kept.ne > 0 ? solver_root_rule(t, kept, lane) : 0;
+            if (p != 0 && lane == 0) {
+                sv->root_proven[g] = p;
+                if (sv->count != nullptr) sv->count[g] += 1;
+            }
+        }
         return;
     }
     const int plen = IS_ROOT ? 0 : plen_ld;
     double backup_value = 0.0;
+    int sol = 0;                    // SOLVER: this step decided the leaf: its value for its own mover + 2 (0: it did not)
+    bool sol_terminal = false;      // ... as a leaf without a legal move, whose edge already carries the terminal mark
+    int leaf_player = 1;
 
     if (kind == kLeafTerminal) {
         backup_value = (double)leaf_value_ld;
@@ -753,6 +883,7 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
         const State s = unpack(leaf_packed);
         const Legal L = legal_actions(s, /*fallback_forced=*/0);     // python semantics (move_generator.py:24-70)
         const int n = legal_count(L);
+        leaf_player = s.player;
         if (ROLE == 2) {                                       // the partner wave expands; this one only needs the value
             backup_value = n == 0 ? -1.0 : (double)value_ld;
             if (n == 0) split->nolegal_edge = leaf_edge; else split->wait_edge = leaf_edge;
@@ -767,6 +898,7 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
                 }
                 else atomicOr(&edges[(size_t)leaf_edge].n_info, (uint32_t)kInfoTerminal << 24);   // value bits stay 0 (= -1)
             }
+            if (SOLVER && !IS_ROOT) { sol = 1; sol_terminal = true; }
         } else {
             // gather per-lane logits / priors of the legal actions in ascending index order
             float h1 = 0.f, h2 = 0.f, hm = 0.f;
@@ -895,6 +1027,7 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
             LZ_TSTAMP(g, 4)                                    // allocation
             // Phase B: one pass (two only when a movement position has more than 64 legal moves)
             Edge* new_run = edges + (size_t)(e0 >= 0 ? e0 : 0);      // wave-uniform base + 32-bit lane offset
+            uint8_t new_info[2] = {0, 0};
             for (int r = 0; r < (n_write > kWave ? 2 : 1); ++r) {
                 const int k = r * kWave + lane;
                 if (k >= n_write) continue;
@@ -908,6 +1041,7 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
                     const int tv = (int)terminal_value_for_mover(c);
                     info |= kInfoTerminal | (uint8_t)((tv + 1) << 2);
                 }
+                if (SOLVER) { if (r == 0) new_info[0] = info; else new_info[1] = info; }
                 Edge rec;
                 rec.W = 0.0;
                 rec.P = shared ? (r == 0 ? cval[0] : cval[1]) : bad ? (1.0f / (float)n) : ((r == 0 ? cval[0] : cval[1]) / psum);
@@ -921,7 +1055,15 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
             }
             backup_value = (double)value_ld;
             LZ_TSTAMP(g, 5)                                    // child states, terminal tests, edge records
+            if (SOLVER && n_write > 0) {                       // (a refused expansion marks nothing)
+                const bool nok[2] = {lane < n_write, kWave + lane < n_write};
+                sol = solver_rule(new_info, nok, s.player);
+            }
         }
+    }
+    if (SOLVER && IS_ROOT && sol != 0 && lane == 0) {
+        sv->root_proven[g] = sol;
+        if (sv->count != nullptr) sv->count[g] += 1;
     }
     if (IS_ROOT || ROLE == 1) return;
     // ---- backup along the path (portable_mcts.py:123-138), one lane per path entry ----
@@ -949,6 +1091,14 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
             t.root_W[g] = root_w + ((flips_above & 1) ? -backup_value : backup_value);
         }
         if (root_after != nullptr) root_after->visits = root.visits;
+        if (SOLVER && sol != 0) {                              // mark the leaf's edge, then climb as far as the marks decide
+            const uint8_t mark = (uint8_t)(kInfoProven | ((sol - 1) << 2));
+            if (!sol_terminal && lane == 0) atomicOr(&edges[(size_t)leaf_edge].n_info, (uint32_t)mark << 24);
+            const uint8_t info_j = (uint8_t)((leaf_player < 0 ? kInfoWhite : 0) | (sol_terminal ? kInfoTerminal : mark));
+            const int marks = 1 + solver_climb(t, g, lane, *sv, path, plen - 1, leaf_edge, info_j, root);
+            if (sv->count != nullptr && lane == 0) sv->count[g] += marks;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+        }
     }
     LZ_TSTAMP(g, 6)                                            // backup issued
 }
@@ -1014,6 +1164,9 @@ inline CapArrays make_cap(const LzTreeDesc* d) { return CapArrays{d->sim_budget,
 inline bool forced_set(const LzTreeDesc* d) { return d->forced_k > 0.0; }
 inline ForcedArgs make_forced(const LzTreeDesc* d) { return ForcedArgs{d->forced_k, d->forced_count}; }
 inline bool gumbel_set(const LzTreeDesc* d) { return d->gumbel_m != 0; }
+inline bool solver_set(const LzTreeDesc* d) { return d->solver != 0; }
+inline int solver_check(const LzTreeDesc* d) { return solver_set(d) && !d->root_proven ? LZ_ERR_ARG : LZ_OK; }
+inline SolverArgs make_solver(const LzTreeDesc* d) { return SolverArgs{d->root_proven, d->solver_count}; }
 // LZ_OK, LZ_ERR_ARG (fields out of range / missing arrays) or LZ_ERR_UNSUPPORTED (with forced playouts)
 inline int gumbel_check(const LzTreeDesc* d) {
     if (!gumbel_set(d)) return LZ_OK;

@@ -152,6 +152,7 @@ class RootSearchBatchOutput:
     chosen_action_indices: torch.Tensor
     chosen_action_codes: torch.Tensor
     chosen_valid_mask: torch.Tensor
+    root_proven: Optional[torch.Tensor] = None     # tree search with the MCTS-Solver: 0 unknown, 1 lost, 2 drawn, 3 won
 
 
 class V1RootMCTS:

@@ -82,6 +82,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     forced_meta: Optional[Dict[str, Any]] = None
     gumbel_meta: Optional[Dict[str, Any]] = None
     td_meta: Optional[Dict[str, Any]] = None
+    solver_meta = False
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -109,6 +110,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         wtd = (wm.get("metadata") or {}).get("value_target")
         if isinstance(wtd, dict) and td_meta is None:
             td_meta = {"td_lambda": float(wtd.get("td_lambda", 1.0))}
+        solver_meta = solver_meta or bool((wm.get("metadata") or {}).get("mcts_solver"))
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -133,6 +135,8 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         meta["gumbel"] = {**gumbel_meta, "gumbel_searches": int(merged.mcts_counters.get("gumbel_searches", 0))}
     if td_meta is not None:             # TD(lambda) value targets: the lambda the rows' value_targets were blended with
         meta["value_target"] = td_meta
+    if solver_meta:                     # MCTS-Solver: on (its counters travel in the merged mcts_counters)
+        meta["mcts_solver"] = True
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -157,7 +161,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         in_process: bool = False, playout_cap_fast_simulations: int = 0,
                         playout_cap_full_prob: float = 1.0, forced_playouts_k: float = 0.0,
                         gumbel_considered: int = 0, gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0,
-                        value_target_lambda: float = 1.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        value_target_lambda: float = 1.0,
+                        mcts_solver: bool = False) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
@@ -166,7 +171,12 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
     (tree backend, forced playouts and policy target pruning) only when it is > 0, and `gumbel_considered` /
     `gumbel_c_visit` / `gumbel_c_scale` (tree backend, Gumbel root search with Sequential Halving; a Gumbel search never
     mixes Dirichlet noise into the root priors, whatever `add_dirichlet_noise` says) only when gumbel_considered > 0, and
-    `value_target_lambda` (tree backend, TD(lambda) value targets from the searches' root values; 1 = off) only when < 1."""
+    `value_target_lambda` (tree backend, TD(lambda) value targets from the searches' root values; 1 = off) only when < 1,
+    and `mcts_solver` (tree backend, the MCTS-Solver) only when it is on."""
+    solver = bool(mcts_solver)
+    if solver and str(search_backend).strip().lower() not in ("portable", "tree"):
+        raise ValueError(f"the MCTS-Solver needs the tree backend, not the root-PUCT search ({search_backend!r}): it marks "
+                         "proven results in the search tree")
     from .gumbel import gumbel_on
     from .tree_engine import forced_playouts_on, gumbel_refusal, playout_cap_on
     from .value_target import td_lambda_on
@@ -227,7 +237,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             **({"forced_playouts_k": float(forced_playouts_k)} if forced else {}),
             **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
                 "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
-            **({"value_target_lambda": float(value_target_lambda)} if td else {}))
+            **({"value_target_lambda": float(value_target_lambda)} if td else {}),
+            **({"mcts_solver": True} if solver else {}))
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

@@ -582,7 +582,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          policy_target_prior_pseudocount: float = 0.0, eval_symmetry="none",
                          playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
                          forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
-                         gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0) -> Dict[str, Any]:
+                         gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0,
+                         mcts_solver: bool = False) -> Dict[str, Any]:
     """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
     `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
     tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on.
@@ -593,7 +594,13 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
     priors, whatever `add_dirichlet_noise` says.  Recorded in the manifests' metadata["gumbel"] when on.
     `value_target_lambda` (tree backend only; 1 = off): TD(lambda) value targets from the searches' root values, see
     tree_engine.self_play_tree_gpu; they travel in `value_targets`.  Recorded in the manifests'
-    metadata["value_target"] when on."""
+    metadata["value_target"] when on.
+    `mcts_solver` (tree backend only): the MCTS-Solver, see tree_engine.self_play_tree_gpu.  Recorded in the manifests'
+    metadata["mcts_solver"] when on."""
+    solver = bool(mcts_solver)
+    if solver and str(search_backend).strip().lower() not in ("portable", "tree"):
+        raise ValueError(f"the MCTS-Solver needs the tree backend, not the root-PUCT search ({search_backend!r}): it marks "
+                         "proven results in the search tree")
     from .gumbel import gumbel_on
     from .tree_engine import forced_playouts_on, gumbel_refusal, parse_eval_symmetry, playout_cap_on
     from .value_target import td_lambda_on
@@ -689,7 +696,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                           **({"gumbel_considered": int(gumbel_considered),
                                               "gumbel_c_visit": float(gumbel_c_visit),
                                               "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
-                                          **({"value_target_lambda": float(value_target_lambda)} if td else {}), **common)
+                                          **({"value_target_lambda": float(value_target_lambda)} if td else {}),
+                                          **({"mcts_solver": True} if solver else {}), **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
                                     sparse_top_k=int(sparse_top_k), row_log=row_log, **common)
@@ -711,7 +719,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        **({"forced_playouts": {"k": float(forced_playouts_k)}} if forced else {}),
                        **({"gumbel": {"considered": int(gumbel_considered), "c_visit": float(gumbel_c_visit),
                                       "c_scale": float(gumbel_c_scale)}} if gumbel else {}),
-                       **({"value_target": {"td_lambda": float(value_target_lambda)}} if td else {})}
+                       **({"value_target": {"td_lambda": float(value_target_lambda)}} if td else {}),
+                       **({"mcts_solver": True} if solver else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

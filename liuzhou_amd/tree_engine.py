@@ -59,7 +59,8 @@ class LzTreeDesc(C.Structure):
                [("gumbel_m", C.c_int32), ("gumbel_sims", C.c_int32), ("gumbel_c_visit", C.c_double),
                 ("gumbel_c_scale", C.c_double)] + \
                [(n, C.c_void_p) for n in ("gumbel_g", "gumbel_table", "gumbel_gl", "gumbel_base", "gumbel_root_base",
-                                          "gumbel_root_value", "gumbel_count")] + [("gumbel_stride", C.c_int64)]
+                                          "gumbel_root_value", "gumbel_count")] + [("gumbel_stride", C.c_int64)] + \
+               [("solver", C.c_int32), ("root_proven", C.c_void_p), ("solver_count", C.c_void_p)]
 
 
 def playout_cap_on(fast_simulations: int, full_prob: float, sims: int) -> bool:
@@ -197,6 +198,16 @@ def gumbel_refusal(*, batch_k=1, several_networks=False, fused=True, forced_play
             if float(policy_target_prior_pseudocount) > 0.0 else None)
 
 
+def solver_refusal(*, batch_k=1, several_networks=False, fused=True) -> Optional[str]:
+    """Why a configuration cannot run the MCTS-Solver (None: it can): the marks are made by the expand step of the fused
+    launch-pair search, which the legacy waves, the multi-network search, the host-side split protocol and the persistent
+    kernel do not run."""
+    return ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
+            "several networks in one search" if several_networks else
+            "an external evaluator (split-phase path)" if not fused else
+            "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else None)
+
+
 def forced_playouts_on(k) -> bool:
     """Validate `forced_playouts_k`: 0 = off, a positive finite number = on; negative or non-finite is a ValueError."""
     k = float(k)
@@ -325,6 +336,11 @@ class TreeEngine:
         # Gumbel root search (set_gumbel; LzTreeDesc.gumbel_*): the buffers exist only once it is switched on
         self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale = 0, 50.0, 1.0
         self.gumbel: Dict[str, torch.Tensor] = {}
+        # MCTS-Solver (set_solver; LzTreeDesc.solver / root_proven / solver_count): the buffers exist only once it is on
+        self.solver = False
+        self.root_proven: Optional[torch.Tensor] = None
+        self.solver_count: Optional[torch.Tensor] = None
+        self.solver_overrides: Optional[torch.Tensor] = None
         self.segment_games = None if segment_games is None else int(segment_games)
         self.num_segments = 1
         if self.segment_games is not None:
@@ -468,6 +484,40 @@ class TreeEngine:
             setattr(d, "gumbel_" + name, self.gumbel[name].data_ptr())
         self.persistent = False           # the persistent kernel refuses the descriptor: the launch-pair search
 
+    def set_solver(self, on: bool = True) -> None:
+        """MCTS-Solver (LzTreeDesc.solver; off by default): the expand step marks proven edges and carries them up the
+        tree, select() / search() take a proven win, avoid proven losses and end a descent at a decided edge, and
+        solver_pick() (after finish()) keeps the played move from throwing a proven win away.  `root_proven` int32[B]
+        (0 unknown, 1 lost, 2 drawn, 3 won for the root's mover), `solver_count` int32[B] (marks made, summed over the
+        searches) and `solver_overrides` int32[B] (picks changed).  Must be set before a search is captured into a graph."""
+        on = bool(on)
+        if on and self.batch_k > 1:
+            raise ValueError("the MCTS-Solver is not supported by the legacy waves (batch_k > 1)")
+        if on and self.segment_games is not None:
+            raise ValueError("the MCTS-Solver is not supported with several networks in one search")
+        self.solver = on
+        d = self.desc
+        d.solver = 1 if on else 0
+        if not on:
+            d.root_proven = d.solver_count = None
+            return
+        if self.root_proven is None:
+            z = lambda: torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+            self.root_proven, self.solver_count, self.solver_overrides = z(), z(), z()
+        d.root_proven, d.solver_count = self.root_proven.data_ptr(), self.solver_count.data_ptr()
+        self.persistent = False           # the persistent kernel refuses the descriptor: the launch-pair search
+
+    def solver_pick(self, force_uniform: Optional[torch.Tensor] = None) -> None:
+        """lz_tree_solver_pick over the last finish()'s picks (nothing is launched while the solver is off)."""
+        if not self.solver:
+            return
+        if force_uniform is not None and force_uniform.dtype != torch.uint8:
+            force_uniform = force_uniform.to(torch.uint8)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_tree_solver_pick(C.byref(self.desc), L.ptr(force_uniform), L.ptr(self.chosen_index),
+                                                L.ptr(self.chosen_code), L.ptr(self.chosen_valid),
+                                                L.ptr(self.solver_overrides), self._stream()), "tree_solver_pick")
+
     _NODE_DT = [("w0", "<u8"), ("w1", "<u8"), ("w2", "<u8"), ("w3", "<u8"), ("edge_begin", "<i4"), ("nedges", "<i4"),
                 ("parent", "<i4"), ("old_begin", "<i4")]
     _EDGE_DT = [("W", "<f8"), ("P", "<f4"), ("n_info", "<u4"), ("child", "<i4"), ("cbegin", "<i4"),
@@ -494,7 +544,7 @@ class TreeEngine:
         recs = self.edge_run(e0, ne)
         return [{"action_index": int(r["act"]), "prior": float(r["P"]), "visit_count": int(r["n_info"] & 0xFFFFFF),
                  "value_sum": float(r["W"]), "child_white": bool((r["n_info"] >> 24) & 1),
-                 "terminal": bool((r["n_info"] >> 24) & 2)} for r in recs]
+                 "terminal": bool((r["n_info"] >> 24) & 2), "info": int(r["n_info"] >> 24)} for r in recs]
 
     def pool_status(self) -> Dict[str, int]:
         """Edge pool: chunks, free now, fewest free seen since construction, refused expansions (must stay 0)."""
@@ -769,7 +819,7 @@ class PortableTreeMCTS:
                  collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none",
                  segment_games: Optional[int] = None, multi_launch: bool = True, fast_simulations: int = 0,
                  full_prob: float = 1.0, forced_playouts_k: float = 0.0, gumbel_considered: int = 0,
-                 gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0) -> None:
+                 gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0, solver: bool = False) -> None:
         """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
         searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
         FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
@@ -813,9 +863,20 @@ class PortableTreeMCTS:
         uniform do not apply to it either (opening random moves keep precedence).  The variates come from the per-game
         RNG (GameRng.gumbel_into); parity runs inject their own through `injected_gumbel` ([B, <= OUT_CAP]).
         `gumbel_searches` counts the searches that ran the rule.  Refused where the cap is refused, and with
-        forced playouts, `policy_target_temperature` and `policy_target_prior_pseudocount` > 0 (ValueError)."""
+        forced playouts, `policy_target_temperature` and `policy_target_prior_pseudocount` > 0 (ValueError).
+        `solver`: MCTS-Solver (TreeEngine.set_solver).  Exact results -- eliminations, draws by the
+        move or no-capture limit -- are marked on the edges and carried up as far as they decide the parent; decided children
+        stop being searched, and the played move never throws a proven win away (nor picks a proven loss next to another
+        move).  The outputs gain `root_proven`; `solver_counts` sums proofs, decided roots and changed picks.  Composes with
+        the cap, forced playouts, Gumbel, symmetric evaluation, shared leaves and tree reuse; refused where the cap is."""
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
+        self.solver = bool(solver)
+        if self.solver:
+            why = solver_refusal(batch_k=batch_k, several_networks=self.multi or len(self.nets) != 1,
+                                 fused=isinstance(self.nets[0], FusedNet))
+            if why is not None:
+                raise ValueError(f"the MCTS-Solver is not supported with {why}")
         self.gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
         self.gumbel_considered = int(gumbel_considered)
         self.gumbel_c_visit, self.gumbel_c_scale = float(gumbel_c_visit), float(gumbel_c_scale)
@@ -887,6 +948,9 @@ class PortableTreeMCTS:
         self.injected_gumbel: Optional[torch.Tensor] = None      # parity runs: [B, <= OUT_CAP] instead of the RNG's draws
         if self.gumbel:
             self.engine.set_gumbel(self.gumbel_considered, self.gumbel_c_visit, self.gumbel_c_scale, int(num_simulations))
+        self._roots_decided = torch.zeros((1,), dtype=torch.int64, device=self.engine.device)
+        if self.solver:
+            self.engine.set_solver(True)
         if not self.fused:
             if self.batch_k > 1:
                 raise ValueError("an external evaluator supports batch_k = 1 only")
@@ -945,6 +1009,21 @@ class PortableTreeMCTS:
     def forced_counts(self) -> torch.Tensor:
         """int64[2] on the device: forced descents and pruned visits of the searches so far (zeros when off)."""
         return torch.cat((self.engine.forced_count.sum(dtype=torch.int64).view(1), self._pruned_total))
+
+    @property
+    def solver_counts(self) -> torch.Tensor:
+        """int64[3] on the device: proofs (edges and roots the expand step decided), searches that ended with a decided
+        root, and picks the solver changed, so far (zeros when off)."""
+        if not self.solver:
+            return torch.zeros((3,), dtype=torch.int64, device=self.engine.device)
+        e = self.engine
+        return torch.cat((e.solver_count.sum(dtype=torch.int64).view(1), self._roots_decided,
+                          e.solver_overrides.sum(dtype=torch.int64).view(1)))
+
+    def _reset_solver_counts(self) -> None:
+        self._roots_decided.zero_()
+        if self.solver:
+            self.engine.solver_count.zero_(); self.engine.solver_overrides.zero_()
 
     @property
     def gumbel_searches(self) -> torch.Tensor:
@@ -1103,6 +1182,7 @@ class PortableTreeMCTS:
                 counted = (e.live_total.clone(), e.eval_count.clone(), e.share_count.clone())   # warm-ups are not searches
                 forced_counted = e.forced_count.clone() if self.forced else None
                 gumbel_counted = e.gumbel["count"].clone() if self.gumbel else None
+                solver_counted = e.solver_count.clone() if self.solver else None
                 for form in ((lists, not lists) if (e.compact_evals and not self.fused_multi) else (lists,)):
                     self._run_search(min(self.sims, 2), noise, False, form)
                 e.live_total.copy_(counted[0]); e.eval_count.copy_(counted[1]); e.share_count.copy_(counted[2])
@@ -1110,6 +1190,8 @@ class PortableTreeMCTS:
                     e.forced_count.copy_(forced_counted)
                 if gumbel_counted is not None:
                     e.gumbel["count"].copy_(gumbel_counted)
+                if solver_counted is not None:
+                    e.solver_count.copy_(solver_counted)
             torch.cuda.synchronize(e.device)
             try:
                 g = torch.cuda.CUDAGraph()
@@ -1201,6 +1283,7 @@ class PortableTreeMCTS:
         self.engine.forced_count.zero_(); self._pruned_total.zero_()
         if self.gumbel:
             self.engine.gumbel["count"].zero_()
+        self._reset_solver_counts()
         # refused expansions / fewest free chunks are per run too (a cached engine must not report an earlier run's)
         # (pool_stats[2], the chunks reserved for fresh roots, follows the trees' state and is NOT a per-run statistic)
         self.engine.buf["pool_stats"][:2].copy_(torch.tensor([0, self.engine.pool_chunks], dtype=torch.int32))
@@ -1227,6 +1310,7 @@ class PortableTreeMCTS:
         self.engine.forced_count.zero_(); self._pruned_total.zero_()
         if self.gumbel:
             self.engine.gumbel["count"].zero_()
+        self._reset_solver_counts()
         self.get_timing(reset=True)
         if self.batch_k > 1:
             self.engine.wbuf["eval_total"].zero_(); self.engine.wbuf["eval_count"].zero_()
@@ -1313,12 +1397,16 @@ class PortableTreeMCTS:
             e.finish(temps, uniforms, tt, self.prior_pseudocount, force_uniform_random_mask, self.sample_moves)
             if self.forced:
                 self._pruned_total.add_(e.pruned_visits.sum(dtype=torch.int64))
+            if self.solver:               # a proven win is played, a proven loss is not while another move exists
+                e.solver_pick(force_uniform_random_mask)
+                self._roots_decided.add_((e.root_proven != 0).sum(dtype=torch.int64))
             model_input = states_to_model_input(state)
             legal_mask, _ = encode_actions_fast(state)
         return RootSearchBatchOutput(
             model_input=model_input, legal_mask=legal_mask, policy_dense=e.policy_dense, root_value=e.root_value,
             terminal_mask=e.terminal_mask, chosen_action_indices=e.chosen_index.to(torch.int64),
-            chosen_action_codes=e.chosen_code, chosen_valid_mask=e.chosen_valid)
+            chosen_action_codes=e.chosen_code, chosen_valid_mask=e.chosen_valid,
+            **({"root_proven": e.root_proven} if self.solver else {}))
 
 
 class DualStreamTreeMCTS:
@@ -1364,6 +1452,7 @@ class DualStreamTreeMCTS:
         self.cap = self.parts[0].cap
         self.forced = self.parts[0].forced
         self.gumbel = self.parts[0].gumbel
+        self.solver = self.parts[0].solver
         self.full_search = None
         if self.cap:
             self.full_search = torch.zeros((self.B,), dtype=torch.uint8, device=dev)
@@ -1404,6 +1493,10 @@ class DualStreamTreeMCTS:
     @property
     def forced_counts(self) -> torch.Tensor:
         return sum(p.forced_counts for p in self.parts)
+
+    @property
+    def solver_counts(self) -> torch.Tensor:
+        return sum(p.solver_counts for p in self.parts)
 
     @property
     def last_full_search(self) -> Optional[torch.Tensor]:
@@ -1554,7 +1647,8 @@ class DualStreamTreeMCTS:
                 main.wait_stream(st)
         return RootSearchBatchOutput(*(torch.cat([getattr(o, f) for o in outs], dim=0)
                                        for f in ("model_input", "legal_mask", "policy_dense", "root_value", "terminal_mask",
-                                                 "chosen_action_indices", "chosen_action_codes", "chosen_valid_mask")))
+                                                 "chosen_action_indices", "chosen_action_codes", "chosen_valid_mask")),
+                                     **({"root_proven": torch.cat([o.root_proven for o in outs], dim=0)} if self.solver else {}))
 
 
 class SteadyStateTreeSelfPlay:
@@ -1656,7 +1750,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        collect_timing: bool = False, row_log=None, eval_symmetry="none",
                        playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
                        forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
-                       gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0
+                       gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0, mcts_solver: bool = False
                        ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
@@ -1687,8 +1781,13 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     t-th search from Black's frame (every search counts, the playout cap's fast ones and a terminal root's too), y_L = the
     result and y_t = (1 - lambda) Q_t + lambda y_{t+1}, the row recorded at ply t gets value_target = sign * y_t instead of
     sign * result; `soft_value_targets` stay as they are.  Needs `device_tail` (ValueError otherwise: the host loop keeps
-    the reference's finalisation); composes with everything else."""
+    the reference's finalisation); composes with everything else.
+    `mcts_solver`: MCTS-Solver (PortableTreeMCTS `solver`) in every search: proven wins, draws and losses are marked in the
+    tree, decided children stop being searched and the played move never throws a proven win away.  mcts_counters gain
+    solver_proofs / solver_roots_decided / solver_pick_overrides.  Fused network and batch_k = 1 only (ValueError
+    otherwise); composes with everything else."""
     dev = torch.device(device)
+    solver = bool(mcts_solver)
     td = td_lambda_on(value_target_lambda)
     if td and not device_tail:
         raise ValueError("value_target_lambda < 1 needs device_tail: the host loop keeps the reference's finalisation "
@@ -1724,6 +1823,10 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                          "evaluator, not legacy waves)")
     if forced and _persistent_default():
         raise ValueError("forced playouts are not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
+    if solver:
+        why = solver_refusal(batch_k=batch_k, fused=use_fused)
+        if why is not None:
+            raise ValueError(f"the MCTS-Solver is not supported with {why}")
     if gumbel:
         why = gumbel_refusal(batch_k=batch_k, fused=use_fused, forced_playouts_k=forced_playouts_k,
                              policy_target_temperature=policy_target_temperature,
@@ -1751,6 +1854,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     if gumbel:
         kw.update(gumbel_considered=int(gumbel_considered), gumbel_c_visit=float(gumbel_c_visit),
                   gumbel_c_scale=float(gumbel_c_scale))
+    if solver:
+        kw["solver"] = True
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a
@@ -1931,6 +2036,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        **(dict(zip(("forced_playouts", "pruned_visits"), (int(x) for x in mcts.forced_counts.tolist())))
                           if forced else {}),
                        # Gumbel root search: searches of live games that ran the rule
-                       **({"gumbel_searches": int(mcts.gumbel_searches.item())} if gumbel else {})},
+                       **({"gumbel_searches": int(mcts.gumbel_searches.item())} if gumbel else {}),
+                       # MCTS-Solver: edges / roots the expand steps decided, searches that ended with a decided root, picks changed
+                       **(dict(zip(("solver_proofs", "solver_roots_decided", "solver_pick_overrides"),
+                                   (int(x) for x in mcts.solver_counts.tolist()))) if solver else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))
     return batch, stats

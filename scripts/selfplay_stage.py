@@ -60,6 +60,9 @@ def parse(argv=None):
     ap.add_argument("--value_target_lambda", type=float, default=1.0,
                     help="TD(lambda) value targets (tree backend): lambda of y_t = (1 - lambda) Q_t + lambda y_(t+1) over the "
                          "searches' root values, 1 = off (every row gets the final result)")
+    ap.add_argument("--mcts_solver", action="store_true",
+                    help="MCTS-Solver (tree backend): mark proven wins, draws and losses in the search tree, stop searching "
+                         "decided children and never play away a proven win")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -122,7 +125,7 @@ def main(argv=None) -> int:
         playout_cap_fast_simulations=args.playout_cap_fast_simulations, playout_cap_full_prob=args.playout_cap_full_prob,
         forced_playouts_k=args.forced_playouts_k, gumbel_considered=args.gumbel_considered,
         gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale,
-        value_target_lambda=args.value_target_lambda)
+        value_target_lambda=args.value_target_lambda, **({"mcts_solver": True} if args.mcts_solver else {}))
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
