@@ -594,6 +594,31 @@ typedef struct LzTreeDesc {
     int32_t* root_proven;          /* [B] required when solver != 0 */
     int32_t* solver_count;         /* [B] optional: += 1 for every edge the expand step marks (proven, or terminal for want of
                                       a legal move) and every root result it sets */
+    /* Optional PUCT shape: first-play urgency and a visit-scaled exploration constant (puct_shape == 0 = off: nothing below
+     * is read).  Both act on the levels that PUCT decides -- a root level under the forced-playout rule and a child the solver
+     * takes outright are decided before the score and stay as they are.  n_v is the visit count the level already uses:
+     * root_visits at the root, the count on the incoming edge elsewhere.
+     *   Bit 1, the table: c(n_v) = cpuct_table[min(n_v, cpuct_table_len - 1)] replaces exploration_weight in the score
+     *   q + c * P * sqrt(max(n_v, 1)) / (1 + n), same operation order.  The host builds the table once
+     *   (table[i] = c_puct + cpuct_log * ln((i + cpuct_base + 1) / cpuct_base) in float64); there is no log on the device.
+     *   lz_tree_finish_pruned uses c(root_visits) wherever its rule has exploration_weight.
+     *   Bit 0, first-play urgency: a child with n == 0 that the solver has not decided scores q = f instead of 0,
+     *     V = W_v / n_v (one double division; W_v = root_w at the root, the incoming edge's W below it, both already in the
+     *         node's mover's frame; with n_v == 0, V = (double)root_init_value),
+     *     S = sum over the children with n > 0, decided or not, of (uint64)((double)P * 2^30)   (an integer sum),
+     *     f = max(V - r * sqrt((double)S / 2^30), -1.0), r = fpu_root_reduction at the root and fpu_reduction below it; the
+     *         product and the difference are rounded separately.
+     *   Decided children keep q = x, visited children +-W / n.  fpu_reduction = 0 is a valid "on" (the parent's value).
+     * A shaped level always takes the double arithmetic, and a shaped search the one-wave step at every launch size (the
+     * two-waves-per-game step is not used).  Honoured by lz_tree_select, lz_tree_search / _continue (dense, list and
+     * gathering launches; with the playout cap, forced playouts and the solver), lz_tree_search_multi and
+     * lz_tree_finish_pruned.  With gumbel_m != 0, and in the wave and persistent searches: LZ_ERR_UNSUPPORTED.  Bit 1 with
+     * a NULL table or cpuct_table_len < 2, bit 0 with a negative or non-finite reduction: LZ_ERR_ARG. */
+    int32_t  puct_shape;           /* bit 0: first-play urgency, bit 1: cpuct_table; 0 = off */
+    int32_t  cpuct_table_len;
+    double   fpu_reduction;
+    double   fpu_root_reduction;
+    const double* cpuct_table;     /* [cpuct_table_len] device memory */
 } LzTreeDesc;
 LZ_API int64_t lz_tree_desc_bytes(void);
 

@@ -86,12 +86,14 @@ __global__ __launch_bounds__(kBlock) void pos_clear_kernel(int* __restrict__ tab
 // GUMBEL (here and in the expand + select kernels): the Gumbel root search (`ga`, tree_select); likewise never read by the
 // other instantiations.
 // SOLVER (here and in the expand / expand + select kernels): the MCTS-Solver (`sv`, tree_select / tree_expand); likewise.
-template <bool FORCED = false, bool GUMBEL = false, bool SOLVER = false>
-__global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t, ForcedArgs fa, GumbelArgs ga) {
+// SHAPE (here, in the expand + select kernels and in the pruning finish): first-play urgency and the visit-scaled c (`sh`,
+// tree_select); likewise.  There is no SHAPE form of the two-wave split kernel: a shaped search runs the one-wave step.
+template <bool FORCED = false, bool GUMBEL = false, bool SOLVER = false, bool SHAPE = false>
+__global__ __launch_bounds__(kBlock) void tree_select_kernel(Tree t, ForcedArgs fa, GumbelArgs ga, ShapeArgs sh) {
     const int g = wave_game();
     if (g >= t.B) return;
-    tree_select<FORCED, GUMBEL, SOLVER>(t, g, lane_id(), load_root_info(t, g), -1, -1, nullptr, FORCED ? fa.k : 0.0, fa.count,
-                                &ga, GUMBEL);
+    tree_select<FORCED, GUMBEL, SOLVER, SHAPE>(t, g, lane_id(), load_root_info(t, g), -1, -1, nullptr, FORCED ? fa.k : 0.0,
+                                               fa.count, &ga, GUMBEL, &sh);
 }
 // the root step's snapshot as a launch of its own (lz_tree_expand with is_root: the step-by-step protocol)
 __global__ __launch_bounds__(kBlock) void gumbel_root_kernel(Tree t, GumbelArgs ga,
@@ -254,14 +256,15 @@ __global__ __launch_bounds__(kScanBlock) void tree_live_scan_seg_kernel(Tree t, 
 // records it just touched are still in L1/L2) -- one launch per simulation besides the network kernel.
 // (forcing 8 waves / SIMD -- <= 96 SGPRs, 126 scalar spills -- was measured: no gain at 16 384 games, 1 % slower at C2)
 template <bool IS_ROOT, bool COMPACT = false, bool CAP = false, bool FORCED = false, bool GUMBEL = false,
-          bool SOLVER = false>
+          bool SOLVER = false, bool SHAPE = false>
 __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, const float* __restrict__ lp1,
                                                                     const float* __restrict__ lp2,
                                                                     const float* __restrict__ lpm,
                                                                     const float* __restrict__ values,
                                                                     const float* __restrict__ noise, int noise_stride,
                                                                     float epsilon, int step, CapArrays cap,
-                                                                    ForcedArgs fa, GumbelArgs ga, SolverArgs sv) {
+                                                                    ForcedArgs fa, GumbelArgs ga, SolverArgs sv,
+                                                                    ShapeArgs sh) {
 #ifndef LZ_EXP_NO_TREE_PRIO
     // The kernel is a chain of dependent loads with a few dozen instructions in between; in the two-stream search it
     // shares the SIMDs with the other half's network waves, which always have MFMAs to issue.  Raised wave priority
@@ -293,7 +296,7 @@ __global__ __launch_bounds__(kBlock) void tree_expand_select_kernel(Tree t, cons
     LZ_TSTAMP(g, 7)                                            // fence (+ root reload)
     // forced playouts: the games whose root-noise switch is on (every game without the cap, the full searches with it)
     const double fk = FORCED && (!CAP || cap_noise(cap, g)) ? fa.k : 0.0;
-    tree_select<FORCED, GUMBEL, SOLVER>(t, g, lane, root, -1, -1, nullptr, fk, fa.count, &ga, gum_on LZ_TSTAMP_PASS);
+    tree_select<FORCED, GUMBEL, SOLVER, SHAPE>(t, g, lane, root, -1, -1, nullptr, fk, fa.count, &ga, gum_on, &sh LZ_TSTAMP_PASS);
 #ifdef LZ_EXP_TREE_STAMPS
     LZ_TADD(g, 19, 1)
 #endif
@@ -950,7 +953,9 @@ __device__ __forceinline__ void score_policy(const float (&sc)[2], const bool (&
 // PRUNE (lz_tree_finish_pruned): policy target pruning for the games whose search was forced (forced_k > 0, root-noise
 // switch on): the training target is formed from the pruned visits N' (see liuzhou_hip.h), everything else from N.
 // Every decision of the stage is in double, and no product meets a sum without a division or a comparison in between.
-template <bool PRUNE = false>
+// SHAPE (PRUNE only): c(T) from the visit-scaled table (ShapeArgs) wherever the pruning rule has c_puct; first-play urgency
+// does not enter, the rule only looks at visited children.
+template <bool PRUNE = false, bool SHAPE = false>
 __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float* __restrict__ temps,
                                                              const float* __restrict__ target_temps,
                                                              float prior_pseudocount,
@@ -970,7 +975,7 @@ __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float
                                                              double forced_k,
                                                              const uint8_t* __restrict__ root_noise,
                                                              int* __restrict__ child_target_visits,
-                                                             int* __restrict__ pruned_visits) {
+                                                             int* __restrict__ pruned_visits, ShapeArgs sh) {
     const int lane = lane_id();
     const int g = wave_game();
     if (g >= t.B) return;
@@ -1040,7 +1045,10 @@ __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float
             const int T = t.root_visits[g];
             const double tm = (double)(T > 1 ? T : 1);
             const double sq = sqrt(tm);
-            const double s_star = qs + t.c_puct * (double)ps * sq / (1.0 + (double)ns);
+            double c_root = t.c_puct;
+            if (SHAPE && (sh.flags & kShapeTable))
+                c_root = sh.table[T < sh.table_len - 1 ? (T > 0 ? T : 0) : sh.table_len - 1];
+            const double s_star = qs + c_root * (double)ps * sq / (1.0 + (double)ns);
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 const int n = nv[r];
@@ -1056,7 +1064,7 @@ __global__ __launch_bounds__(kBlock) void tree_finish_kernel(Tree t, const float
                 int least = n;                                 // L: nothing may be taken unless the gap is positive
                 const double gap = s_star - q[r];
                 if (gap > 0.0) {
-                    const double x = (t.c_puct * (double)pr[r] * sq) / gap - 1.0;
+                    const double x = (c_root * (double)pr[r] * sq) / gap - 1.0;
                     least = x < 0.0 ? 0 : (x >= (double)n ? n : (int)floor(x) + 1);
                 }
                 int np = keep > least ? keep : least;
@@ -1582,12 +1590,17 @@ extern "C++" template <bool SOLVER>
 static void tree_select_launch(const LzTreeDesc* d, void* stream) {
     const Tree t = no_share(make_tree(d));
     const dim3 grid(gw(d->num_games)), block(kBlock);
-    if (gumbel_set(d))
-        hipLaunchKernelGGL((tree_select_kernel<false, true, SOLVER>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, make_gumbel(d));
+    if (shape_set(d)) {                                            // (shape_check refused a Gumbel descriptor)
+        if (forced_set(d))
+            hipLaunchKernelGGL((tree_select_kernel<true, false, SOLVER, true>), grid, block, 0, as_stream(stream), t, make_forced(d), GumbelArgs{}, make_shape(d));
+        else
+            hipLaunchKernelGGL((tree_select_kernel<false, false, SOLVER, true>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, GumbelArgs{}, make_shape(d));
+    } else if (gumbel_set(d))
+        hipLaunchKernelGGL((tree_select_kernel<false, true, SOLVER>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, make_gumbel(d), ShapeArgs{});
     else if (forced_set(d))
-        hipLaunchKernelGGL((tree_select_kernel<true, false, SOLVER>), grid, block, 0, as_stream(stream), t, make_forced(d), GumbelArgs{});
+        hipLaunchKernelGGL((tree_select_kernel<true, false, SOLVER>), grid, block, 0, as_stream(stream), t, make_forced(d), GumbelArgs{}, ShapeArgs{});
     else
-        hipLaunchKernelGGL((tree_select_kernel<false, false, SOLVER>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, GumbelArgs{});
+        hipLaunchKernelGGL((tree_select_kernel<false, false, SOLVER>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, GumbelArgs{}, ShapeArgs{});
 }
 
 int lz_tree_select(const LzTreeDesc* d, void* stream) {
@@ -1595,6 +1608,7 @@ int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: lz_tree_search only
     if (const int rc = gumbel_check(d)) return rc;
     if (const int rc = solver_check(d)) return rc;
+    if (const int rc = shape_check(d)) return rc;
     if (d->num_games == 0) return LZ_OK;
     if (solver_set(d)) tree_select_launch<true>(d, stream);
     else tree_select_launch<false>(d, stream);
@@ -1649,11 +1663,18 @@ static int tree_finish_impl(const LzTreeDesc* d, const float* temperatures, cons
     if (d->num_games == 0) return LZ_OK;
     if (!(prior_pseudocount >= 0.f) || ((force_uniform || sample_moves) && !uniforms)) return LZ_ERR_ARG;
     if (PRUNE && !(d->forced_k >= 0.0)) return LZ_ERR_ARG;
-    hipLaunchKernelGGL(tree_finish_kernel<PRUNE>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
-                       temperatures, target_temperatures, prior_pseudocount, force_uniform, sample_moves, uniforms, policy_dense, chosen_index, reinterpret_cast<int4*>(chosen_code),
-                       chosen_valid, terminal_mask, root_value, child_count, child_action, child_visits, child_prior,
-                       (int)out_cap, PRUNE ? d->forced_k : 0.0, PRUNE ? d->root_noise : nullptr, child_target_visits,
-                       pruned_visits);
+    if (PRUNE) { if (const int rc = shape_check(d)) return rc; }
+    if (PRUNE && shape_set(d) && (d->puct_shape & kShapeTable))     // the pruning rule under c(T)
+        hipLaunchKernelGGL((tree_finish_kernel<PRUNE, PRUNE>), dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
+                           temperatures, target_temperatures, prior_pseudocount, force_uniform, sample_moves, uniforms, policy_dense, chosen_index, reinterpret_cast<int4*>(chosen_code),
+                           chosen_valid, terminal_mask, root_value, child_count, child_action, child_visits, child_prior,
+                           (int)out_cap, d->forced_k, d->root_noise, child_target_visits, pruned_visits, make_shape(d));
+    else
+        hipLaunchKernelGGL(tree_finish_kernel<PRUNE>, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
+                           temperatures, target_temperatures, prior_pseudocount, force_uniform, sample_moves, uniforms, policy_dense, chosen_index, reinterpret_cast<int4*>(chosen_code),
+                           chosen_valid, terminal_mask, root_value, child_count, child_action, child_visits, child_prior,
+                           (int)out_cap, PRUNE ? d->forced_k : 0.0, PRUNE ? d->root_noise : nullptr, child_target_visits,
+                           pruned_visits, ShapeArgs{});
     return st();
 }
 
@@ -1787,8 +1808,9 @@ static bool tree_gather_path(const LzNetDesc* net, int64_t B) {
 // FORCED: the select kernels of forced playouts (LzTreeDesc.forced_k), the same launch sequence.
 // GUMBEL: the kernels of the Gumbel root search (LzTreeDesc.gumbel_*), the same launch sequence.
 // SOLVER: the kernels of the MCTS-Solver (LzTreeDesc.solver), the same launch sequence with the one-wave step throughout.
-extern "C++" template <bool CAP, bool FORCED, bool GUMBEL = false, bool SOLVER = false>
-static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const ForcedArgs& fa, const GumbelArgs& ga, const SolverArgs& sv, const LzNetDesc* net, int64_t sims, float* lp1,
+// SHAPE: the select steps of first-play urgency and the visit-scaled c (LzTreeDesc.puct_shape), likewise the one-wave step.
+extern "C++" template <bool CAP, bool FORCED, bool GUMBEL = false, bool SOLVER = false, bool SHAPE = false>
+static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const ForcedArgs& fa, const GumbelArgs& ga, const SolverArgs& sv, const ShapeArgs& sh, const LzNetDesc* net, int64_t sims, float* lp1,
                               float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                               float epsilon, void* stream) {
     const int64_t B = d->num_games;
@@ -1812,16 +1834,16 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                     hipLaunchKernelGGL((tree_expand_kernel<false, true, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
                                        lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap, sv);
             } else if (s == 0) {
-                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP, FORCED, GUMBEL, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga, sv);
+                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga, sv, sh);
             } else {
                 (void)lz_prof_aux_begin(0, stream);
-                if (!SOLVER && split_step(t.B))
+                if (!SOLVER && !SHAPE && split_step(t.B))
                     hipLaunchKernelGGL((tree_expand_select_split_kernel<true, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), dim3(kBlock), 0,
                                        as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, cap, fa, ga);
                 else
-                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP, FORCED, GUMBEL, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv);
+                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv, sh);
                 (void)lz_prof_aux_end(0, stream, B);
             }
             if (s < sims)                                           // the leaves of simulation s + 1
@@ -1845,16 +1867,16 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                 hipLaunchKernelGGL((tree_expand_kernel<false, false, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
                                    lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap, sv);
         } else if (s == 0) {
-            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP, FORCED, GUMBEL, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga, sv);
+            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga, sv, sh);
         } else {
             (void)lz_prof_aux_begin(0, stream);                      // no-ops unless lz_prof_enable(1) (never in a capture)
-            if (!SOLVER && split_step(t.B))
+            if (!SOLVER && !SHAPE && split_step(t.B))
                 hipLaunchKernelGGL((tree_expand_select_split_kernel<false, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
                                    t, lp1, lp2, lpmc, values, (int)s, cap, fa, ga);
             else
-                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP, FORCED, GUMBEL, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv);
+                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
+                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv, sh);
             (void)lz_prof_aux_end(0, stream, B);
         }
     }
@@ -1863,24 +1885,25 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
     return st();
 }
 
-// tree_search_launch for the descriptor's options: cap x (forced | Gumbel | neither), with or without the solver
-extern "C++" template <bool SOLVER>
-static int tree_search_dispatch(const LzTreeDesc* d, const Tree& t, const SolverArgs& sv, const LzNetDesc* net, int64_t sims,
+// tree_search_launch for the descriptor's options: cap x (forced | Gumbel | neither), with or without the solver, with or
+// without the PUCT shape (never with Gumbel: shape_check)
+extern "C++" template <bool SOLVER, bool SHAPE = false>
+static int tree_search_dispatch(const LzTreeDesc* d, const Tree& t, const SolverArgs& sv, const ShapeArgs& sh, const LzNetDesc* net, int64_t sims,
                                 float* lp1, float* lp2, float* lpmc, float* values, const float* noise,
                                 int64_t noise_stride, float epsilon, void* stream) {
-    if (gumbel_set(d)) {                                           // (a Gumbel search never mixes Dirichlet noise in)
+    if (!SHAPE && gumbel_set(d)) {                                 // (a Gumbel search never mixes Dirichlet noise in)
         if (cap_set(d))
-            return tree_search_launch<true, false, true, SOLVER>(d, t, make_cap(d), ForcedArgs{}, make_gumbel(d), sv, net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
-        return tree_search_launch<false, false, true, SOLVER>(d, t, CapArrays{}, ForcedArgs{}, make_gumbel(d), sv, net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
+            return tree_search_launch<true, false, !SHAPE, SOLVER, false>(d, t, make_cap(d), ForcedArgs{}, make_gumbel(d), sv, sh, net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
+        return tree_search_launch<false, false, !SHAPE, SOLVER, false>(d, t, CapArrays{}, ForcedArgs{}, make_gumbel(d), sv, sh, net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
     }
     if (forced_set(d)) {
         if (cap_set(d))
-            return tree_search_launch<true, true, false, SOLVER>(d, t, make_cap(d), make_forced(d), GumbelArgs{}, sv, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-        return tree_search_launch<false, true, false, SOLVER>(d, t, CapArrays{}, make_forced(d), GumbelArgs{}, sv, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+            return tree_search_launch<true, true, false, SOLVER, SHAPE>(d, t, make_cap(d), make_forced(d), GumbelArgs{}, sv, sh, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_launch<false, true, false, SOLVER, SHAPE>(d, t, CapArrays{}, make_forced(d), GumbelArgs{}, sv, sh, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
     }
     if (cap_set(d))
-        return tree_search_launch<true, false, false, SOLVER>(d, t, make_cap(d), ForcedArgs{}, GumbelArgs{}, sv, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    return tree_search_launch<false, false, false, SOLVER>(d, t, CapArrays{}, ForcedArgs{}, GumbelArgs{}, sv, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_launch<true, false, false, SOLVER, SHAPE>(d, t, make_cap(d), ForcedArgs{}, GumbelArgs{}, sv, sh, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    return tree_search_launch<false, false, false, SOLVER, SHAPE>(d, t, CapArrays{}, ForcedArgs{}, GumbelArgs{}, sv, sh, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
 }
 
 static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t sims, float* planes, float* lp1,
@@ -1889,6 +1912,7 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     if (!tree_ok(d) || !net || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
     if (const int grc = gumbel_check(d)) return grc;
     if (const int src = solver_check(d)) return src;
+    if (const int hrc = shape_check(d)) return hrc;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
@@ -1898,9 +1922,15 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     // function of the packed state alone.  The step-by-step entry points (external evaluators) and the two-wave split
     // step (where the descent runs beside the expansion that inserts into the index) keep the index but do not look it up.
     // with the solver always the one-wave step (so the position index is looked up at every launch size)
+    // ... and likewise with the PUCT shape
+    if (shape_set(d)) {
+        if (solver_set(d))
+            return tree_search_dispatch<true, true>(d, make_tree(d), make_solver(d), make_shape(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_dispatch<false, true>(d, make_tree(d), SolverArgs{}, make_shape(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    }
     if (solver_set(d))
-        return tree_search_dispatch<true>(d, make_tree(d), make_solver(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    return tree_search_dispatch<false>(d, split_step(B) ? no_share(make_tree(d)) : make_tree(d), SolverArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+        return tree_search_dispatch<true>(d, make_tree(d), make_solver(d), ShapeArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    return tree_search_dispatch<false>(d, split_step(B) ? no_share(make_tree(d)) : make_tree(d), SolverArgs{}, ShapeArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
 }
 
 // lz_net.hip (internal): the checks of lz_net_forward_packed_multi_f16 on its networks
@@ -1917,6 +1947,9 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
     if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: likewise
+    if (const int hrc = shape_check(d)) return hrc;
+    const bool shaped = shape_set(d);                               // the PUCT shape: the one-wave step's two COMPACT forms
+    const ShapeArgs sh = shaped ? make_shape(d) : ShapeArgs{};
     int rc = lz_net_multi_validate(nets, num_nets);
     if (rc) return rc;
     const int64_t B = d->num_games, G = d->seg_games;
@@ -1925,7 +1958,7 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
     if (d->sym_mode != 0) return LZ_ERR_UNSUPPORTED;                // symmetric evaluation: one network per search only
     rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
     if (rc) return rc;
-    const Tree t = split_step(B) ? no_share(make_tree(d)) : make_tree(d);
+    const Tree t = !shaped && split_step(B) ? no_share(make_tree(d)) : make_tree(d);
     const int64_t R = num_nets + 1;
     auto scan = [&](int64_t s) {
         hipLaunchKernelGGL(tree_live_scan_seg_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t, (int)G, num_nets,
@@ -1943,16 +1976,23 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
             else
                 hipLaunchKernelGGL((tree_expand_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
                                    lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, CapArrays{}, SolverArgs{});
+        } else if (shaped) {
+            if (s == 0)
+                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, false, false, false, false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{}, sh);
+            else
+                hipLaunchKernelGGL((tree_expand_select_kernel<false, true, false, false, false, false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
+                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{}, sh);
         } else if (s == 0) {
             hipLaunchKernelGGL((tree_expand_select_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{});
+                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{}, ShapeArgs{});
         } else {
             if (split_step(t.B))
                 hipLaunchKernelGGL((tree_expand_select_split_kernel<true>), dim3(gw2(t.B)), dim3(kBlock), 0,
                                    as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{});
             else
                 hipLaunchKernelGGL((tree_expand_select_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{});
+                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{}, ShapeArgs{});
         }
         if (s < sims) scan(s + 1);                                  // the leaves of simulation s + 1
     }
@@ -2102,6 +2142,7 @@ int lz_tree_wave_select(const LzTreeDesc* d, const LzTreeWaveDesc* w, int64_t si
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
     if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: likewise
+    if (shape_set(d)) return LZ_ERR_UNSUPPORTED;                   // the PUCT shape: likewise
     if (d->num_games == 0) return LZ_OK;
     const Tree t = make_tree(d);
     const WaveArrays a = make_wave(w);
@@ -2130,7 +2171,7 @@ int lz_tree_search_waves(const LzTreeDesc* d, const LzTreeWaveDesc* w, const LzN
                          float* lp1, float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                          float epsilon, int continue_trees, int skip_roots, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || !net || sims < 0 || waves < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
-    if (forced_set(d) || gumbel_set(d) || solver_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (forced_set(d) || gumbel_set(d) || solver_set(d) || shape_set(d)) return LZ_ERR_UNSUPPORTED;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = LZ_OK;

@@ -168,6 +168,7 @@ int lz_tree_search_persistent(const LzTreeDesc* d, const LzNetDesc* net, int64_t
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_search only
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: lz_tree_search only
     if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: lz_tree_search only
+    if (shape_set(d)) return LZ_ERR_UNSUPPORTED;                   // the PUCT shape (FPU, visit-scaled c): lz_tree_search only
     if (!net->wfrag || !net->fparams) return LZ_ERR_ARG;
     if (net->blocks < 0 || net->blocks > 15 || net->num_layers != 2 + 2 * net->blocks) return LZ_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(net->wfrag) & 15) || (reinterpret_cast<uintptr_t>(net->fparams) & 15)) return LZ_ERR_ALIGN;

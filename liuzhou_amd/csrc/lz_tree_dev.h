@@ -104,6 +104,17 @@ struct ForcedArgs { double k; int* count; };
 // Optional MCTS-Solver (LzTreeDesc.solver / root_proven / solver_count): handed over the same way, read only by the SOLVER
 // instantiations of the select / expand kernels.
 struct SolverArgs { int* root_proven; int* count; };
+// Optional PUCT shape (LzTreeDesc.puct_shape / fpu_* / cpuct_table*): handed over the same way, read only by the SHAPE
+// instantiations of the select / expand + select kernels and of the pruning finish.  flags bit 0: first-play urgency -- an
+// unvisited, undecided child scores q = f = max(V - r * sqrt(S / 2^30), -1) instead of 0, with V = W_v / n_v the node's own
+// mean in its mover's frame (root: root_W / root_visits; below: the incoming edge's W / n; n_v == 0: root_init_value),
+// S = sum over the visited children of (uint64)((double)P * 2^30) (an integer sum: order-independent) and r = fpu_root at
+// the root, fpu below it.  flags bit 1: c = table[min(n_v, table_len - 1)] instead of c_puct; the table is built on the
+// host (no log on the device: one ulp could flip an exact tie).  A shaped level always takes the double arithmetic, and a
+// shaped search the one-wave step at every launch size: the two-wave split kernel has no SHAPE instantiation.
+struct ShapeArgs { double fpu, fpu_root; const double* table; int flags, table_len; };
+constexpr int kShapeFpu = 1, kShapeTable = 2;
+constexpr double kShapeFix = 1073741824.0;      // 2^30: the fixed point of S
 // Optional Gumbel root search (LzTreeDesc.gumbel_*): handed over the same way, read only by the GUMBEL instantiations of
 // the select / expand + select kernels, by the root-step snapshot and by the Gumbel finish.  FORCED and GUMBEL exclude
 // each other (two rules for the same level).
@@ -498,12 +509,19 @@ __device__ __forceinline__ int solver_climb(const Tree& t, int g, int lane, cons
 // the children decided with x = -1 are no candidates (unless all are), a decided child scores with q = x at any visit count,
 // and the descent ends at a decided edge -- terminal or proven -- with the value in its info bits.  These levels always take
 // the double arithmetic (the single-precision argmax's bound is derived for q = W / N only).
-template <bool FORCED = false, bool GUMBEL = false, bool SOLVER = false>
+// SHAPE (first-play urgency and the visit-scaled c, `sh`: see ShapeArgs; every level that PUCT decides, so neither a forced
+// root level nor a child the solver takes outright): three more loads per descent (root_W, root_init_value -- both next
+// to the root's run -- and per level the table entry, next to that level's run), the incoming edge's W broadcast with the
+// edge, and per level with an unvisited candidate one integer wave sum over both slots, a division and a square root.
+template <bool FORCED = false, bool GUMBEL = false, bool SOLVER = false, bool SHAPE = false>
 __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, const RootInfo& root, int wait_edge = -1,
                                             int nolegal_edge = -1, volatile int* flag = nullptr, double forced_k = 0.0,
                                             int* forced_count = nullptr, const GumbelArgs* gum = nullptr,
-                                            bool gum_on = false LZ_TSTAMP_ARG) {
+                                            bool gum_on = false, const ShapeArgs* sh = nullptr LZ_TSTAMP_ARG) {
+    static_assert(!(SHAPE && GUMBEL), "the Gumbel root search has no shaped form");
     if (t.root_terminal[g]) { if (lane == 0) t.leaf_kind[g] = kLeafInactive; return; }
+    double node_W = 0.0, init_v = 0.0;                         // SHAPE: the current node's own value sum; V of an unvisited node
+    if (SHAPE && (sh->flags & kShapeFpu)) { node_W = t.root_W[g]; init_v = (double)t.root_init_value[g]; }
     const Node* nodes = t.nodes + (size_t)g * t.node_cap;
     const Edge* edges = t.edges;                               // pool indices
     int* path = t.path + (size_t)g * t.path_cap;
@@ -529,6 +547,9 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
             const int k = r * kWave + lane;
             if (k < ne) mine[r] = load_edge(&run[k]);
         }
+        double c_level = t.c_puct;                             // SHAPE: c(n_v), in flight together with the run
+        if (SHAPE && (sh->flags & kShapeTable))
+            c_level = sh->table[parent_n < sh->table_len - 1 ? (parent_n > 0 ? parent_n : 0) : sh->table_len - 1];
 #ifdef LZ_EXP_TREE_STAMPS
         if (LZ_TSTAMP_ON(g)) { LZ_TCLOCK(g, lv_t1) LZ_TADD(g, 16, lv_t1 - lv_t0) lv_t0 = lv_t1; }   // wait for the run
 #endif
@@ -586,7 +607,7 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
             chosen = gumbel_argmax(s, cand, lane);
             if (chosen < 0) break;                                 // every score NaN
         }
-        if (!SOLVER && (!FORCED || chosen < 0) && (!GUMBEL || chosen < 0) && t.fast_select) {
+        if (!SOLVER && !SHAPE && (!FORCED || chosen < 0) && (!GUMBEL || chosen < 0) && t.fast_select) {
             const float sqf = sqrtf((float)(parent_n > 1 ? parent_n : 1));
             const float cf = (float)t.c_puct;
             float fs[2] = {-INFINITY, -INFINITY};
@@ -641,6 +662,31 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
         }
         if (chosen < 0) {
             const double sq = sqrt((double)(parent_n > 1 ? parent_n : 1));
+            double fpu_q = 0.0;                                    // SHAPE: q of an unvisited, undecided child
+            if (SHAPE && (sh->flags & kShapeFpu)) {
+                bool fresh = false;                                // a candidate that will score with f
+                uint64_t s = 0;                                    // this lane's share of S, both slots
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    if (r == 1 && ne <= kWave) break;
+                    if (r * kWave + lane < ne) {
+                        const bool dec = SOLVER && (edge_info(mine[r].n_info) & kInfoDecided) != 0;
+                        if (edge_n(mine[r].n_info) > 0) s += (uint64_t)((double)mine[r].P * kShapeFix);
+                        else fresh = fresh || (!dec && (!SOLVER || cand[r]));
+                    }
+                }
+                if (__ballot(fresh) != 0ull) {                     // wave-uniform: fully visited levels skip the arithmetic
+                    // 64-bit integer sum over the wave in three 20-bit pieces (each piece's sum stays below 2^31)
+                    const int s0 = lzw::lane_bcast(lzw::wave_incl_scan((int)(s & 0xFFFFFu)), kWave - 1);
+                    const int s1 = lzw::lane_bcast(lzw::wave_incl_scan((int)((s >> 20) & 0xFFFFFu)), kWave - 1);
+                    const int s2 = lzw::lane_bcast(lzw::wave_incl_scan((int)(s >> 40)), kWave - 1);
+                    const uint64_t S = (uint64_t)(uint32_t)s0 + ((uint64_t)(uint32_t)s1 << 20) + ((uint64_t)(uint32_t)s2 << 40);
+                    const double V = parent_n > 0 ? node_W / (double)parent_n : init_v;
+                    const double red = (depth == 0 ? sh->fpu_root : sh->fpu) * sqrt((double)S / kShapeFix);
+                    fpu_q = V - red;
+                    if (fpu_q < -1.0) fpu_q = -1.0;
+                }
+            }
             double best = -INFINITY;
             int best_k = -1;
 #pragma unroll
@@ -656,8 +702,10 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
                         const double mv = mine[r].W / (double)n;
                         const int child_player = (edge_info(mine[r].n_info) & kInfoWhite) ? -1 : 1;
                         q = child_player == node_player ? mv : -mv;
+                    } else if (SHAPE) {
+                        q = fpu_q;
                     }
-                    const double u = t.c_puct * (double)mine[r].P * sq / (1.0 + (double)n);
+                    const double u = (SHAPE ? c_level : t.c_puct) * (double)mine[r].P * sq / (1.0 + (double)n);
                     const double sc = q + u;
                     if (sc > best) { best = sc; best_k = k; }
                 }
@@ -700,6 +748,10 @@ __device__ __forceinline__ void tree_select(const Tree& t, int g, int lane, cons
         }
         if (c_child < 0) { kind = kLeafExpand; leaf_action = c_meta & 0xFF; break; }
         node_state = load_state(&nodes[c_child].state);     // in flight together with the next level's edges
+        if (SHAPE && (sh->flags & kShapeFpu)) {              // the child's own value sum, already in its mover's frame
+            const double w = up ? mine[1].W : mine[0].W;
+            node_W = __hiloint2double(lzw::lane_bcast(__double2hiint(w), src), lzw::lane_bcast(__double2loint(w), src));
+        }
         parent_n = edge_n(c_ni);
         node_player = child_player;
         node = c_child;
@@ -1167,6 +1219,20 @@ inline bool gumbel_set(const LzTreeDesc* d) { return d->gumbel_m != 0; }
 inline bool solver_set(const LzTreeDesc* d) { return d->solver != 0; }
 inline int solver_check(const LzTreeDesc* d) { return solver_set(d) && !d->root_proven ? LZ_ERR_ARG : LZ_OK; }
 inline SolverArgs make_solver(const LzTreeDesc* d) { return SolverArgs{d->root_proven, d->solver_count}; }
+inline bool shape_set(const LzTreeDesc* d) { return (d->puct_shape & (kShapeFpu | kShapeTable)) != 0; }
+// LZ_OK, LZ_ERR_ARG (table missing or shorter than 2, reductions negative or not finite) or LZ_ERR_UNSUPPORTED (Gumbel)
+inline int shape_check(const LzTreeDesc* d) {
+    if (!shape_set(d)) return LZ_OK;
+    if ((d->puct_shape & kShapeTable) && (!d->cpuct_table || d->cpuct_table_len < 2)) return LZ_ERR_ARG;
+    if ((d->puct_shape & kShapeFpu) && (!(d->fpu_reduction >= 0.0) || !(d->fpu_root_reduction >= 0.0) ||
+                                        !isfinite(d->fpu_reduction) || !isfinite(d->fpu_root_reduction)))
+        return LZ_ERR_ARG;
+    return gumbel_set(d) ? LZ_ERR_UNSUPPORTED : LZ_OK;
+}
+inline ShapeArgs make_shape(const LzTreeDesc* d) {
+    return ShapeArgs{d->fpu_reduction, d->fpu_root_reduction, d->cpuct_table, d->puct_shape & (kShapeFpu | kShapeTable),
+                     d->cpuct_table_len};
+}
 // LZ_OK, LZ_ERR_ARG (fields out of range / missing arrays) or LZ_ERR_UNSUPPORTED (with forced playouts)
 inline int gumbel_check(const LzTreeDesc* d) {
     if (!gumbel_set(d)) return LZ_OK;

@@ -119,10 +119,16 @@ def _pad16(n: int) -> int:
 class TreeSearchAgent:
     """Checkpoint + the full-tree search (`PortableTreeMCTS`), as the reference's `_PortableEvalAgent`
     (eval_checkpoint.py:324-445): a fresh tree for every move (no subtree reuse), no Dirichlet noise, and the pick by
-    `sample_moves` (visit counts ^ 1/temperature) or the N -> Q -> P -> index order of the deterministic pick."""
+    `sample_moves` (visit counts ^ 1/temperature) or the N -> Q -> P -> index order of the deterministic pick.
+    `fpu_reduction` / `fpu_root_reduction` / `cpuct_log` / `cpuct_base`: first-play urgency and the visit-scaled
+    exploration constant of its searches (tree_engine.PortableTreeMCTS; off by default), so that the arena searches the way
+    self-play does.  Agents share one multi-network engine only when these are equal."""
 
     def __init__(self, model, device, mcts_simulations: int, temperature: float = 0.1, sample_moves: bool = False,
-                 seed: int = 0) -> None:
+                 seed: int = 0, fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
+                 cpuct_log: float = 0.0, cpuct_base: float = 19652.0) -> None:
+        from .puct_shape import parse_puct_shape
+        self.puct_shape = parse_puct_shape(fpu_reduction, fpu_root_reduction, cpuct_log, cpuct_base)
         dev = torch.device(device)
         from .net_hip import fused_supported
         self.net = FusedNet(model.to(dev).eval(), dev) if fused_supported(model) else model.to(dev).eval()
@@ -148,7 +154,8 @@ def _tree_engine(agents: Sequence[TreeSearchAgent], slots: int):
     from .tree_engine import PortableTreeMCTS
     a = agents[0]
     nets = [x.net for x in agents]
-    kw = dict(add_dirichlet_noise=False, sample_moves=a.sample_moves, reuse_tree=False, compact_evals=True, seed=a.seed)
+    kw = dict(add_dirichlet_noise=False, sample_moves=a.sample_moves, reuse_tree=False, compact_evals=True, seed=a.seed,
+              **a.puct_shape.kwargs())
     if len(agents) == 1:
         return PortableTreeMCTS(nets[0], slots, a.sims, a.device, **kw)
     return PortableTreeMCTS(nets, slots * len(agents), a.sims, a.device, segment_games=slots, **kw)
@@ -159,7 +166,7 @@ def _joint_engine(group: Sequence[TreeSearchAgent], slots: int):
     Keyed by the networks themselves (the cached engine holds them, so no other object can take their ids while it is
     kept) and the search settings; one joint engine per agent: another group replaces it."""
     a = group[0]
-    key = ("joint", tuple(id(x.net) for x in group), int(slots), a.sims, a.sample_moves, a.seed)
+    key = ("joint", tuple(id(x.net) for x in group), int(slots), a.sims, a.sample_moves, a.seed, a.puct_shape.key())
     eng = a._engines.get(key)
     if eng is None or any(x is not y for x, y in zip(eng.nets, [x.net for x in group])):
         for k in [k for k in a._engines if isinstance(k, tuple) and k[0] == "joint"]:
@@ -172,7 +179,8 @@ def _joinable(agents: Sequence[TreeSearchAgent]) -> bool:
     """Tree agents one engine can search together: the same search settings (the networks may differ in anything)."""
     a = agents[0]
     return 2 <= len(agents) <= 8 and all(x.sims == a.sims and x.sample_moves == a.sample_moves and x.seed == a.seed and
-                                         x.device == a.device for x in agents)
+                                         x.device == a.device and x.puct_shape.key() == a.puct_shape.key()
+                                         for x in agents)
 
 
 def _play_games(agents: Sequence[Any], player_a: torch.Tensor, player_b: torch.Tensor, a_black: torch.Tensor, device, *,
@@ -350,29 +358,40 @@ SEARCH_BACKENDS = ("v1", "portable")
 
 
 def make_agent(model, search_backend: str, device, mcts_simulations: int, temperature: float, sample_moves: bool,
-               seed: int = 0):
-    """`search_backend` "v1" (root PUCT, RootSearchAgent) or "portable" (the tree search, TreeSearchAgent)."""
+               seed: int = 0, fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
+               cpuct_log: float = 0.0, cpuct_base: float = 19652.0):
+    """`search_backend` "v1" (root PUCT, RootSearchAgent) or "portable" (the tree search, TreeSearchAgent).  The PUCT
+    shape parameters (first-play urgency, visit-scaled cpuct) need the tree search (ValueError with "v1")."""
+    from .puct_shape import parse_puct_shape
+    shape = parse_puct_shape(fpu_reduction, fpu_root_reduction, cpuct_log, cpuct_base)
     if search_backend == "v1":
+        if shape.on:
+            raise ValueError("first-play urgency / the visit-scaled cpuct need the tree backend (search_backend "
+                             "'portable'), not the root-PUCT search")
         return RootSearchAgent(model, device, mcts_simulations, temperature, sample_moves)
     if search_backend == "portable":
-        return TreeSearchAgent(model, device, mcts_simulations, temperature, sample_moves, seed=seed)
+        return TreeSearchAgent(model, device, mcts_simulations, temperature, sample_moves, seed=seed, **shape.kwargs())
     raise ValueError(f"search_backend must be one of {SEARCH_BACKENDS}, got {search_backend!r}")
 
 
 def evaluate_checkpoint(challenger_checkpoint: str, opponent_checkpoint: Optional[str] = None, *, num_games: int = 200,
                         device: str = "cuda:0", mcts_simulations: int = 64, temperature: float = 0.1,
                         sample_moves: bool = False, opening_random_moves: int = 0, max_game_plies: int = 512,
-                        seed: int = 0, search_backend: str = "v1") -> Dict[str, Any]:
+                        seed: int = 0, search_backend: str = "v1", fpu_reduction: Optional[float] = None,
+                        fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
+                        cpuct_base: float = 19652.0) -> Dict[str, Any]:
     """vs-previous (two checkpoints) or vs-random (opponent None) probe; payload as eval_checkpoint.py:139-154.
     `search_backend`: "v1" (root PUCT) or "portable" (the tree search, both sides in one engine)."""
     games = int(num_games) if int(num_games) % 2 == 0 else max(2, (int(num_games) // 2) * 2)   # even (:48-54)
     if search_backend not in SEARCH_BACKENDS:
         raise ValueError(f"search_backend must be one of {SEARCH_BACKENDS}, got {search_backend!r}")
+    shape = dict(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
+                 cpuct_base=cpuct_base)
     chall = make_agent(load_checkpoint_model(challenger_checkpoint), search_backend, device, mcts_simulations,
-                       temperature, sample_moves, seed)
+                       temperature, sample_moves, seed, **shape)
     opp = RandomAgent() if not opponent_checkpoint else make_agent(
         load_checkpoint_model(opponent_checkpoint), search_backend, device, mcts_simulations, temperature, sample_moves,
-        seed)
+        seed, **shape)
     stats = play_matches(chall, opp, games, device, opening_random_moves=opening_random_moves,
                          max_game_plies=max_game_plies, seed=seed)
     payload = stats.to_payload("vs_previous" if opponent_checkpoint else "vs_random")

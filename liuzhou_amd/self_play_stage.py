@@ -83,6 +83,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     gumbel_meta: Optional[Dict[str, Any]] = None
     td_meta: Optional[Dict[str, Any]] = None
     solver_meta = False
+    shape_meta: Optional[Dict[str, Any]] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -111,6 +112,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         if isinstance(wtd, dict) and td_meta is None:
             td_meta = {"td_lambda": float(wtd.get("td_lambda", 1.0))}
         solver_meta = solver_meta or bool((wm.get("metadata") or {}).get("mcts_solver"))
+        wsh = (wm.get("metadata") or {}).get("puct_shape")
+        if isinstance(wsh, dict) and shape_meta is None:
+            shape_meta = {k: wsh.get(k) for k in ("fpu_reduction", "fpu_root_reduction", "cpuct_log", "cpuct_base")}
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -137,6 +141,8 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         meta["value_target"] = td_meta
     if solver_meta:                     # MCTS-Solver: on (its counters travel in the merged mcts_counters)
         meta["mcts_solver"] = True
+    if shape_meta is not None:          # first-play urgency / visit-scaled cpuct: the four values the searches ran with
+        meta["puct_shape"] = shape_meta
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -162,7 +168,9 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         playout_cap_full_prob: float = 1.0, forced_playouts_k: float = 0.0,
                         gumbel_considered: int = 0, gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0,
                         value_target_lambda: float = 1.0,
-                        mcts_solver: bool = False) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        mcts_solver: bool = False, fpu_reduction: Optional[float] = None,
+                        fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
+                        cpuct_base: float = 19652.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
@@ -172,7 +180,12 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
     `gumbel_c_visit` / `gumbel_c_scale` (tree backend, Gumbel root search with Sequential Halving; a Gumbel search never
     mixes Dirichlet noise into the root priors, whatever `add_dirichlet_noise` says) only when gumbel_considered > 0, and
     `value_target_lambda` (tree backend, TD(lambda) value targets from the searches' root values; 1 = off) only when < 1,
-    and `mcts_solver` (tree backend, the MCTS-Solver) only when it is on."""
+    and `mcts_solver` (tree backend, the MCTS-Solver) only when it is on, and `fpu_reduction` / `fpu_root_reduction` /
+    `cpuct_log` / `cpuct_base` (tree backend, first-play urgency and the visit-scaled exploration constant) only when one
+    of the two halves is on."""
+    from .tree_engine import puct_shape_refusal
+    shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
+                               cpuct_base=cpuct_base, gumbel_considered=gumbel_considered, search_backend=search_backend)
     solver = bool(mcts_solver)
     if solver and str(search_backend).strip().lower() not in ("portable", "tree"):
         raise ValueError(f"the MCTS-Solver needs the tree backend, not the root-PUCT search ({search_backend!r}): it marks "
@@ -238,7 +251,7 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
                 "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
             **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-            **({"mcts_solver": True} if solver else {}))
+            **({"mcts_solver": True} if solver else {}), **shape.kwargs())
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

@@ -583,7 +583,9 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
                          forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
                          gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0,
-                         mcts_solver: bool = False) -> Dict[str, Any]:
+                         mcts_solver: bool = False, fpu_reduction: Optional[float] = None,
+                         fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
+                         cpuct_base: float = 19652.0) -> Dict[str, Any]:
     """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
     `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
     tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on.
@@ -596,7 +598,13 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
     tree_engine.self_play_tree_gpu; they travel in `value_targets`.  Recorded in the manifests'
     metadata["value_target"] when on.
     `mcts_solver` (tree backend only): the MCTS-Solver, see tree_engine.self_play_tree_gpu.  Recorded in the manifests'
-    metadata["mcts_solver"] when on."""
+    metadata["mcts_solver"] when on.
+    `fpu_reduction` (None = off), `fpu_root_reduction`, `cpuct_log` (0 = off), `cpuct_base` (tree backend only): first-play
+    urgency and the visit-scaled exploration constant, see tree_engine.self_play_tree_gpu.  The four values are recorded in
+    the manifests' metadata["puct_shape"] when either half is on."""
+    from .tree_engine import puct_shape_refusal
+    shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
+                               cpuct_base=cpuct_base, gumbel_considered=gumbel_considered, search_backend=search_backend)
     solver = bool(mcts_solver)
     if solver and str(search_backend).strip().lower() not in ("portable", "tree"):
         raise ValueError(f"the MCTS-Solver needs the tree backend, not the root-PUCT search ({search_backend!r}): it marks "
@@ -697,7 +705,7 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                               "gumbel_c_visit": float(gumbel_c_visit),
                                               "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
                                           **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-                                          **({"mcts_solver": True} if solver else {}), **common)
+                                          **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
                                     sparse_top_k=int(sparse_top_k), row_log=row_log, **common)
@@ -720,7 +728,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        **({"gumbel": {"considered": int(gumbel_considered), "c_visit": float(gumbel_c_visit),
                                       "c_scale": float(gumbel_c_scale)}} if gumbel else {}),
                        **({"value_target": {"td_lambda": float(value_target_lambda)}} if td else {}),
-                       **({"mcts_solver": True} if solver else {})}
+                       **({"mcts_solver": True} if solver else {}),
+                       **({"puct_shape": shape.meta()} if shape.on else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

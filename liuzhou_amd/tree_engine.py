@@ -29,6 +29,7 @@ from .gumbel import considered_table, gumbel_on
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput, TOTAL_ACTION_DIM, states_to_model_input, \
     encode_actions_fast
 from .net_hip import DescArray, FusedNet, LzNetDesc, MAX_MULTI_NETS, multi_compatible
+from .puct_shape import CPUCT_BASE_DEFAULT, CPUCT_TABLE_LEN, PuctShape, cpuct_table, parse_puct_shape
 from .self_play_types import SelfPlayV1Stats
 from .streams import CAPTURE_MODE
 from .trajectory_buffer import TensorSelfPlayBatch, TensorTrajectoryBuffer
@@ -60,7 +61,9 @@ class LzTreeDesc(C.Structure):
                 ("gumbel_c_scale", C.c_double)] + \
                [(n, C.c_void_p) for n in ("gumbel_g", "gumbel_table", "gumbel_gl", "gumbel_base", "gumbel_root_base",
                                           "gumbel_root_value", "gumbel_count")] + [("gumbel_stride", C.c_int64)] + \
-               [("solver", C.c_int32), ("root_proven", C.c_void_p), ("solver_count", C.c_void_p)]
+               [("solver", C.c_int32), ("root_proven", C.c_void_p), ("solver_count", C.c_void_p)] + \
+               [("puct_shape", C.c_int32), ("cpuct_table_len", C.c_int32), ("fpu_reduction", C.c_double),
+                ("fpu_root_reduction", C.c_double), ("cpuct_table", C.c_void_p)]
 
 
 def playout_cap_on(fast_simulations: int, full_prob: float, sims: int) -> bool:
@@ -208,6 +211,29 @@ def solver_refusal(*, batch_k=1, several_networks=False, fused=True) -> Optional
             "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else None)
 
 
+def puct_shape_refusal(*, fpu_reduction=None, fpu_root_reduction=None, cpuct_log=0.0, cpuct_base=CPUCT_BASE_DEFAULT,
+                       batch_k=1, fused=True, gumbel_considered=0, search_backend="tree",
+                       persistent: Optional[bool] = None) -> PuctShape:
+    """Validate the PUCT shape parameters (first-play urgency, visit-scaled cpuct) and the configuration they are asked
+    for; returns the parsed PuctShape.  ValueError for a non-finite or negative value, cpuct_base <= 0, fpu_root_reduction
+    without fpu_reduction, and -- only when the shape is on -- for the Gumbel root search, batch_k > 1, the persistent kernel,
+    an external evaluator and the root-PUCT backend: the shaped score lives in the select step of the fused launch-pair
+    tree search, which none of them runs."""
+    shape = parse_puct_shape(fpu_reduction, fpu_root_reduction, cpuct_log, cpuct_base)
+    if not shape.on:
+        return shape
+    persistent = _persistent_default() if persistent is None else bool(persistent)
+    why = ("the root-PUCT search (it needs the tree backend)"
+           if str(search_backend).strip().lower() not in ("portable", "tree") else
+           "the Gumbel root search (its root level has a rule of its own)" if int(gumbel_considered) > 0 else
+           "batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
+           "an external evaluator (split-phase path)" if not fused else
+           "the persistent search kernel (LZ_TREE_PERSISTENT)" if persistent else None)
+    if why is not None:
+        raise ValueError(f"first-play urgency / the visit-scaled cpuct are not supported with {why}")
+    return shape
+
+
 def forced_playouts_on(k) -> bool:
     """Validate `forced_playouts_k`: 0 = off, a positive finite number = on; negative or non-finite is a ValueError."""
     k = float(k)
@@ -341,6 +367,9 @@ class TreeEngine:
         self.root_proven: Optional[torch.Tensor] = None
         self.solver_count: Optional[torch.Tensor] = None
         self.solver_overrides: Optional[torch.Tensor] = None
+        # PUCT shape (set_puct_shape; LzTreeDesc.puct_shape ..): the c(n) table exists only once that half is switched on
+        self.puct_shape = parse_puct_shape()
+        self.cpuct_table: Optional[torch.Tensor] = None
         self.segment_games = None if segment_games is None else int(segment_games)
         self.num_segments = 1
         if self.segment_games is not None:
@@ -463,6 +492,8 @@ class TreeEngine:
             raise ValueError("the Gumbel root search is not supported with several networks in one search")
         if on and self.forced_k > 0.0:
             raise ValueError("the Gumbel root search and forced playouts are two rules for the same root level")
+        if on and self.puct_shape.on:
+            raise ValueError("the Gumbel root search is not supported with first-play urgency / the visit-scaled cpuct")
         d = self.desc
         self.gumbel_m = int(considered)
         self.gumbel_c_visit, self.gumbel_c_scale = float(c_visit), float(c_scale)
@@ -483,6 +514,36 @@ class TreeEngine:
         for name in ("g", "table", "gl", "base", "root_base", "root_value", "count"):
             setattr(d, "gumbel_" + name, self.gumbel[name].data_ptr())
         self.persistent = False           # the persistent kernel refuses the descriptor: the launch-pair search
+
+    def set_puct_shape(self, fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
+                       cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT,
+                       table_len: int = CPUCT_TABLE_LEN) -> None:
+        """First-play urgency and the visit-scaled exploration constant (LzTreeDesc.puct_shape; off
+        by default).  `fpu_reduction` (None: off; 0.0 is on): an unvisited child scores the node's own mean value minus
+        fpu_reduction * sqrt(explored prior mass), clamped at -1; `fpu_root_reduction` (None: fpu_reduction) is the root's
+        reduction.  `cpuct_log` > 0: c(n) = exploration_weight + cpuct_log * ln((n + cpuct_base + 1) / cpuct_base) from a
+        table of `table_len` float64 entries built by puct_shape.cpuct_table and uploaded here once (visit counts beyond it
+        take the last entry).  select() / search() / search_multi honour both, finish() with forced playouts prunes under
+        c(root visits).  Everything off: nothing is allocated and the descriptor is as before.  Must be set before a search
+        is captured into a graph."""
+        shape = parse_puct_shape(fpu_reduction, fpu_root_reduction, cpuct_log, cpuct_base)
+        if shape.on and self.batch_k > 1:
+            raise ValueError("first-play urgency / the visit-scaled cpuct are not supported by the legacy waves (batch_k > 1)")
+        if shape.on and self.gumbel_m > 0:
+            raise ValueError("first-play urgency / the visit-scaled cpuct are not supported with the Gumbel root search")
+        d = self.desc
+        self.puct_shape = shape
+        d.puct_shape = shape.flags
+        d.fpu_reduction, d.fpu_root_reduction = shape.fpu_reduction, shape.fpu_root_reduction
+        if shape.table:
+            tab = cpuct_table(float(d.exploration_weight), shape.cpuct_log, shape.cpuct_base, int(table_len))
+            self.cpuct_table = torch.tensor(tab, dtype=torch.float64, device=self.device)
+            d.cpuct_table, d.cpuct_table_len = self.cpuct_table.data_ptr(), len(tab)
+        else:
+            self.cpuct_table = None
+            d.cpuct_table, d.cpuct_table_len = None, 0
+        if shape.on:
+            self.persistent = False       # the persistent kernel refuses the descriptor: the launch-pair search
 
     def set_solver(self, on: bool = True) -> None:
         """MCTS-Solver (LzTreeDesc.solver; off by default): the expand step marks proven edges and carries them up the
@@ -819,7 +880,10 @@ class PortableTreeMCTS:
                  collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none",
                  segment_games: Optional[int] = None, multi_launch: bool = True, fast_simulations: int = 0,
                  full_prob: float = 1.0, forced_playouts_k: float = 0.0, gumbel_considered: int = 0,
-                 gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0, solver: bool = False) -> None:
+                 gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0, solver: bool = False,
+                 fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
+                 cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT,
+                 cpuct_table_len: int = CPUCT_TABLE_LEN) -> None:
         """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
         searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
         FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
@@ -868,7 +932,13 @@ class PortableTreeMCTS:
         move or no-capture limit -- are marked on the edges and carried up as far as they decide the parent; decided children
         stop being searched, and the played move never throws a proven win away (nor picks a proven loss next to another
         move).  The outputs gain `root_proven`; `solver_counts` sums proofs, decided roots and changed picks.  Composes with
-        the cap, forced playouts, Gumbel, symmetric evaluation, shared leaves and tree reuse; refused where the cap is."""
+        the cap, forced playouts, Gumbel, symmetric evaluation, shared leaves and tree reuse; refused where the cap is.
+        `fpu_reduction` (None = off, 0.0 = on without a reduction), `fpu_root_reduction` (None = fpu_reduction), `cpuct_log`
+        (0 = off), `cpuct_base`: first-play urgency and the visit-scaled exploration constant (TreeEngine.set_puct_shape,
+        DESIGN.md section 16) on every level that PUCT decides.  Either half works without the other.  Composes with the cap,
+        forced playouts (the pruning rule then uses c(root visits)), the solver, several networks in one launch, symmetric
+        evaluation, shared leaves and tree reuse; refused with the Gumbel root search, batch_k > 1, an external evaluator
+        and the persistent kernel (ValueError).  Such a search runs the one-wave tree step at every launch size."""
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
         self.solver = bool(solver)
@@ -921,6 +991,9 @@ class PortableTreeMCTS:
         self.fused_multi = self.multi and bool(multi_launch) and multi_compatible(self.nets)
         self.fused = isinstance(net, FusedNet) and (not self.multi or self.fused_multi)
         self._desc_array = DescArray(self.nets) if self.fused_multi else None
+        self.puct_shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction,
+                                             cpuct_log=cpuct_log, cpuct_base=cpuct_base, batch_k=batch_k,
+                                             fused=self.fused, gumbel_considered=gumbel_considered if self.gumbel else 0)
         self.reuse_tree = bool(reuse_tree)
         self.batch_k = max(1, int(batch_k))
         env_c = os.environ.get("LZ_TREE_COMPACT", "").strip()
@@ -951,6 +1024,8 @@ class PortableTreeMCTS:
         self._roots_decided = torch.zeros((1,), dtype=torch.int64, device=self.engine.device)
         if self.solver:
             self.engine.set_solver(True)
+        if self.puct_shape.on:
+            self.engine.set_puct_shape(**self.puct_shape.kwargs(), table_len=int(cpuct_table_len))
         if not self.fused:
             if self.batch_k > 1:
                 raise ValueError("an external evaluator supports batch_k = 1 only")
@@ -1453,6 +1528,7 @@ class DualStreamTreeMCTS:
         self.forced = self.parts[0].forced
         self.gumbel = self.parts[0].gumbel
         self.solver = self.parts[0].solver
+        self.puct_shape = self.parts[0].puct_shape
         self.full_search = None
         if self.cap:
             self.full_search = torch.zeros((self.B,), dtype=torch.uint8, device=dev)
@@ -1750,7 +1826,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        collect_timing: bool = False, row_log=None, eval_symmetry="none",
                        playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
                        forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
-                       gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0, mcts_solver: bool = False
+                       gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0, mcts_solver: bool = False,
+                       fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
+                       cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT
                        ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
@@ -1785,7 +1863,11 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     `mcts_solver`: MCTS-Solver (PortableTreeMCTS `solver`) in every search: proven wins, draws and losses are marked in the
     tree, decided children stop being searched and the played move never throws a proven win away.  mcts_counters gain
     solver_proofs / solver_roots_decided / solver_pick_overrides.  Fused network and batch_k = 1 only (ValueError
-    otherwise); composes with everything else."""
+    otherwise); composes with everything else.
+    `fpu_reduction` (None = off), `fpu_root_reduction` (None = fpu_reduction), `cpuct_log` (0 = off), `cpuct_base`: first-play
+    urgency and the visit-scaled exploration constant (PortableTreeMCTS) in every search.  Fused
+    network and batch_k = 1 only, not with the Gumbel root search or the persistent kernel (ValueError); composes with
+    everything else.  Off, nothing is allocated and every output is byte-identical."""
     dev = torch.device(device)
     solver = bool(mcts_solver)
     td = td_lambda_on(value_target_lambda)
@@ -1833,6 +1915,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                              policy_target_prior_pseudocount=policy_target_prior_pseudocount)
         if why is not None:
             raise ValueError(f"the Gumbel root search is not supported with {why}")
+    shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
+                               cpuct_base=cpuct_base, batch_k=batch_k, fused=use_fused,
+                               gumbel_considered=gumbel_considered if gumbel else 0)
     if use_fused and persistent_search_available(net, batch_k) and eval_symmetry == "none":
         if cap:
             raise ValueError("playout cap randomization is not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
@@ -1856,6 +1941,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                   gumbel_c_scale=float(gumbel_c_scale))
     if solver:
         kw["solver"] = True
+    kw.update(shape.kwargs())
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a

@@ -33,6 +33,10 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--match_name", default=None)
     ap.add_argument("--output_json", default=None)
+    ap.add_argument("--fpu_reduction", type=float, default=None)         # tree backend: first-play urgency (unset = off)
+    ap.add_argument("--fpu_root_reduction", type=float, default=None)    # ... at the root (default: --fpu_reduction)
+    ap.add_argument("--cpuct_log", type=float, default=0.0)              # tree backend: visit-scaled cpuct (0 = off)
+    ap.add_argument("--cpuct_base", type=float, default=19652.0)
     args, ignored = ap.parse_known_args(argv)
     args.ignored = ignored
     return args
@@ -52,6 +56,10 @@ def main(argv=None) -> int:
                   sample_moves=bool(args.sample_moves), opening_random_moves=args.v1_opening_random_moves, seed=seed)
     if backend != "v1":
         common["search_backend"] = backend
+    if args.fpu_reduction is not None or args.fpu_root_reduction is not None:
+        common.update(fpu_reduction=args.fpu_reduction, fpu_root_reduction=args.fpu_root_reduction)
+    if args.cpuct_log != 0.0:
+        common.update(cpuct_log=args.cpuct_log, cpuct_base=args.cpuct_base)
     out = {"challenger_checkpoint": args.challenger_checkpoint, "previous_checkpoint": args.previous_checkpoint,
            "backend": backend, "mcts_simulations": int(args.mcts_simulations), "seed": seed}
     if args.eval_games_vs_random > 0:

@@ -63,6 +63,15 @@ def parse(argv=None):
     ap.add_argument("--mcts_solver", action="store_true",
                     help="MCTS-Solver (tree backend): mark proven wins, draws and losses in the search tree, stop searching "
                          "decided children and never play away a proven win")
+    ap.add_argument("--fpu_reduction", type=float, default=None,
+                    help="first-play urgency (tree backend): an unvisited child scores the node's own value minus this times "
+                         "sqrt(explored prior mass); unset = off (unvisited children score 0), 0 = the node's value")
+    ap.add_argument("--fpu_root_reduction", type=float, default=None,
+                    help="the reduction at the root (default: --fpu_reduction)")
+    ap.add_argument("--cpuct_log", type=float, default=0.0,
+                    help="visit-scaled exploration (tree backend): c(n) = exploration_weight + cpuct_log * "
+                         "ln((n + cpuct_base + 1) / cpuct_base); 0 = off")
+    ap.add_argument("--cpuct_base", type=float, default=19652.0, help="base of the visit-scaled exploration constant")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -125,7 +134,10 @@ def main(argv=None) -> int:
         playout_cap_fast_simulations=args.playout_cap_fast_simulations, playout_cap_full_prob=args.playout_cap_full_prob,
         forced_playouts_k=args.forced_playouts_k, gumbel_considered=args.gumbel_considered,
         gumbel_c_visit=args.gumbel_c_visit, gumbel_c_scale=args.gumbel_c_scale,
-        value_target_lambda=args.value_target_lambda, **({"mcts_solver": True} if args.mcts_solver else {}))
+        value_target_lambda=args.value_target_lambda, **({"mcts_solver": True} if args.mcts_solver else {}),
+        **({"fpu_reduction": args.fpu_reduction, "fpu_root_reduction": args.fpu_root_reduction}
+           if args.fpu_reduction is not None or args.fpu_root_reduction is not None else {}),
+        **({"cpuct_log": args.cpuct_log, "cpuct_base": args.cpuct_base} if args.cpuct_log != 0.0 else {}))
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
