@@ -285,6 +285,43 @@ LZ_API int lz_wave_td_targets(const uint8_t* done, const uint8_t* was_live, int6
                               const int64_t* step_index_matrix, const int64_t* step_counts, int64_t max_steps,
                               void* stream);
 
+/* Resignation with play-through calibration (v0/python/self_play_runner.py:264-266,325-374; off there by default).
+ * Per live slot and searched ply, with p = plies[g], c = the side to move and v = root_value[g] (the mover's frame):
+ * the ply is ELIGIBLE when the phase is movement, capture selection or counter removal, p >= min_moves and
+ * terminal_mask[g] == 0; it is LOW when it is eligible and v <= threshold in float32 (a NaN is never low).
+ * per_ply == 0: the mover's own counter streak[g, c > 0 ? 0 : 1] = low ? + 1 : 0, an ineligible ply clears both;
+ * per_ply != 0: streak[g, 0] = low ? + 1 : 0 on every searched ply whoever moves (the reference's literal counter).
+ * The slot wants to resign when the ply is low and its counter has reached `consecutive`.  Game id = (slot_game ?
+ * slot_game[g] : g) + game_base plays through iff u(seed, id) < playthrough_fraction, u = one Philox draw of
+ * lz_rng.h (purpose 3, ply 0, index 1023): a pure function of (seed, id), whichever slot, stream or rank seats it.
+ *
+ * lz_wave_resign: after lz_wave_record / lz_wave_note_value, before lz_wave_step_finish, which is then given
+ * terminal_out in place of terminal_mask.  A slot at p == 0 clears its state first (a re-seated slot needs no reset).
+ * A play-through game that wants to resign plays on and latches the first such event: would[g] = c (+1 / -1, 0 =
+ * none), would_ply[g] = p.  Any other game that wants to resign gets resigned[g] = 1.  For every live slot
+ * terminal_out[g] = terminal_mask[g] | resigned[g], was_live[g] = 1, resigned[g] = 0 / 1; a finished slot gets
+ * was_live[g] = 0 and is otherwise untouched.  streak int32[num_slots, 2], would / would_ply int32[num_slots],
+ * terminal_out / was_live / resigned uint8[num_slots].  threshold in [-1, 0), consecutive >= 1, min_moves >= 0,
+ * playthrough_fraction in [0, 1] (LZ_ERR_ARG otherwise).
+ *
+ * lz_wave_resign_book: after lz_wave_step_finish (reseat == 0), before lz_wave_td_targets and lz_wave_log_finished.
+ * For every slot whose game ended this ply (was_live[g] && done[g]) counters int64[8] += {resigned, resigned by
+ * Black, resigned by White, play-through games finished, play-through games that wanted to resign, of those the ones
+ * whose would-be resigner did not lose (false positives), plies[g] of the resigned, plies[g] - would_ply[g] of the
+ * play-through games that wanted to resign}.  The result of a play-through game is formed by the step kernel's own
+ * rule from terminal_out, chosen_valid_mask and the state that kernel left; no trajectory row is read. */
+LZ_API int lz_wave_resign(const uint8_t* done, int64_t num_slots, const int64_t* plies, const int64_t* phase,
+                          const int64_t* current_player, const float* root_value, const uint8_t* terminal_mask,
+                          const int64_t* slot_game, int64_t game_base, uint64_t seed, float threshold,
+                          int64_t min_moves, int32_t consecutive, float playthrough_fraction, int per_ply,
+                          int32_t* streak, int32_t* would, int32_t* would_ply, uint8_t* terminal_out,
+                          uint8_t* was_live, uint8_t* resigned, void* stream);
+LZ_API int lz_wave_resign_book(const LzStateSoA* states, int64_t num_slots, const uint8_t* done,
+                               const uint8_t* was_live, const int64_t* plies, const uint8_t* terminal_out,
+                               const uint8_t* chosen_valid_mask, const uint8_t* resigned, const int32_t* would,
+                               const int32_t* would_ply, const int64_t* slot_game, int64_t game_base, uint64_t seed,
+                               float playthrough_fraction, int64_t* counters, void* stream);
+
 /* lz_wave_reseat: the wave loop of self_play_gpu_runner.py:84-90 starts the next `concurrent_games` games only when the
  * whole wave has finished; here finished slots (done[g] != 0, ascending g) restart from the empty board at once while
  * *budget (games not yet started) lasts: slot_game[g] = (*next_game)++, plies / step_counts = 0, done[g] = 0,

@@ -13,6 +13,7 @@
 #include <mutex>
 #include <vector>
 
+#include "lz_rng.h"
 #include "lz_soa.h"
 #include "lz_wave.h"
 
@@ -1440,6 +1441,101 @@ __global__ __launch_bounds__(kBlock) void wave_td_targets_kernel(
     }
 }
 
+// ---- resignation with play-through calibration (v0/python/self_play_runner.py:325-374 stops a lost game; AlphaZero's
+// safeguard, a share of games that never resigns, measures how often the resigner would not have lost).
+// A resignation is one more bit in the terminal mask the step kernel reads: "the side to move has lost".
+// Does game `game` of the run keyed by `seed` play through?  One Philox draw, a pure function of (seed, game id): purpose
+// 3, ply 0, index 1023 (lz_rng.h lists the index layouts of purpose 3).
+__device__ __forceinline__ bool resign_plays_through(uint64_t seed, int64_t game, float fraction) {
+    return lzrng::u01(lzrng::draw(seed, game, 0, lzrng::kPurposeGumbel, lzrng::kIndexResignPlaythrough, 0u).x) < fraction;
+}
+
+// one lane per slot, after wave_record_kernel / wave_note_value_kernel and before wave_step_finish_kernel (plies[g] is
+// still this search's ply, the state is the searched one)
+__global__ __launch_bounds__(kBlock) void wave_resign_kernel(
+    const uint8_t* __restrict__ done, int64_t G, const int64_t* __restrict__ plies, const int64_t* __restrict__ phase,
+    const int64_t* __restrict__ player, const float* __restrict__ root_value, const uint8_t* __restrict__ terminal,
+    const int64_t* __restrict__ slot_game, int64_t game_base, uint64_t seed, float threshold, int64_t min_moves,
+    int consecutive, float fraction, int per_ply, int32_t* __restrict__ streak, int32_t* __restrict__ would,
+    int32_t* __restrict__ would_ply, uint8_t* __restrict__ terminal_out, uint8_t* __restrict__ was_live,
+    uint8_t* __restrict__ resigned) {
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= G) return;
+    if (done[g] != 0) { was_live[g] = 0; return; }
+    was_live[g] = 1;
+    const int64_t p = plies[g];
+    int s0 = streak[2 * g], s1 = streak[2 * g + 1], wd = would[g], wp = would_ply[g];
+    if (p == 0) { s0 = 0; s1 = 0; wd = 0; wp = -1; }    // a new game in the slot: no reset kernel needed
+    const bool term = terminal[g] != 0;
+    const int64_t ph = phase[g];
+    const int c = player[g] >= 0 ? 1 : -1;
+    const bool eligible = (ph == kMovement || ph == kCaptureSelection || ph == kCounterRemoval) && p >= min_moves && !term;
+    const bool low = eligible && root_value[g] <= threshold;      // a NaN compares false
+    int count;
+    if (per_ply) {                                      // the reference's counter: one per game, whoever moves
+        s0 = low ? s0 + 1 : 0;
+        count = s0;
+    } else if (!eligible) {
+        s0 = 0; s1 = 0; count = 0;
+    } else if (c > 0) {
+        s0 = low ? s0 + 1 : 0; count = s0;
+    } else {
+        s1 = low ? s1 + 1 : 0; count = s1;
+    }
+    int out = 0;
+    if (low && count >= consecutive) {
+        if (resign_plays_through(seed, (slot_game ? slot_game[g] : g) + game_base, fraction)) {
+            if (wd == 0) { wd = c; wp = (int32_t)p; }   // the first such event of a game that plays on
+        } else {
+            out = 1;
+        }
+    }
+    streak[2 * g] = s0;
+    streak[2 * g + 1] = s1;
+    would[g] = wd;
+    would_ply[g] = wp;
+    resigned[g] = (uint8_t)out;
+    terminal_out[g] = (uint8_t)((term || out) ? 1 : 0);
+}
+
+// one lane per slot, after wave_step_finish_kernel (reseat == 0): books the games that ended this ply.  The result is
+// formed by the step kernel's own rule from what that kernel read and left (never from a row: with the playout cap a
+// game may have none).  counters int64[8]: resigned, resigned by Black, by White, play-through games finished, those that
+// wanted to resign, those whose would-be resigner did not lose, sum of plies at resignation, sum of plies played on after
+// the first wish to resign.
+__global__ __launch_bounds__(kBlock) void wave_resign_book_kernel(
+    LzStateSoA s, int64_t G, const uint8_t* __restrict__ done, const uint8_t* __restrict__ was_live,
+    const int64_t* __restrict__ plies, const uint8_t* __restrict__ terminal_out, const uint8_t* __restrict__ cvalid,
+    const uint8_t* __restrict__ resigned, const int32_t* __restrict__ would, const int32_t* __restrict__ would_ply,
+    const int64_t* __restrict__ slot_game, int64_t game_base, uint64_t seed, float fraction,
+    unsigned long long* __restrict__ counters) {
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= G) return;
+    if (was_live[g] == 0 || done[g] == 0) return;
+    const int64_t p = plies[g];
+    if (resigned[g] != 0) {                             // the state is the resigner's: the step kernel did not move
+        atomicAdd(&counters[0], 1ull);
+        atomicAdd(&counters[s.current_player[g] >= 0 ? 1 : 2], 1ull);
+        atomicAdd(&counters[6], (unsigned long long)p);
+    }
+    if (!resign_plays_through(seed, (slot_game ? slot_game[g] : g) + game_base, fraction)) return;
+    atomicAdd(&counters[3], 1ull);
+    const int wd = would[g];
+    if (wd == 0) return;
+    int res = 0;                                        // from Black's frame, as wave_step_finish_kernel forms it
+    if (terminal_out[g] != 0) {
+        res = s.current_player[g] >= 0 ? -1 : 1;
+    } else if (cvalid[g] != 0) {
+        const int64_t ph = s.phase[g];
+        const bool post = ph == kMovement || ph == kCaptureSelection || ph == kCounterRemoval;
+        if (post && popc(cells_equal(s.board + g * kCells, 1)) < kLoseThreshold) res = -1;
+        if (post && popc(cells_equal(s.board + g * kCells, -1)) < kLoseThreshold) res = 1;
+    }
+    atomicAdd(&counters[4], 1ull);
+    if (res != -wd) atomicAdd(&counters[5], 1ull);      // the side that would have resigned drew or won
+    atomicAdd(&counters[7], (unsigned long long)(p - (int64_t)would_ply[g]));
+}
+
 // ---- finished-row log: the rows of a game leave the slot-major live arena for a game-major log the moment the game
 // has ended, so that a consumer can take finished samples away WHILE the wave goes on playing (the worker streams
 // them to the host; v1/python/self_play_worker.py:430-546 only sees its rows after a whole wave has drained).
@@ -1981,6 +2077,41 @@ int lz_wave_td_targets(const uint8_t* done, const uint8_t* was_live, int64_t G, 
     if (!done || !was_live || !q_hist || !step_ply || !hist_len || !value_t || !signs || !step_counts) return LZ_ERR_ARG;
     hipLaunchKernelGGL(wave_td_targets_kernel, dim3(grid_waves(G)), dim3(kBlock), 0, as_stream(stream), done, was_live, G,
                        lambda, q_hist, step_ply, hist_len, Tmax, value_t, signs, step_index, step_counts, max_steps);
+    return launch_status();
+}
+
+int lz_wave_resign(const uint8_t* done, int64_t G, const int64_t* plies, const int64_t* phase,
+                   const int64_t* current_player, const float* root_value, const uint8_t* terminal_mask,
+                   const int64_t* slot_game, int64_t game_base, uint64_t seed, float threshold, int64_t min_moves,
+                   int32_t consecutive, float playthrough_fraction, int per_ply, int32_t* streak, int32_t* would,
+                   int32_t* would_ply, uint8_t* terminal_out, uint8_t* was_live, uint8_t* resigned, void* stream) {
+    if (G < 0 || min_moves < 0 || consecutive < 1 || !(threshold < 0.f && threshold >= -1.f) ||
+        !(playthrough_fraction >= 0.f && playthrough_fraction <= 1.f))
+        return LZ_ERR_ARG;
+    if (G == 0) return LZ_OK;
+    if (!done || !plies || !phase || !current_player || !root_value || !terminal_mask || !streak || !would ||
+        !would_ply || !terminal_out || !was_live || !resigned)
+        return LZ_ERR_ARG;
+    hipLaunchKernelGGL(wave_resign_kernel, dim3(grid_threads(G)), dim3(kBlock), 0, as_stream(stream), done, G, plies,
+                       phase, current_player, root_value, terminal_mask, slot_game, game_base, seed, threshold,
+                       min_moves, (int)consecutive, playthrough_fraction, per_ply, streak, would, would_ply,
+                       terminal_out, was_live, resigned);
+    return launch_status();
+}
+
+int lz_wave_resign_book(const LzStateSoA* s, int64_t G, const uint8_t* done, const uint8_t* was_live,
+                        const int64_t* plies, const uint8_t* terminal_out, const uint8_t* chosen_valid_mask,
+                        const uint8_t* resigned, const int32_t* would, const int32_t* would_ply,
+                        const int64_t* slot_game, int64_t game_base, uint64_t seed, float playthrough_fraction,
+                        int64_t* counters, void* stream) {
+    if (G < 0 || !(playthrough_fraction >= 0.f && playthrough_fraction <= 1.f)) return LZ_ERR_ARG;
+    if (G == 0) return LZ_OK;
+    if (!soa_ok(s) || !done || !was_live || !plies || !terminal_out || !chosen_valid_mask || !resigned || !would ||
+        !would_ply || !counters)
+        return LZ_ERR_ARG;
+    hipLaunchKernelGGL(wave_resign_book_kernel, dim3(grid_threads(G)), dim3(kBlock), 0, as_stream(stream), *s, G, done,
+                       was_live, plies, terminal_out, chosen_valid_mask, resigned, would, would_ply, slot_game,
+                       game_base, seed, playthrough_fraction, reinterpret_cast<unsigned long long*>(counters));
     return launch_status();
 }
 

@@ -102,4 +102,11 @@ LZ_RNG_HD float gumbel_draw(uint64_t seed, int64_t game, int64_t ply, uint32_t k
     return (float)(-log(-log((double)gumbel_u(draw(seed, game, ply, kPurposeGumbel, 1u + k, 0u).x))));
 }
 
+// Index layout of purpose 3 (the two purpose bits are all taken, the 10-bit index field separates the streams):
+//   index 0            the playout cap's full / fast draw of (game, ply)
+//   index 1 + k        the Gumbel variate of child rank k; k < 220 (the action dimension), so indices 1..220
+//   index 1023, ply 0  the resignation play-through draw of a game (wave_resign_kernel, lz_ops.hip): u01(x) < fraction
+// 221..1022 are free.
+constexpr uint32_t kIndexResignPlaythrough = 1023;
+
 }  // namespace lzrng

@@ -84,6 +84,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     td_meta: Optional[Dict[str, Any]] = None
     solver_meta = False
     shape_meta: Optional[Dict[str, Any]] = None
+    resign_meta: Optional[Dict[str, Any]] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -115,6 +116,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         wsh = (wm.get("metadata") or {}).get("puct_shape")
         if isinstance(wsh, dict) and shape_meta is None:
             shape_meta = {k: wsh.get(k) for k in ("fpu_reduction", "fpu_root_reduction", "cpuct_log", "cpuct_base")}
+        wrs = (wm.get("metadata") or {}).get("resign")
+        if isinstance(wrs, dict) and resign_meta is None:
+            resign_meta = {k: wrs.get(k) for k in ("threshold", "min_moves", "consecutive", "playthrough_fraction", "streak")}
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -143,6 +147,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         meta["mcts_solver"] = True
     if shape_meta is not None:          # first-play urgency / visit-scaled cpuct: the four values the searches ran with
         meta["puct_shape"] = shape_meta
+    if resign_meta is not None:         # resignation: its settings, the resigned and the play-through games of all workers
+        from .resign import COUNTER_KEYS, DERIVED_KEYS
+        meta["resign"] = {**resign_meta, **{k: int(merged.mcts_counters.get(k, 0)) for k in COUNTER_KEYS + DERIVED_KEYS}}
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -170,7 +177,9 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         value_target_lambda: float = 1.0,
                         mcts_solver: bool = False, fpu_reduction: Optional[float] = None,
                         fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
-                        cpuct_base: float = 19652.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        cpuct_base: float = 19652.0, resign_threshold: float = 0.0, resign_min_moves: int = 10,
+                        resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
+                        resign_streak: str = "side") -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
@@ -182,7 +191,13 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
     `value_target_lambda` (tree backend, TD(lambda) value targets from the searches' root values; 1 = off) only when < 1,
     and `mcts_solver` (tree backend, the MCTS-Solver) only when it is on, and `fpu_reduction` / `fpu_root_reduction` /
     `cpuct_log` / `cpuct_base` (tree backend, first-play urgency and the visit-scaled exploration constant) only when one
-    of the two halves is on."""
+    of the two halves is on, and `resign_threshold` / `resign_min_moves` / `resign_consecutive` /
+    `resign_playthrough_fraction` / `resign_streak` (tree backend, resignation with play-through calibration) only when
+    resign_threshold < 0."""
+    from .resign import refuse_backend, resign_kwargs
+    resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
+                           resign_streak)
+    refuse_backend(bool(resign), search_backend)
     from .tree_engine import puct_shape_refusal
     shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
                                cpuct_base=cpuct_base, gumbel_considered=gumbel_considered, search_backend=search_backend)
@@ -251,7 +266,7 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
                 "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
             **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-            **({"mcts_solver": True} if solver else {}), **shape.kwargs())
+            **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign)
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

@@ -27,6 +27,7 @@ import torch
 
 from .net import ChessNet
 from .self_play_storage import estimate_bytes_per_sample, plan_sample_ranges, save_self_play_payload, slice_batch_cpu
+from .resign import derive_counters
 from .self_play_types import SelfPlayV1Stats
 from .trajectory_buffer import TensorSelfPlayBatch
 
@@ -115,6 +116,7 @@ def merge_self_play_stats(stats_list: List[SelfPlayV1Stats], elapsed_sec: float)
             buckets[k] += int((s.piece_delta_buckets or {}).get(k, 0) or 0)
         if s.device and s.device not in devices:
             devices.append(s.device)
+    derive_counters(counters)                               # resignation: its two averages do not add up
     busy_ms = sum(max(0.0, float(s.elapsed_sec)) for s in stats_list) * 1000.0
     return SelfPlayV1Stats(
         num_games=games, num_positions=positions, black_wins=sum(int(s.black_wins) for s in stats_list),
@@ -585,7 +587,9 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0,
                          mcts_solver: bool = False, fpu_reduction: Optional[float] = None,
                          fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
-                         cpuct_base: float = 19652.0) -> Dict[str, Any]:
+                         cpuct_base: float = 19652.0, resign_threshold: float = 0.0, resign_min_moves: int = 10,
+                         resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
+                         resign_streak: str = "side") -> Dict[str, Any]:
     """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
     `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
     tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on.
@@ -601,7 +605,14 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
     metadata["mcts_solver"] when on.
     `fpu_reduction` (None = off), `fpu_root_reduction`, `cpuct_log` (0 = off), `cpuct_base` (tree backend only): first-play
     urgency and the visit-scaled exploration constant, see tree_engine.self_play_tree_gpu.  The four values are recorded in
-    the manifests' metadata["puct_shape"] when either half is on."""
+    the manifests' metadata["puct_shape"] when either half is on.
+    `resign_threshold` (tree backend only; 0 = off), `resign_min_moves`, `resign_consecutive`,
+    `resign_playthrough_fraction`, `resign_streak`: resignation with play-through calibration, see
+    tree_engine.self_play_tree_gpu.  The five values are recorded in the manifests' metadata["resign"] when on."""
+    from .resign import refuse_backend, resign_kwargs, resign_meta
+    resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
+                           resign_streak)
+    refuse_backend(bool(resign), search_backend)
     from .tree_engine import puct_shape_refusal
     shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
                                cpuct_base=cpuct_base, gumbel_considered=gumbel_considered, search_backend=search_backend)
@@ -705,7 +716,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                               "gumbel_c_visit": float(gumbel_c_visit),
                                               "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
                                           **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-                                          **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **common)
+                                          **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign,
+                                          **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
                                     sparse_top_k=int(sparse_top_k), row_log=row_log, **common)
@@ -729,7 +741,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                       "c_scale": float(gumbel_c_scale)}} if gumbel else {}),
                        **({"value_target": {"td_lambda": float(value_target_lambda)}} if td else {}),
                        **({"mcts_solver": True} if solver else {}),
-                       **({"puct_shape": shape.meta()} if shape.on else {})}
+                       **({"puct_shape": shape.meta()} if shape.on else {}),
+                       **({"resign": resign_meta(resign)} if resign else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

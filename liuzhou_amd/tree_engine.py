@@ -33,6 +33,7 @@ from .puct_shape import CPUCT_BASE_DEFAULT, CPUCT_TABLE_LEN, PuctShape, cpuct_ta
 from .self_play_types import SelfPlayV1Stats
 from .streams import CAPTURE_MODE
 from .trajectory_buffer import TensorSelfPlayBatch, TensorTrajectoryBuffer
+from .resign import counters_from_block, resign_kwargs
 from .value_target import td_lambda_on
 
 MAX_CHILDREN = 72
@@ -1828,7 +1829,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
                        gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0, mcts_solver: bool = False,
                        fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
-                       cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT
+                       cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT, resign_threshold: float = 0.0,
+                       resign_min_moves: int = 10, resign_consecutive: int = 3,
+                       resign_playthrough_fraction: float = 0.1, resign_streak: str = "side"
                        ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
@@ -1867,9 +1870,22 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     `fpu_reduction` (None = off), `fpu_root_reduction` (None = fpu_reduction), `cpuct_log` (0 = off), `cpuct_base`: first-play
     urgency and the visit-scaled exploration constant (PortableTreeMCTS) in every search.  Fused
     network and batch_k = 1 only, not with the Gumbel root search or the persistent kernel (ValueError); composes with
-    everything else.  Off, nothing is allocated and every output is byte-identical."""
+    everything else.  Off, nothing is allocated and every output is byte-identical.
+    `resign_threshold` (0 = off; on in [-1, 0)), `resign_min_moves`, `resign_consecutive`, `resign_playthrough_fraction`,
+    `resign_streak` ("side" / "ply"): resignation with play-through calibration (resign.py).  A game
+    whose searches' root values have been <= the threshold `resign_consecutive` times in a row (the mover's own searches
+    with "side") in the movement phases, from ply `resign_min_moves` on, ends as a loss of the side to move; the row of
+    that ply stays recorded.  A seeded share `resign_playthrough_fraction` of the games (a pure function of `seed` and the
+    game number) never resigns and measures the false positives.  mcts_counters gain resigned_games / resigned_black /
+    resigned_white / playthrough_games / playthrough_would_resign / playthrough_false_positive / resign_avg_ply /
+    resign_plies_saved_estimate (and the two sums the last two derive from).  Needs `device_tail` (ValueError otherwise);
+    composes with everything else.  Off, nothing is allocated or launched and every output is byte-identical."""
     dev = torch.device(device)
     solver = bool(mcts_solver)
+    resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
+                           resign_streak)
+    if resign and not device_tail:
+        raise ValueError("resignation needs device_tail: the rule runs in the per-ply device tail, the host loop has none")
     td = td_lambda_on(value_target_lambda)
     if td and not device_tail:
         raise ValueError("value_target_lambda < 1 needs device_tail: the host loop keeps the reference's finalisation "
@@ -1979,7 +1995,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     if device_tail:
         from .wave_tail import WaveTail
         tail = WaveTail(buffer, wave, int(max_game_plies), dev, soft_value_k=float(soft_value_k), row_log=row_log,
-                        **({"value_target_lambda": float(value_target_lambda)} if td else {}))
+                        **({"value_target_lambda": float(value_target_lambda)} if td else {}),
+                        **(dict(resign, seed=int(seed)) if resign else {}))
         tail.collect_timing = bool(collect_timing)
         outcome, delta_hist = tail.outcome, tail.delta_hist
         if cap:
@@ -2006,6 +2023,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
             lists_below = wave - (samples_per_launch_pass(net) if use_fused else 0)
             if cap:
                 tail.game_plies = game_plies if continuous else game_plies[base:base + g]
+            if resign:
+                tail.game_base = 0 if continuous else base
             tail.run(lambda st, temps, dn, reseated: mcts.search_batch(
                          st, temperatures=temps, active=~dn, reset=reseated,
                          force_uniform_random_mask=(plies < force_n) if force_n > 0 else None,
@@ -2125,6 +2144,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        **({"gumbel_searches": int(mcts.gumbel_searches.item())} if gumbel else {}),
                        # MCTS-Solver: edges / roots the expand steps decided, searches that ended with a decided root, picks changed
                        **(dict(zip(("solver_proofs", "solver_roots_decided", "solver_pick_overrides"),
-                                   (int(x) for x in mcts.solver_counts.tolist()))) if solver else {})},
+                                   (int(x) for x in mcts.solver_counts.tolist()))) if solver else {}),
+                       # resignation: games that resigned, the play-through games and their false positives
+                       **(counters_from_block(tail.resign_counters.tolist()) if resign else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))
     return batch, stats

@@ -1,6 +1,7 @@
 """Device-side tail of one ply of the v1 wave loop for a fixed wave of slots: trajectory rows, the move and the
 finalisation of finished games without a host round trip (`lz_wave_record`, `lz_wave_step_finish`), and optionally the
-TD(lambda) value targets from the searches' root values (`lz_wave_note_value`, `lz_wave_td_targets`; value_target.py).
+TD(lambda) value targets from the searches' root values (`lz_wave_note_value`, `lz_wave_td_targets`; value_target.py)
+and resignation with play-through calibration (`lz_wave_resign`, `lz_wave_resign_book`; resign.py).
 
 It replaces, for whole waves, the sequence `append_steps` -> `step_index[...] = rows` -> `self_play_step_inplace` ->
 `finalize_games_inplace` of v1/python/self_play_gpu_runner.py:205-247, whose `nonzero`-shaped outputs force one host
@@ -16,6 +17,7 @@ import torch
 from . import _lib as L
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput
 from .trajectory_buffer import TensorTrajectoryBuffer
+from .resign import COUNTER_KEYS, resign_kwargs
 from .value_target import td_lambda_on
 
 DELTA_BINS = 37
@@ -23,12 +25,20 @@ DELTA_BINS = 37
 
 class WaveTail:
     def __init__(self, buffer: TensorTrajectoryBuffer, num_slots: int, max_game_plies: int, device,
-                 soft_value_k: float = 2.0, reseat: bool = False, row_log=None, value_target_lambda: float = 1.0) -> None:
+                 soft_value_k: float = 2.0, reseat: bool = False, row_log=None, value_target_lambda: float = 1.0,
+                 resign_threshold: float = 0.0, resign_min_moves: int = 10, resign_consecutive: int = 3,
+                 resign_playthrough_fraction: float = 0.1, resign_streak: str = "side", seed: int = 0) -> None:
         # TD(lambda) value targets (value_target.py; 1 = off: every row gets the game's result, nothing below exists)
         self.td_lambda = float(value_target_lambda) if td_lambda_on(value_target_lambda) else None
         if self.td_lambda is not None and reseat:
             raise ValueError("WaveTail: value_target_lambda < 1 is not supported with the in-kernel re-seat (reseat=True): "
                              "it clears step_counts inside the step kernel, before the targets of the game are formed")
+        # resignation (resign.py; threshold 0 = off: nothing below exists and `step_finish` reads the search's terminal mask)
+        self.resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
+                                    resign_streak) or None
+        if self.resign is not None and reseat:
+            raise ValueError("WaveTail: resignation is not supported with the in-kernel re-seat (reseat=True): `done` is "
+                             "never set there, so the games that end are never booked")
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("WaveTail needs a HIP device (no CPU path)")
@@ -62,6 +72,21 @@ class WaveTail:
             self.step_ply = torch.zeros((self.G, self.max_plies), dtype=torch.int32, device=dev)
             self.hist_len = z(self.G, torch.int32)
             self.was_live = z(self.G, torch.uint8)
+        # resignation: the per-slot streak counters (Black's, White's; "ply" mode uses the first), the latched would-be
+        # resigner of a play-through game and its ply, the terminal mask the step kernel reads instead of the search's, the
+        # slots that resigned this ply and the int64[8] counter block (21 B per slot + 64 B); `seed` keys the play-through
+        # draw and `game_base` is the game number of slot_game 0 (sequential waves)
+        self.streak = self.would = self.would_ply = self.terminal_out = self.resigned = self.resign_counters = None
+        self.seed, self.game_base = int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+        if self.resign is not None:
+            self.streak = torch.zeros((self.G, 2), dtype=torch.int32, device=dev)
+            self.would = z(self.G, torch.int32)
+            self.would_ply = z(self.G, torch.int32)
+            self.terminal_out = z(self.G, torch.uint8)
+            self.resigned = z(self.G, torch.uint8)
+            self.resign_counters = z(len(COUNTER_KEYS), torch.int64)
+            if self.was_live is None:
+                self.was_live = z(self.G, torch.uint8)
         if row_log is not None:
             if reseat:
                 raise ValueError("WaveTail: the finished-row log needs run()'s re-seating (reseat=False)")
@@ -127,7 +152,7 @@ class WaveTail:
         if any(not t.is_contiguous() for t in ts):
             raise RuntimeError("WaveTail.step_finish: state tensors must be contiguous (they are updated in place)")
         codes = search.chosen_action_codes.contiguous()
-        term = search.terminal_mask.contiguous()
+        term = search.terminal_mask.contiguous() if self.resign is None else self.terminal_out
         cvalid = search.chosen_valid_mask.contiguous()
         with torch.cuda.device(self.device):
             L.check(L.lib().lz_wave_step_finish(
@@ -163,6 +188,40 @@ class WaveTail:
                 L.i64(self.max_plies if step_index is None else int(step_index.shape[1])), L.stream_ptr(self.device)),
                 "wave_td_targets")
 
+    def resign_step(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, search: RootSearchBatchOutput,
+                    slot_game: Optional[torch.Tensor] = None) -> None:
+        """Resignation: this ply's rule for every live slot (after `record` / `note_value`, before `step_finish`, which then
+        reads `terminal_out`)."""
+        rv = search.root_value.contiguous()
+        term = search.terminal_mask.contiguous()
+        if rv.dtype != torch.float32 or int(rv.numel()) != self.G:
+            raise RuntimeError("WaveTail.resign_step: root_value must be float32[num_slots]")
+        if term.element_size() != 1 or int(term.numel()) != self.G:
+            raise RuntimeError("WaveTail.resign_step: terminal_mask must be one byte per slot")
+        r = self.resign
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_wave_resign(
+                L.ptr(done), L.i64(self.G), L.ptr(plies), L.ptr(states.phase), L.ptr(states.current_player), L.ptr(rv),
+                L.ptr(term), L.ptr(slot_game), L.i64(self.game_base), C.c_uint64(self.seed),
+                C.c_float(r["resign_threshold"]), L.i64(r["resign_min_moves"]), C.c_int32(r["resign_consecutive"]),
+                C.c_float(r["resign_playthrough_fraction"]), C.c_int(1 if r["resign_streak"] == "ply" else 0),
+                L.ptr(self.streak), L.ptr(self.would), L.ptr(self.would_ply), L.ptr(self.terminal_out),
+                L.ptr(self.was_live), L.ptr(self.resigned), L.stream_ptr(self.device)), "wave_resign")
+
+    def resign_book(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, search: RootSearchBatchOutput,
+                    slot_game: Optional[torch.Tensor] = None) -> None:
+        """Resignation: book the games that ended this ply (after `step_finish`, before `td_targets` and the log)."""
+        cvalid = search.chosen_valid_mask.contiguous()
+        if cvalid.element_size() != 1 or int(cvalid.numel()) != self.G:
+            raise RuntimeError("WaveTail.resign_book: chosen_valid_mask must be one byte per slot")
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_wave_resign_book(
+                C.byref(L.soa(states.tensors())), L.i64(self.G), L.ptr(done), L.ptr(self.was_live), L.ptr(plies),
+                L.ptr(self.terminal_out), L.ptr(cvalid), L.ptr(self.resigned), L.ptr(self.would), L.ptr(self.would_ply),
+                L.ptr(slot_game), L.i64(self.game_base), C.c_uint64(self.seed),
+                C.c_float(self.resign["resign_playthrough_fraction"]), L.ptr(self.resign_counters),
+                L.stream_ptr(self.device)), "wave_resign_book")
+
     def start_next_games(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, step_counts: torch.Tensor,
                          budget: torch.Tensor, next_game: torch.Tensor, slot_game: torch.Tensor,
                          reseated: Optional[torch.Tensor] = None) -> None:
@@ -186,7 +245,9 @@ class WaveTail:
         With a finished-row log (`row_log`) `step_index` is None, the rows of the games that have ended move to the log
         after every ply, and the loop ends when every game has ended AND is in a log (which the caller then closes).
         With TD(lambda) value targets (`value_target_lambda` < 1) the order per ply is record -> note_value -> step_finish
-        -> td_targets -> the log: the rows of a game that ends carry their final targets before they leave."""
+        -> td_targets -> the log: the rows of a game that ends carry their final targets before they leave.
+        With resignation (`resign_threshold` < 0) it is record -> note_value -> resign -> step_finish -> resign_book ->
+        td_targets -> the log."""
         dev, g = self.device, self.G
         log = self.row_log
         if (log is None) == (step_index is None):
@@ -223,7 +284,11 @@ class WaveTail:
                 if self.td_lambda is not None:
                     self.note_value(states, plies, done, step_counts, search)
             with self._bracket("self_play_step_ms"):
+                if self.resign is not None:
+                    self.resign_step(states, plies, done, search, slot_game=slot_game)
                 self.step_finish(states, plies, done, step_index, step_counts, search, lengths=lengths, slot_game=slot_game)
+                if self.resign is not None:
+                    self.resign_book(states, plies, done, search, slot_game=slot_game)
             if self.td_lambda is not None:
                 with self._bracket("finalize_ms"):
                     self.td_targets(done, step_index, step_counts)

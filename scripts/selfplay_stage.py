@@ -72,6 +72,17 @@ def parse(argv=None):
                     help="visit-scaled exploration (tree backend): c(n) = exploration_weight + cpuct_log * "
                          "ln((n + cpuct_base + 1) / cpuct_base); 0 = off")
     ap.add_argument("--cpuct_base", type=float, default=19652.0, help="base of the visit-scaled exploration constant")
+    ap.add_argument("--self_play_resign_threshold", type=float, default=0.0,
+                    help="resignation (tree backend): a game resigns once its searches' root values were <= this value "
+                         "--self_play_resign_consecutive times in a row; in [-1, 0), 0 = off")
+    ap.add_argument("--self_play_resign_min_moves", type=int, default=10, help="resignation: no resignation before this ply")
+    ap.add_argument("--self_play_resign_consecutive", type=int, default=3,
+                    help="resignation: eligible low-value searches in a row needed to resign")
+    ap.add_argument("--self_play_resign_playthrough_fraction", type=float, default=0.1,
+                    help="resignation: seeded share of games that never resign and measure the false positives")
+    ap.add_argument("--self_play_resign_streak", default="side", choices=["side", "ply"],
+                    help="resignation: 'side' counts the mover's own searches, 'ply' every searched ply (the reference's "
+                         "literal counter)")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -137,7 +148,11 @@ def main(argv=None) -> int:
         value_target_lambda=args.value_target_lambda, **({"mcts_solver": True} if args.mcts_solver else {}),
         **({"fpu_reduction": args.fpu_reduction, "fpu_root_reduction": args.fpu_root_reduction}
            if args.fpu_reduction is not None or args.fpu_root_reduction is not None else {}),
-        **({"cpuct_log": args.cpuct_log, "cpuct_base": args.cpuct_base} if args.cpuct_log != 0.0 else {}))
+        **({"cpuct_log": args.cpuct_log, "cpuct_base": args.cpuct_base} if args.cpuct_log != 0.0 else {}),
+        resign_threshold=args.self_play_resign_threshold, resign_min_moves=args.self_play_resign_min_moves,
+        resign_consecutive=args.self_play_resign_consecutive,
+        resign_playthrough_fraction=args.self_play_resign_playthrough_fraction,
+        resign_streak=args.self_play_resign_streak)
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
