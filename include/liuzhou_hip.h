@@ -631,6 +631,37 @@ typedef struct LzTreeDesc {
     int32_t* root_proven;          /* [B] required when solver != 0 */
     int32_t* solver_count;         /* [B] optional: += 1 for every edge the expand step marks (proven, or terminal for want of
                                       a legal move) and every root result it sets */
+    /* Optional KLD-gain early stopping (Leela Chess Zero's rule; kld_threshold == 0 = off: nothing below is read or
+     * written).  Per game at the root, with the step numbering of lz_tree_search (launch s expands and backs up simulation
+     * s, then selects the leaf of s + 1): n_k = the low 24 bits of root edge k's visit field now, o_k = the same value in
+     * the game's row of kld_snapshot, N = sum n_k, O = sum o_k (children k = 0 .. ne - 1, ne <= 72).
+     *   A game takes part in the check behind launch s when it is active (`active`), its root has edges and its budget
+     *   kld_budget[g] is still > s + 1; any other game is left untouched and never counted.
+     *   s == 0: the row becomes the current visits (zeros for a fresh root, the carried visits for a kept one; entries
+     *   from ne on are 0).  Nothing else happens.
+     *   s > 0: if O > 0 and N > O,
+     *     gain = sum_{k: o_k > 0} (o_k / O) * ln(((double)o_k * N) / ((double)n_k * O))     in double;
+     *   both products are exact integers below 2^53, so equal distributions give exactly 0.  Lane l of 64 adds the terms of
+     *   children l and l + 64 (a missing term is +0.0), then the wave's DPP reduction adds the lanes.  The game stops iff
+     *   s >= kld_min_sims and gain / (double)(N - O) < kld_threshold: kld_budget[g] = s + 1 (the leaf of s + 1 is already
+     *   selected, so launch s + 1 expands it and selects nothing more: exactly what sim_budget means), kld_stops[g] += 1,
+     *   kld_saved[g] += old budget - (s + 1).  kld_trace[g] = gain / (N - O) whenever a gain was formed.  In every case the
+     *   row becomes the current visits.
+     * lz_tree_search / lz_tree_search_continue enqueue the check behind launch 0 and behind every launch s = k *
+     * kld_interval with s + 1 < sims, in the dense, list and gathering forms alike; they require sim_budget, and kld_budget
+     * must alias it (LZ_ERR_ARG otherwise), so such a search runs the playout cap's kernels.  Every other search entry point
+     * refuses a descriptor with kld_threshold > 0 (LZ_ERR_UNSUPPORTED), and so does every entry point when gumbel_m != 0 as
+     * well (the Sequential Halving schedule is a function of a fixed budget).  kld_interval < 1, kld_min_sims < 0, a
+     * negative or non-finite threshold, a NULL snapshot: LZ_ERR_ARG.  (These fields sit in front of the PUCT shape's, which
+     * stay the last five of the descriptor.) */
+    int32_t  kld_interval;         /* I >= 1 */
+    int32_t  kld_min_sims;         /* M >= 0 */
+    double   kld_threshold;        /* theta; 0 = off */
+    int32_t* kld_snapshot;         /* [B][72] */
+    int32_t* kld_budget;           /* [B] the writable view of sim_budget */
+    int64_t* kld_stops;            /* [B] optional */
+    int64_t* kld_saved;            /* [B] optional */
+    double*  kld_trace;            /* [B] optional (tests); NULL in production */
     /* Optional PUCT shape: first-play urgency and a visit-scaled exploration constant (puct_shape == 0 = off: nothing below
      * is read).  Both act on the levels that PUCT decides -- a root level under the forced-playout rule and a child the solver
      * takes outright are decided before the score and stay as they are.  n_v is the visit count the level already uses:
@@ -658,6 +689,10 @@ typedef struct LzTreeDesc {
     const double* cpuct_table;     /* [cpuct_table_len] device memory */
 } LzTreeDesc;
 LZ_API int64_t lz_tree_desc_bytes(void);
+/* One check of the KLD-gain rule behind launch `step` (LzTreeDesc.kld_*; step 0 stores the snapshot only).  What
+ * lz_tree_search enqueues between its launches, exported so that a test can drive a single check.  LZ_OK without a launch
+ * when the rule is off. */
+LZ_API int lz_tree_kld_check(const LzTreeDesc* tree, int64_t step, void* stream);
 
 /* SoA batch -> packed records; packed records -> float32[B,11,6,6] model input (src/neural_network.py:15-65) */
 /* Wave-batched leaves: the legacy search of src/mcts.py:280-497 (`batch_K` distinct leaves per tree and wave, no

@@ -1517,6 +1517,51 @@ __global__ __launch_bounds__(kBlock) void rng_uniform_kernel(uint64_t seed, cons
     out[g] = lzrng::uniform_draw(seed, game ? game[g] : g, ply ? ply[g] : 0, (uint32_t)purpose);
 }
 
+// KLD-gain early stopping (LzTreeDesc.kld_*): one check of the rule behind launch `step`, one wave per game.  Lane l takes
+// the root's children l and l + 64; the sums go through the wave reductions, so there is no LDS, no scratch and no atomic,
+// and a wave owns every word it writes: its game's snapshot row, budget, counters and trace entry.  A game that is not
+// active, has no root edges or has spent its budget (budget <= step + 1) is left untouched.  step == 0 stores the snapshot
+// only.  The budget is written between two launches of the search, whose CAP kernels read it at every launch.
+__global__ __launch_bounds__(kBlock) void tree_kld_check_kernel(Tree t, KldArgs ka, int step) {
+    const int g = wave_game();
+    if (g >= t.B) return;
+    const int lane = lane_id();
+    if (t.active != nullptr && t.active[g] == 0) return;
+    const Node* root = t.nodes + (size_t)g * t.node_cap;
+    int ne = root->nedges;
+    if (ne <= 0) return;
+    if (ne > kMaxChildren) ne = kMaxChildren;
+    const int budget = ka.budget[g];
+    if (budget <= step + 1) return;
+    const Edge* run = t.edges + root->edge_begin;
+    int* snap = ka.snapshot + (size_t)g * kMaxChildren;
+    const int k1 = lane + kWave;
+    const int n0 = lane < ne ? edge_n(run[lane].n_info) : 0;
+    const int n1 = k1 < ne ? edge_n(run[k1].n_info) : 0;
+    if (step > 0) {
+        const int o0 = lane < ne ? snap[lane] : 0;
+        const int o1 = k1 < ne ? snap[k1] : 0;
+        const int N = lzw::wave_sum_i32(n0 + n1), O = lzw::wave_sum_i32(o0 + o1);
+        if (O > 0 && N > O) {
+            // (o * N) and (n * O) are exact integers below 2^53: equal distributions give ln(1) = 0 in every term
+            const double dN = (double)N, dO = (double)O;
+            const double t0 = o0 > 0 ? ((double)o0 / dO) * log(((double)o0 * dN) / ((double)n0 * dO)) : 0.0;
+            const double t1 = o1 > 0 ? ((double)o1 / dO) * log(((double)o1 * dN) / ((double)n1 * dO)) : 0.0;
+            const double per = lzw::wave_sum_f64(t0 + t1) / (double)(N - O);
+            if (lane == 0) {
+                if (ka.trace != nullptr) ka.trace[g] = per;
+                if (step >= ka.min_sims && per < ka.theta) {
+                    ka.budget[g] = step + 1;
+                    if (ka.stops != nullptr) ka.stops[g] += 1;
+                    if (ka.saved != nullptr) ka.saved[g] += (long long)(budget - (step + 1));
+                }
+            }
+        }
+    }
+    snap[lane] = n0;
+    if (k1 < kMaxChildren) snap[k1] = n1;
+}
+
 WaveArrays make_wave(const LzTreeWaveDesc* w) {
     WaveArrays a;
     a.K = w->batch_k; a.cap = w->path_cap;
@@ -1606,6 +1651,7 @@ static void tree_select_launch(const LzTreeDesc* d, void* stream) {
 int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (!tree_ok(d)) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: lz_tree_search only
+    if (kld_set(d)) return LZ_ERR_UNSUPPORTED;                     // KLD-gain early stopping: likewise
     if (const int rc = gumbel_check(d)) return rc;
     if (const int rc = solver_check(d)) return rc;
     if (const int rc = shape_check(d)) return rc;
@@ -1632,7 +1678,7 @@ int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const flo
                    const float* priors220, const float* values, const float* noise, int64_t noise_stride,
                    float epsilon, void* stream) {
     if (!tree_ok(d) || !values) return LZ_ERR_ARG;
-    if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (cap_set(d) || kld_set(d)) return LZ_ERR_UNSUPPORTED;
     if (!priors220 && (!lp1 || !lp2 || !lpmc)) return LZ_ERR_ARG;
     if (const int rc = gumbel_check(d)) return rc;
     if (const int rc = solver_check(d)) return rc;
@@ -1819,6 +1865,14 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
     // gathering launch: the network kernel takes simulation s's live leaves out of leaf_state by their leaf_kind and writes
     // live_count[s]; outputs lie at the game's own row, so the step kernels are the dense branch's and nothing scans
     const bool gather = t.live_count != nullptr && tree_gather_path(net, B);
+    // KLD-gain early stopping: the snapshot behind launch 0, a check behind every launch s = k * kld_interval that is not
+    // one of the search's last two (s + 1 < sims: a stop there would save nothing)
+    const bool kld = CAP && kld_set(d);
+    const KldArgs ka = kld ? make_kld(d) : KldArgs{};
+    auto kld_after = [&](int64_t s) {
+        if (kld && s + 1 < sims && s % ka.interval == 0)
+            hipLaunchKernelGGL(tree_kld_check_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, ka, (int)s);
+    };
     if (t.live_count != nullptr && !gather) {
         // compact evaluation lists: simulation s evaluates live_count[s] leaves (see LzTreeDesc.live_*)
         hipLaunchKernelGGL(tree_live_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t, t.live_count);   // the roots
@@ -1846,6 +1900,7 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                                        t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv, sh);
                 (void)lz_prof_aux_end(0, stream, B);
             }
+            kld_after(s);
             if (s < sims)                                           // the leaves of simulation s + 1
                 hipLaunchKernelGGL(tree_live_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t,
                                    t.live_count + (s + 1));
@@ -1879,6 +1934,7 @@ static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArray
                                    lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv, sh);
             (void)lz_prof_aux_end(0, stream, B);
         }
+        kld_after(s);
     }
     if (GUMBEL && sims == 0)
         hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, ga, cap.root_noise);
@@ -1913,6 +1969,7 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     if (const int grc = gumbel_check(d)) return grc;
     if (const int src = solver_check(d)) return src;
     if (const int hrc = shape_check(d)) return hrc;
+    if (const int krc = kld_check(d)) return krc;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
@@ -1944,6 +2001,7 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
                                   int64_t noise_stride, float epsilon, bool continue_trees, void* stream) {
     if (!tree_ok(d) || sims < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: one network per search only
+    if (kld_set(d)) return LZ_ERR_UNSUPPORTED;                     // KLD-gain early stopping: likewise
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
     if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: likewise
@@ -2011,6 +2069,15 @@ LZ_API int lz_exp_tree_stamps(unsigned long long* out32, int reset) {
 #endif
 
 int64_t lz_tree_desc_bytes(void) { return (int64_t)sizeof(LzTreeDesc); }
+
+int lz_tree_kld_check(const LzTreeDesc* d, int64_t step, void* stream) {
+    if (!tree_ok(d) || step < 0 || step >= ((int64_t)1 << 30)) return LZ_ERR_ARG;
+    if (const int rc = kld_check(d)) return rc;
+    if (!kld_set(d) || d->num_games == 0) return LZ_OK;
+    hipLaunchKernelGGL(tree_kld_check_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
+                       make_kld(d), (int)step);
+    return st();
+}
 
 int lz_root_prepare(const void* root_states, int64_t B, const float* lp1, const float* lp2, const float* lpmc,
                     const float* noise, float epsilon, int64_t* legal_index_mat, float* priors_mat,
@@ -2138,7 +2205,7 @@ int lz_rng_uniform(uint64_t seed, const int64_t* game_id, const int64_t* ply, in
 
 int lz_tree_wave_select(const LzTreeDesc* d, const LzTreeWaveDesc* w, int64_t sims, int reset_budget, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || sims < 0) return LZ_ERR_ARG;
-    if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (cap_set(d) || kld_set(d)) return LZ_ERR_UNSUPPORTED;
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_select / lz_tree_search only
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
     if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: likewise
@@ -2154,7 +2221,7 @@ int lz_tree_wave_select(const LzTreeDesc* d, const LzTreeWaveDesc* w, int64_t si
 int lz_tree_wave_expand(const LzTreeDesc* d, const LzTreeWaveDesc* w, const float* lp1, const float* lp2,
                         const float* lpmc, const float* priors220, const float* values, int slot_major, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || !values) return LZ_ERR_ARG;
-    if (cap_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (cap_set(d) || kld_set(d)) return LZ_ERR_UNSUPPORTED;
     if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver marks in lz_tree_expand / lz_tree_search only
     if (!priors220 && (!lp1 || !lp2 || !lpmc)) return LZ_ERR_ARG;
     if (d->num_games == 0) return LZ_OK;
@@ -2171,7 +2238,7 @@ int lz_tree_search_waves(const LzTreeDesc* d, const LzTreeWaveDesc* w, const LzN
                          float* lp1, float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                          float epsilon, int continue_trees, int skip_roots, void* stream) {
     if (!tree_ok(d) || !wave_ok(w) || !net || sims < 0 || waves < 0 || !lp1 || !lp2 || !lpmc || !values) return LZ_ERR_ARG;
-    if (forced_set(d) || gumbel_set(d) || solver_set(d) || shape_set(d)) return LZ_ERR_UNSUPPORTED;
+    if (forced_set(d) || gumbel_set(d) || solver_set(d) || shape_set(d) || kld_set(d)) return LZ_ERR_UNSUPPORTED;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
     int rc = LZ_OK;

@@ -165,6 +165,7 @@ int lz_tree_search_persistent(const LzTreeDesc* d, const LzNetDesc* net, int64_t
                               void* stream) {
     if (!tree_ok(d) || !net || sims < 0 || !lp1 || !lp2 || !lpmc || !values || stagger_us < 0) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: lz_tree_search only
+    if (kld_set(d)) return LZ_ERR_UNSUPPORTED;                     // KLD-gain early stopping: lz_tree_search only
     if (forced_set(d)) return LZ_ERR_UNSUPPORTED;                  // forced playouts: lz_tree_search only
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: lz_tree_search only
     if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: lz_tree_search only

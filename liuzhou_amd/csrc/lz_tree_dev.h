@@ -1248,6 +1248,25 @@ inline GumbelArgs make_gumbel(const LzTreeDesc* d) {
                       d->gumbel_root_base, d->gumbel_root_value, d->gumbel_count, d->gumbel_m, d->gumbel_sims,
                       (int)d->gumbel_stride};
 }
+// Optional KLD-gain early stopping (LzTreeDesc.kld_*): the arguments of tree_kld_check_kernel, which alone reads them.
+struct KldArgs {
+    double theta; int interval, min_sims;
+    int* snapshot; int* budget; long long* stops; long long* saved; double* trace;
+};
+inline bool kld_set(const LzTreeDesc* d) { return d->kld_threshold != 0.0; }
+// LZ_OK, LZ_ERR_ARG (fields out of range, snapshot or budget missing, budget not the cap's own array) or
+// LZ_ERR_UNSUPPORTED (with the Gumbel root search)
+inline int kld_check(const LzTreeDesc* d) {
+    if (!kld_set(d)) return LZ_OK;
+    if (!(d->kld_threshold > 0.0) || !isfinite(d->kld_threshold) || d->kld_interval < 1 || d->kld_min_sims < 0 ||
+        !d->kld_snapshot || !d->kld_budget || d->kld_budget != d->sim_budget)
+        return LZ_ERR_ARG;
+    return gumbel_set(d) ? LZ_ERR_UNSUPPORTED : LZ_OK;
+}
+inline KldArgs make_kld(const LzTreeDesc* d) {
+    return KldArgs{d->kld_threshold, d->kld_interval, d->kld_min_sims, d->kld_snapshot, d->kld_budget,
+                   reinterpret_cast<long long*>(d->kld_stops), reinterpret_cast<long long*>(d->kld_saved), d->kld_trace};
+}
 bool tree_ok(const LzTreeDesc* d) {
     return d && d->num_games >= 0 && d->node_cap >= 2 && d->path_cap >= 3 &&
            d->edge_chunk >= 128 && (d->edge_chunk & (d->edge_chunk - 1)) == 0 && d->chunk_cap >= 1 &&

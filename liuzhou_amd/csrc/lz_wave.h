@@ -51,6 +51,14 @@ __device__ __forceinline__ float wave_sum(float v) {
     LZW_REDUCE(float, dpp_f32, ident, fadd)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+__device__ __forceinline__ double dadd(double a, double b) { return a + b; }
+// the same sum in double / over integers, under names of their own: no call of wave_sum changes its overload
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    const double ident = 0.0;
+    LZW_REDUCE(double, dpp_f64, ident, dadd)
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63),
+                            __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
 #undef LZW_REDUCE
 
 // The same maximum for inputs that are never NaN, one fused v_max_f32_dpp per step (the select form above costs a DPP
@@ -79,6 +87,8 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
     v += dpp_i32<0x143, 0xc>(0, v);
     return v;
 }
+// integer sum over the wave: the last lane's inclusive prefix
+__device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(wave_incl_scan(v), 63); }
 
 // value of `v` in lane `src` (src must be wave-uniform): v_readlane, no LDS
 __device__ __forceinline__ int lane_bcast(int v, int src) { return __builtin_amdgcn_readlane(v, src); }

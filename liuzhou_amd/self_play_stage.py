@@ -85,6 +85,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     solver_meta = False
     shape_meta: Optional[Dict[str, Any]] = None
     resign_meta: Optional[Dict[str, Any]] = None
+    kld_meta: Optional[Dict[str, Any]] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -119,6 +120,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         wrs = (wm.get("metadata") or {}).get("resign")
         if isinstance(wrs, dict) and resign_meta is None:
             resign_meta = {k: wrs.get(k) for k in ("threshold", "min_moves", "consecutive", "playthrough_fraction", "streak")}
+        wkl = (wm.get("metadata") or {}).get("kld_stop")
+        if isinstance(wkl, dict) and kld_meta is None:
+            kld_meta = {k: wkl.get(k) for k in ("threshold", "interval", "min_simulations")}
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -150,6 +154,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     if resign_meta is not None:         # resignation: its settings, the resigned and the play-through games of all workers
         from .resign import COUNTER_KEYS, DERIVED_KEYS
         meta["resign"] = {**resign_meta, **{k: int(merged.mcts_counters.get(k, 0)) for k in COUNTER_KEYS + DERIVED_KEYS}}
+    if kld_meta is not None:            # KLD-gain early stopping: its settings, the stopped searches of all workers
+        from .kld_stop import COUNTER_KEYS as KLD_COUNTER_KEYS
+        meta["kld_stop"] = {**kld_meta, **{k: int(merged.mcts_counters.get(k, 0)) for k in KLD_COUNTER_KEYS}}
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -179,7 +186,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
                         cpuct_base: float = 19652.0, resign_threshold: float = 0.0, resign_min_moves: int = 10,
                         resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
-                        resign_streak: str = "side") -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        resign_streak: str = "side", kld_stop_threshold: float = 0.0, kld_stop_interval: int = 100,
+                        kld_stop_min_simulations: Optional[int] = None) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
@@ -193,7 +201,11 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
     `cpuct_log` / `cpuct_base` (tree backend, first-play urgency and the visit-scaled exploration constant) only when one
     of the two halves is on, and `resign_threshold` / `resign_min_moves` / `resign_consecutive` /
     `resign_playthrough_fraction` / `resign_streak` (tree backend, resignation with play-through calibration) only when
-    resign_threshold < 0."""
+    resign_threshold < 0, and `kld_stop_threshold` / `kld_stop_interval` / `kld_stop_min_simulations` (tree backend, KLD-gain
+    early stopping of the searches) only when kld_stop_threshold > 0."""
+    from .kld_stop import kld_stop_refusal, parse_kld_stop, refuse_backend as kld_refuse_backend
+    kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
+    kld_refuse_backend(kld.on, search_backend)
     from .resign import refuse_backend, resign_kwargs
     resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
                            resign_streak)
@@ -213,6 +225,10 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
         raise ValueError(f"TD(lambda) value targets need the tree backend, not the root-PUCT search ({search_backend!r}): "
                          "they blend the tree search's root values")
     gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
+    if kld.on:
+        why = kld_stop_refusal(gumbel_considered=gumbel_considered if gumbel else 0)
+        if why is not None:
+            raise ValueError(f"KLD-gain early stopping is not supported with {why}")
     if gumbel:
         if str(search_backend).strip().lower() not in ("portable", "tree"):
             raise ValueError(f"the Gumbel root search needs the tree backend, not the root-PUCT search ({search_backend!r})")
@@ -266,7 +282,7 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
                 "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
             **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-            **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign)
+            **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign, **kld.kwargs())
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

@@ -589,7 +589,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
                          cpuct_base: float = 19652.0, resign_threshold: float = 0.0, resign_min_moves: int = 10,
                          resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
-                         resign_streak: str = "side") -> Dict[str, Any]:
+                         resign_streak: str = "side", kld_stop_threshold: float = 0.0, kld_stop_interval: int = 100,
+                         kld_stop_min_simulations: Optional[int] = None) -> Dict[str, Any]:
     """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
     `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
     tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on.
@@ -608,7 +609,19 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
     the manifests' metadata["puct_shape"] when either half is on.
     `resign_threshold` (tree backend only; 0 = off), `resign_min_moves`, `resign_consecutive`,
     `resign_playthrough_fraction`, `resign_streak`: resignation with play-through calibration, see
-    tree_engine.self_play_tree_gpu.  The five values are recorded in the manifests' metadata["resign"] when on."""
+    tree_engine.self_play_tree_gpu.  The five values are recorded in the manifests' metadata["resign"] when on.
+    `kld_stop_threshold` (tree backend only; 0 = off), `kld_stop_interval`, `kld_stop_min_simulations` (None = the
+    interval): KLD-gain early stopping of the searches, see tree_engine.self_play_tree_gpu.  The three values are recorded
+    in the manifests' metadata["kld_stop"] when on."""
+    from .kld_stop import kld_stop_refusal, parse_kld_stop, refuse_backend as kld_refuse_backend
+    kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
+    kld_refuse_backend(kld.on, search_backend)
+    if kld.on:
+        from .gumbel import gumbel_on as _gumbel_on
+        why = kld_stop_refusal(gumbel_considered=gumbel_considered
+                               if _gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale) else 0)
+        if why is not None:
+            raise ValueError(f"KLD-gain early stopping is not supported with {why}")
     from .resign import refuse_backend, resign_kwargs, resign_meta
     resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
                            resign_streak)
@@ -717,6 +730,7 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                               "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
                                           **({"value_target_lambda": float(value_target_lambda)} if td else {}),
                                           **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign,
+                                          **kld.kwargs(),
                                           **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
@@ -742,7 +756,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        **({"value_target": {"td_lambda": float(value_target_lambda)}} if td else {}),
                        **({"mcts_solver": True} if solver else {}),
                        **({"puct_shape": shape.meta()} if shape.on else {}),
-                       **({"resign": resign_meta(resign)} if resign else {})}
+                       **({"resign": resign_meta(resign)} if resign else {}),
+                       **({"kld_stop": kld.meta()} if kld.on else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

@@ -33,6 +33,7 @@ from .puct_shape import CPUCT_BASE_DEFAULT, CPUCT_TABLE_LEN, PuctShape, cpuct_ta
 from .self_play_types import SelfPlayV1Stats
 from .streams import CAPTURE_MODE
 from .trajectory_buffer import TensorSelfPlayBatch, TensorTrajectoryBuffer
+from .kld_stop import INTERVAL_DEFAULT as KLD_INTERVAL_DEFAULT, KldStop, kld_stop_refusal, parse_kld_stop
 from .resign import counters_from_block, resign_kwargs
 from .value_target import td_lambda_on
 
@@ -63,6 +64,8 @@ class LzTreeDesc(C.Structure):
                [(n, C.c_void_p) for n in ("gumbel_g", "gumbel_table", "gumbel_gl", "gumbel_base", "gumbel_root_base",
                                           "gumbel_root_value", "gumbel_count")] + [("gumbel_stride", C.c_int64)] + \
                [("solver", C.c_int32), ("root_proven", C.c_void_p), ("solver_count", C.c_void_p)] + \
+               [("kld_interval", C.c_int32), ("kld_min_sims", C.c_int32), ("kld_threshold", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("kld_snapshot", "kld_budget", "kld_stops", "kld_saved", "kld_trace")] + \
                [("puct_shape", C.c_int32), ("cpuct_table_len", C.c_int32), ("fpu_reduction", C.c_double),
                 ("fpu_root_reduction", C.c_double), ("cpuct_table", C.c_void_p)]
 
@@ -371,6 +374,9 @@ class TreeEngine:
         # PUCT shape (set_puct_shape; LzTreeDesc.puct_shape ..): the c(n) table exists only once that half is switched on
         self.puct_shape = parse_puct_shape()
         self.cpuct_table: Optional[torch.Tensor] = None
+        # KLD-gain early stopping (set_kld_stop; LzTreeDesc.kld_*): the buffers exist only once it is switched on
+        self.kld_stop = parse_kld_stop()
+        self.kld: Dict[str, torch.Tensor] = {}
         self.segment_games = None if segment_games is None else int(segment_games)
         self.num_segments = 1
         if self.segment_games is not None:
@@ -457,6 +463,10 @@ class TreeEngine:
                 raise ValueError(f"{name} must be a contiguous {dt} tensor of {self.B} elements on {self.device}")
             setattr(self.desc, name, None if t is None else t.data_ptr())
         self._cap_arrays = (sim_budget, root_noise)              # keep them alive while the descriptor points at them
+        if self.kld_stop.on:                                      # the rule writes the very array the searches read
+            if sim_budget is None:
+                raise ValueError("KLD-gain early stopping needs the per-game budget array")
+            self.desc.kld_budget = sim_budget.data_ptr()
 
     def set_forced_playouts(self, k: float) -> None:
         """Forced playouts and policy target pruning (LzTreeDesc.forced_k; 0 = off): select() and search() force due root
@@ -495,6 +505,8 @@ class TreeEngine:
             raise ValueError("the Gumbel root search and forced playouts are two rules for the same root level")
         if on and self.puct_shape.on:
             raise ValueError("the Gumbel root search is not supported with first-play urgency / the visit-scaled cpuct")
+        if on and self.kld_stop.on:
+            raise ValueError("the Gumbel root search is not supported with KLD-gain early stopping")
         d = self.desc
         self.gumbel_m = int(considered)
         self.gumbel_c_visit, self.gumbel_c_scale = float(c_visit), float(c_scale)
@@ -545,6 +557,49 @@ class TreeEngine:
             d.cpuct_table, d.cpuct_table_len = None, 0
         if shape.on:
             self.persistent = False       # the persistent kernel refuses the descriptor: the launch-pair search
+
+    def set_kld_stop(self, kld_stop: Optional[KldStop], trace: bool = False) -> None:
+        """KLD-gain early stopping (LzTreeDesc.kld_*; None / threshold 0 = off).  search() then runs
+        one check of the rule behind launch 0 (the snapshot) and behind every launch s = k * interval with s + 1 < sims; a
+        stopped game's entry of the budget array set by set_playout_cap() -- required, and refilled by the caller before
+        every search -- becomes s + 1.  `kld["stops"]` / `kld["saved"]` (int64[B]) sum the stopped searches and the
+        simulations they did not run, `kld["snapshot"]` (int32[B, 72]) holds the root visits of the last check, `trace`
+        adds `kld["trace"]` (float64[B]: the last per-simulation gain; tests).  Call after set_playout_cap() and before a
+        search is captured into a graph."""
+        ks = parse_kld_stop() if kld_stop is None else kld_stop
+        d = self.desc
+        if ks.on:
+            if self.batch_k > 1:
+                raise ValueError("KLD-gain early stopping is not supported by the legacy waves (batch_k > 1)")
+            if self.segment_games is not None:
+                raise ValueError("KLD-gain early stopping is not supported with several networks in one search")
+            if self.gumbel_m > 0:
+                raise ValueError("KLD-gain early stopping is not supported with the Gumbel root search (its Sequential "
+                                 "Halving schedule is a function of a fixed budget)")
+            budget = getattr(self, "_cap_arrays", (None, None))[0]
+            if budget is None:
+                raise ValueError("KLD-gain early stopping needs the per-game budget array (set_playout_cap) first")
+        self.kld_stop = ks
+        d.kld_threshold, d.kld_interval, d.kld_min_sims = (ks.threshold, ks.interval, ks.min_simulations) if ks.on else (0.0, 0, 0)
+        if not ks.on:
+            d.kld_snapshot = d.kld_budget = d.kld_stops = d.kld_saved = d.kld_trace = None
+            return
+        B, dev = self.B, self.device
+        if not self.kld:
+            self.kld = {"snapshot": torch.zeros((B, MAX_CHILDREN), dtype=torch.int32, device=dev),
+                        "stops": torch.zeros((B,), dtype=torch.int64, device=dev),
+                        "saved": torch.zeros((B,), dtype=torch.int64, device=dev)}
+        if trace and "trace" not in self.kld:
+            self.kld["trace"] = torch.zeros((B,), dtype=torch.float64, device=dev)
+        d.kld_snapshot, d.kld_budget = self.kld["snapshot"].data_ptr(), budget.data_ptr()
+        d.kld_stops, d.kld_saved = self.kld["stops"].data_ptr(), self.kld["saved"].data_ptr()
+        d.kld_trace = self.kld["trace"].data_ptr() if "trace" in self.kld else None
+        self.persistent = False           # the persistent kernel refuses the descriptor: the launch-pair search
+
+    def kld_check(self, step: int) -> None:
+        """One check of the rule behind launch `step` (lz_tree_kld_check; tests drive single checks with it)."""
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_tree_kld_check(C.byref(self.desc), L.i64(step), self._stream()), "tree_kld_check")
 
     def set_solver(self, on: bool = True) -> None:
         """MCTS-Solver (LzTreeDesc.solver; off by default): the expand step marks proven edges and carries them up the
@@ -781,7 +836,7 @@ class TreeEngine:
                 L.check(rc, "tree_search_persistent")
                 return
         fn = L.lib().lz_tree_search_continue if continue_trees else L.lib().lz_tree_search
-        use_lists = self.compact_evals and (compact is None or bool(compact))
+        use_lists = self.compact_evals and (compact is None or bool(compact) or self.kld_stop.on)
         desc = self.desc
         if self.compact_evals and not use_lists:                    # the same engine, dense launches for this move
             desc = LzTreeDesc()
@@ -884,7 +939,7 @@ class PortableTreeMCTS:
                  gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0, solver: bool = False,
                  fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
                  cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT,
-                 cpuct_table_len: int = CPUCT_TABLE_LEN) -> None:
+                 cpuct_table_len: int = CPUCT_TABLE_LEN, kld_stop: Optional[KldStop] = None) -> None:
         """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
         searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
         FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
@@ -939,7 +994,17 @@ class PortableTreeMCTS:
         DESIGN.md section 16) on every level that PUCT decides.  Either half works without the other.  Composes with the cap,
         forced playouts (the pruning rule then uses c(root visits)), the solver, several networks in one launch, symmetric
         evaluation, shared leaves and tree reuse; refused with the Gumbel root search, batch_k > 1, an external evaluator
-        and the persistent kernel (ValueError).  Such a search runs the one-wave tree step at every launch size."""
+        and the persistent kernel (ValueError).  Such a search runs the one-wave tree step at every launch size.
+        `kld_stop` (kld_stop.parse_kld_stop(threshold, interval, min_simulations); None or threshold 0 = off): KLD-gain early
+        stopping.  Every `interval` simulations a game's root visit distribution is compared with the
+        one `interval` simulations earlier, and from `min_simulations` on the game's search ends once the gain per
+        simulation is below the threshold: its budget becomes the check's simulation + 1, and its tree is bit for bit the
+        one a search of that many simulations builds.  `sim_budget` (int32[B]) is refilled before every search -- with
+        `num_simulations`, or by the playout cap's draw, which the rule may only lower -- and `last_sim_budget` is what the
+        search left in it; `kld_counts` (int64[2]) sums the stopped searches and the simulations they did not run; parity
+        runs hand every game its budget through `injected_sim_budget` (int32[B], honoured by any search that owns a budget
+        array, after the cap's draw).  Searches then always use the compact lists.  Refused where the cap is refused and
+        with the Gumbel root search (ValueError)."""
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
         self.solver = bool(solver)
@@ -967,6 +1032,14 @@ class PortableTreeMCTS:
                    "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else None)
             if why is not None:
                 raise ValueError(f"forced playouts are not supported with {why}")
+        self.kld_stop = parse_kld_stop() if kld_stop is None else parse_kld_stop(*kld_stop)
+        self.kld = self.kld_stop.on
+        if self.kld:
+            why = kld_stop_refusal(batch_k=batch_k, several_networks=self.multi or len(self.nets) != 1,
+                                   fused=isinstance(self.nets[0], FusedNet),
+                                   gumbel_considered=gumbel_considered if self.gumbel else 0)
+            if why is not None:
+                raise ValueError(f"KLD-gain early stopping is not supported with {why}")
         self.cap = playout_cap_on(fast_simulations, full_prob, num_simulations)
         self.fast_simulations, self.full_prob = int(fast_simulations), float(full_prob)
         if self.cap:
@@ -977,6 +1050,8 @@ class PortableTreeMCTS:
             if why is not None:
                 raise ValueError(f"playout cap randomization is not supported with {why}")
             compact_evals = True           # a dense launch would evaluate every slot at every simulation: nothing saved
+        if self.kld:
+            compact_evals = True           # likewise: a stopped game must leave the network launches
         if not self.multi and len(self.nets) != 1:
             raise ValueError("several networks need segment_games")
         if self.multi:
@@ -1008,7 +1083,7 @@ class PortableTreeMCTS:
         if compact_evals is None:
             compact_evals = self.fused and int(num_games) >= 2 * samples_per_launch_pass(net)
             self.compact_default = compact_evals and self.batch_k == 1 and shares_leaves(num_games)
-        if self.cap:
+        if self.cap or self.kld:
             compact_evals = self.compact_default = True
         self.engine = TreeEngine(num_games, num_simulations, device, exploration_weight,
                                  reuse_factor=float(reuse_factor) if self.reuse_tree else 0.0, batch_k=self.batch_k,
@@ -1065,16 +1140,57 @@ class PortableTreeMCTS:
         # playout cap: per-game budget / root noise switch of the next search, filled on the device before every launch
         self.injected_full_search: Optional[torch.Tensor] = None   # parity runs: bool[B] instead of the RNG's draws
         self.cap_counts = torch.zeros((2,), dtype=torch.int64, device=self.engine.device)   # full / fast searches of live games
-        if self.cap:
+        # KLD-gain early stopping: the same budget array (the rule lowers what the cap's draw, or `sims`, put there)
+        self.injected_sim_budget: Optional[torch.Tensor] = None    # parity runs: int32[B] instead of the draw / `sims`
+        self.full_search: Optional[torch.Tensor] = None
+        if self.cap or self.kld:
             z = lambda dt: torch.zeros((self.engine.B,), dtype=dt, device=self.engine.device)
-            self._cap_u, self.sim_budget = z(torch.float32), z(torch.int32)
-            self.bind_full_search(z(torch.uint8))
+            self.sim_budget = z(torch.int32)
+            if self.cap:
+                self._cap_u = z(torch.float32)
+                self.bind_full_search(z(torch.uint8))
+            else:
+                self.engine.set_playout_cap(self.sim_budget, None)
+            if self.kld:
+                self.engine.set_kld_stop(self.kld_stop, trace=bool(trace))
 
     def bind_full_search(self, buf: torch.Tensor) -> None:
         """Use `buf` (uint8[B], contiguous; DualStreamTreeMCTS hands each part a slice of one mask) as the full / fast mask
         of the playout cap, which the searches also read as their root noise switch.  Before the first search."""
         self.full_search = buf
         self.engine.set_playout_cap(self.sim_budget, buf)
+
+    def bind_sim_budget(self, buf: torch.Tensor) -> None:
+        """Use `buf` (int32[B], contiguous; DualStreamTreeMCTS hands each part a slice of one array) as the per-game budget
+        of the playout cap and of KLD-gain early stopping.  Before the first search."""
+        self.sim_budget = buf
+        self.engine.set_playout_cap(buf, self.full_search if self.cap else None)
+
+    @property
+    def last_sim_budget(self) -> Optional[torch.Tensor]:
+        """int32[B]: every game's budget as the last search left it (None: neither the cap nor the KLD-gain rule is on)."""
+        return self.sim_budget if (self.cap or self.kld) else None
+
+    @property
+    def kld_counts(self) -> torch.Tensor:
+        """int64[2] on the device: searches the KLD-gain rule stopped and the simulations they did not run, so far (zeros
+        when off)."""
+        if not self.kld:
+            return torch.zeros((2,), dtype=torch.int64, device=self.engine.device)
+        k = self.engine.kld
+        return torch.stack((k["stops"].sum(), k["saved"].sum()))
+
+    def _reset_kld_counts(self) -> None:
+        if self.kld:
+            self.engine.kld["stops"].zero_(); self.engine.kld["saved"].zero_()
+
+    def _fill_sim_budget(self) -> None:
+        """Budgets of a search without the cap's draw (KLD-gain early stopping alone): `sims` for every game, or the
+        injected ones.  On the device, outside the captured search."""
+        if self.injected_sim_budget is not None:
+            self.sim_budget.copy_(self.injected_sim_budget.to(device=self.engine.device, dtype=torch.int32))
+        else:
+            self.sim_budget.fill_(self.sims)
 
     @property
     def last_full_search(self) -> Optional[torch.Tensor]:
@@ -1118,6 +1234,8 @@ class PortableTreeMCTS:
             full = self._cap_u.double() < self.full_prob
         self.full_search.copy_(full)
         self.sim_budget.copy_(torch.where(full, self.sims, self.fast_simulations))
+        if self.injected_sim_budget is not None:
+            self.sim_budget.copy_(self.injected_sim_budget.to(device=self.engine.device, dtype=torch.int32))
         live = torch.ones_like(full) if active is None else active.to(device=full.device, dtype=torch.bool)
         self.cap_counts.add_(torch.stack(((full & live).sum(), (~full & live).sum())))
 
@@ -1360,6 +1478,7 @@ class PortableTreeMCTS:
         if self.gumbel:
             self.engine.gumbel["count"].zero_()
         self._reset_solver_counts()
+        self._reset_kld_counts()
         # refused expansions / fewest free chunks are per run too (a cached engine must not report an earlier run's)
         # (pool_stats[2], the chunks reserved for fresh roots, follows the trees' state and is NOT a per-run statistic)
         self.engine.buf["pool_stats"][:2].copy_(torch.tensor([0, self.engine.pool_chunks], dtype=torch.int32))
@@ -1387,6 +1506,7 @@ class PortableTreeMCTS:
         if self.gumbel:
             self.engine.gumbel["count"].zero_()
         self._reset_solver_counts()
+        self._reset_kld_counts()
         self.get_timing(reset=True)
         if self.batch_k > 1:
             self.engine.wbuf["eval_total"].zero_(); self.engine.wbuf["eval_count"].zero_()
@@ -1417,7 +1537,7 @@ class PortableTreeMCTS:
         e = self.engine
         # compact lists or dense launches for this move (engines built with compact_evals; the runner passes a hint from
         # the number of live games: the lists pay once a launch gets at least one network pass per CU shorter)
-        self.compact_now = self.compact_default if (compact is None or self.cap) else bool(compact)
+        self.compact_now = self.compact_default if (compact is None or self.cap or self.kld) else bool(compact)
         add_noise = self.add_noise if add_dirichlet_noise is None else bool(add_dirichlet_noise)
         if self.gumbel:
             add_noise = False             # the Gumbel variates are the exploration: no Dirichlet mix, no noise draws
@@ -1427,6 +1547,8 @@ class PortableTreeMCTS:
         self._explicit_plies = rng_plies is not None
         if self.cap:
             self._draw_playout_cap(active)
+        elif self.kld:
+            self._fill_sim_budget()
         with self._timed("root_puct_ms"):
             if continue_trees:
                 e.advance(played_action, reset, self.sims)
@@ -1535,6 +1657,15 @@ class DualStreamTreeMCTS:
             self.full_search = torch.zeros((self.B,), dtype=torch.uint8, device=dev)
             for (a, b), part in zip(self.bounds, self.parts):
                 part.bind_full_search(self.full_search[a:b])
+        # KLD-gain early stopping: likewise one budget array over all games, each part refilling and lowering its slice
+        self.kld = self.parts[0].kld
+        self.kld_stop = self.parts[0].kld_stop
+        self.sim_budget = None
+        self.injected_sim_budget: Optional[torch.Tensor] = None    # parity runs: int32[B], cut for the parts at every search
+        if self.kld:
+            self.sim_budget = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+            for (a, b), part in zip(self.bounds, self.parts):
+                part.bind_sim_budget(self.sim_budget[a:b])
         self.serialize = False        # measurement aid: run the halves one after the other on the caller's stream
         # Overlap watch.  A probed pair of streams can still end up on one hardware queue later (the runtime maps streams
         # to its 4 queues when they become active; other streams of the process come and go): the halves then run one
@@ -1574,6 +1705,16 @@ class DualStreamTreeMCTS:
     @property
     def solver_counts(self) -> torch.Tensor:
         return sum(p.solver_counts for p in self.parts)
+
+    @property
+    def kld_counts(self) -> torch.Tensor:
+        return sum(p.kld_counts for p in self.parts)
+
+    @property
+    def last_sim_budget(self) -> Optional[torch.Tensor]:
+        if self.kld:
+            return self.sim_budget
+        return torch.cat([p.sim_budget for p in self.parts]) if self.cap else None
 
     @property
     def last_full_search(self) -> Optional[torch.Tensor]:
@@ -1692,6 +1833,8 @@ class DualStreamTreeMCTS:
             with torch.cuda.stream(st):
                 if watch is not None:
                     watch[2 * i].record(st)
+                if self.injected_sim_budget is not None:
+                    part.injected_sim_budget = self.injected_sim_budget[a:b]
                 part.launch_search(sub, active=cut(active, a, b), add_dirichlet_noise=add_dirichlet_noise,
                                    reset=cut(reset, a, b), played_action=cut(played_action, a, b),
                                    rng_game_ids=cut(rng_game_ids, a, b), rng_plies=cut(rng_plies, a, b), compact=compact)
@@ -1831,7 +1974,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
                        cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT, resign_threshold: float = 0.0,
                        resign_min_moves: int = 10, resign_consecutive: int = 3,
-                       resign_playthrough_fraction: float = 0.1, resign_streak: str = "side"
+                       resign_playthrough_fraction: float = 0.1, resign_streak: str = "side",
+                       kld_stop_threshold: float = 0.0, kld_stop_interval: int = KLD_INTERVAL_DEFAULT,
+                       kld_stop_min_simulations: Optional[int] = None
                        ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
@@ -1879,9 +2024,17 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     game number) never resigns and measures the false positives.  mcts_counters gain resigned_games / resigned_black /
     resigned_white / playthrough_games / playthrough_would_resign / playthrough_false_positive / resign_avg_ply /
     resign_plies_saved_estimate (and the two sums the last two derive from).  Needs `device_tail` (ValueError otherwise);
-    composes with everything else.  Off, nothing is allocated or launched and every output is byte-identical."""
+    composes with everything else.  Off, nothing is allocated or launched and every output is byte-identical.
+    `kld_stop_threshold` (0 = off), `kld_stop_interval` (100), `kld_stop_min_simulations` (None = the interval): KLD-gain
+    early stopping (kld_stop.py, PortableTreeMCTS `kld_stop`): a game's search ends once its root
+    visit distribution gains less than the threshold per simulation between two checks `kld_stop_interval` simulations
+    apart.  mcts_counters gain kld_stopped_searches / kld_simulations_saved.  Fused network and batch_k = 1 only, not with
+    the Gumbel root search or the persistent kernel (ValueError); composes with everything else -- with the playout cap the
+    cap's draw sets the budget and the rule may only lower it.  Off, nothing is allocated or launched and every output is
+    byte-identical."""
     dev = torch.device(device)
     solver = bool(mcts_solver)
+    kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
     resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
                            resign_streak)
     if resign and not device_tail:
@@ -1934,6 +2087,10 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
                                cpuct_base=cpuct_base, batch_k=batch_k, fused=use_fused,
                                gumbel_considered=gumbel_considered if gumbel else 0)
+    if kld.on:
+        why = kld_stop_refusal(batch_k=batch_k, fused=use_fused, gumbel_considered=gumbel_considered if gumbel else 0)
+        if why is not None:
+            raise ValueError(f"KLD-gain early stopping is not supported with {why}")
     if use_fused and persistent_search_available(net, batch_k) and eval_symmetry == "none":
         if cap:
             raise ValueError("playout cap randomization is not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
@@ -1958,6 +2115,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     if solver:
         kw["solver"] = True
     kw.update(shape.kwargs())
+    if kld.on:
+        kw["kld_stop"] = kld
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a
@@ -2118,7 +2277,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         # (... unless that ply was launched densely: the two-plies-old live estimate had not seen the wave end yet)
         mcts_counters={"leaf_eval_count": int(mcts.leaf_evals) - (
                            wasted_plies * wave * (int(mcts_simulations) + 1)
-                           if int(batch_k) <= 1 and not (compact_lists and (cap or getattr(mcts, "last_search_lists", False)))
+                           if int(batch_k) <= 1 and not (compact_lists and (cap or kld.on or getattr(mcts, "last_search_lists", False)))
                            else 0),
                        "compact_eval_lists": int(compact_lists), "search_parts": len(engines),
                        "list_searches": int(sum(getattr(p, "list_searches", 0) for p in (getattr(mcts, "parts", None) or [mcts]))),
@@ -2145,6 +2304,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        # MCTS-Solver: edges / roots the expand steps decided, searches that ended with a decided root, picks changed
                        **(dict(zip(("solver_proofs", "solver_roots_decided", "solver_pick_overrides"),
                                    (int(x) for x in mcts.solver_counts.tolist()))) if solver else {}),
+                       # KLD-gain early stopping: searches it ended early, simulations they did not run
+                       **(dict(zip(("kld_stopped_searches", "kld_simulations_saved"),
+                                   (int(x) for x in mcts.kld_counts.tolist()))) if kld.on else {}),
                        # resignation: games that resigned, the play-through games and their false positives
                        **(counters_from_block(tail.resign_counters.tolist()) if resign else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))

@@ -83,6 +83,12 @@ def parse(argv=None):
     ap.add_argument("--self_play_resign_streak", default="side", choices=["side", "ply"],
                     help="resignation: 'side' counts the mover's own searches, 'ply' every searched ply (the reference's "
                          "literal counter)")
+    ap.add_argument("--kld_stop_threshold", type=float, default=0.0,
+                    help="KLD-gain early stopping (tree backend): a search ends once its root visit distribution gains "
+                         "less than this per simulation between two checks; 0 = off")
+    ap.add_argument("--kld_stop_interval", type=int, default=100, help="KLD-gain early stopping: simulations between checks")
+    ap.add_argument("--kld_stop_min_simulations", type=int, default=None,
+                    help="KLD-gain early stopping: no stop before this many simulations (default: the interval)")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -152,7 +158,9 @@ def main(argv=None) -> int:
         resign_threshold=args.self_play_resign_threshold, resign_min_moves=args.self_play_resign_min_moves,
         resign_consecutive=args.self_play_resign_consecutive,
         resign_playthrough_fraction=args.self_play_resign_playthrough_fraction,
-        resign_streak=args.self_play_resign_streak)
+        resign_streak=args.self_play_resign_streak,
+        **({"kld_stop_threshold": args.kld_stop_threshold, "kld_stop_interval": args.kld_stop_interval,
+            "kld_stop_min_simulations": args.kld_stop_min_simulations} if args.kld_stop_threshold != 0.0 else {}))
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
