@@ -805,6 +805,30 @@ LZ_API int lz_tree_finish_gumbel(const LzTreeDesc* tree, const float* temperatur
  * solver == 0 it launches nothing. */
 LZ_API int lz_tree_solver_pick(const LzTreeDesc* tree, const uint8_t* force_uniform, int32_t* chosen_index,
                                int32_t* chosen_code /*[B,4]*/, uint8_t* chosen_valid, int32_t* overrides, void* stream);
+/* Visit-offset / value-cutoff move pick (Leela Chess Zero's TempVisitOffset / TempValueCutoff, KataGo's chosenMoveSubtract /
+ * chosenMovePrune), launched after lz_tree_finish* and before lz_tree_solver_pick on the same stream, with the arrays the
+ * finish was given.  visit_offset o (finite, >= 0) and value_cutoff c (in [0, 2]); anything else is LZ_ERR_ARG.  The rule is
+ * on when either is above 0; with both 0, or with sample_moves == 0, the call launches nothing and returns LZ_OK.
+ * A game is re-picked only where the finish sampled its move from the visits: non-terminal root (a game that was not
+ * searched counts as terminal), temperatures[g] > 1e-6, force_uniform == NULL or force_uniform[g] == 0.  For such a game,
+ * with the root's children k = 0 .. ne-1 in edge order, N(k) the raw visits and q(k) the child's mean value in the root
+ * mover's frame as the finish forms it (double W / N, sign from the info bit, 0 when N == 0), all in double:
+ *   1. k* = the most visited child, lowest index among equals.
+ *   2. n'(k) = N(k) - o.  If n'(k*) <= 0 the pick is k*.
+ *   3. k is eligible if k == k*, or n'(k) > 0 and (c == 0 or q(k) >= q(k*) - c).
+ *   4. w(k) = exp((log n'(k) - log n'(k*)) / T) for an eligible k != k*, w(k*) = 1, else 0;
+ *      T = (double) max(temperatures[g], 1e-6f).
+ *   5. C(k) = the inclusive cumulative weight in edge order, S = the total.
+ *   6. the pick is the first eligible k with C(k) > (double) uniforms[g] * S, or the last eligible child if there is none.
+ * uniforms[g] is the value the finish consumed: no further random number is drawn.  Only chosen_index and chosen_code
+ * (index_to_code of the root's phase, as in the finish) are written, and only where the pick differs from the finish's.
+ * counters int64[4] (optional), one atomic add per game and counter: [0] games the rule applied to, [1] children other than
+ * k* with N > 0 and n' <= 0 (cut by the offset), [2] children other than k* with n' > 0 that failed the value test, [3] games
+ * whose pick differs from the finish's.  The cumulative weights are summed by a wave scan, whose association differs from
+ * a sequential sum by a few ulp of S.  One wave per game, up to 128 children; no LDS, no scratch; capturable. */
+LZ_API int lz_tree_move_pick(const LzTreeDesc* tree, const float* temperatures, const uint8_t* force_uniform,
+                             const float* uniforms, int sample_moves, double visit_offset, double value_cutoff,
+                             int32_t* chosen_index, int32_t* chosen_code /*[B,4]*/, int64_t* counters, void* stream);
 /* One whole search enqueued from C++: begin, root evaluation + expansion, then `sims` x
  * (select -> planes -> fused network -> expand + backup).  No host synchronisation; capturable. */
 LZ_API int lz_tree_search(const LzTreeDesc* tree, const LzNetDesc* net, int64_t sims, float* planes /*[B,11,36]*/,

@@ -1274,6 +1274,101 @@ __global__ __launch_bounds__(kBlock) void tree_solver_pick_kernel(Tree t, const 
     }
 }
 
+// Visit-offset / value-cutoff move pick (lz_tree_move_pick; the rule is stated in liuzhou_hip.h), launched behind the finish
+// kernel and in front of the solver pick.  One wave per game, two children per lane; a game is re-picked only where the
+// finish sampled its move from the visits.  Only chosen_index / chosen_code and the counters are written.
+// Inclusive prefix sum of a double over the wave in lane order (the shuffle ladder of wave_td_targets_kernel, upwards).
+__device__ __forceinline__ double move_pick_scan(double v, int lane) {
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) { const double up = __shfl_up(v, o, kWave); if (lane >= o) v += up; }
+    return v;
+}
+__device__ __forceinline__ double bcast_f64(double v, int src) {
+    return __hiloint2double(lzw::lane_bcast(__double2hiint(v), src), lzw::lane_bcast(__double2loint(v), src));
+}
+__global__ __launch_bounds__(kBlock) void tree_move_pick_kernel(Tree t, const float* __restrict__ temps,
+                                                                const uint8_t* __restrict__ force_uniform,
+                                                                const float* __restrict__ uniforms,
+                                                                double offset, double cutoff,
+                                                                int* __restrict__ chosen_index,
+                                                                int4* __restrict__ chosen_code,
+                                                                unsigned long long* __restrict__ counters) {
+    const int lane = lane_id();
+    const int g = wave_game();
+    if (g >= t.B) return;
+    if (force_uniform != nullptr && force_uniform[g] != 0) return;   // opening random move: kept
+    const float temp = temps[g];
+    if (!(temp > 1e-6f)) return;                                     // the finish took the most visited child itself
+    const RootInfo root = load_root_info(t, g);
+    if (t.root_terminal[g] != 0 || root.ne <= 0) return;
+    int n[2], act[2]; double q[2]; bool ok[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int k = r * kWave + lane;
+        ok[r] = k < root.ne;
+        const Edge e = load_edge(&t.edges[(size_t)(root.e0 + (ok[r] ? k : 0))]);
+        n[r] = ok[r] ? edge_n(e.n_info) : -1;
+        act[r] = ok[r] ? (int)e.act : -1;
+        q[r] = 0.0;
+        if (n[r] > 0) {
+            const double mv = e.W / (double)n[r];
+            q[r] = ((edge_info(e.n_info) & kInfoWhite) ? -1 : 1) == root.player ? mv : -mv;
+        }
+    }
+    // k*: most visits (counts are below 2^24: exact in fp32), lowest edge index among equals
+    const float nmax = lzw::wave_max(fmaxf((float)n[0], (float)n[1]));
+    const uint64_t lo = __ballot(ok[0] && (float)n[0] == nmax);
+    const int ks = lo ? __ffsll((unsigned long long)lo) - 1
+                      : kWave + __ffsll((unsigned long long)__ballot(ok[1] && (float)n[1] == nmax)) - 1;
+    const double qs = bcast_f64(ks >= kWave ? q[1] : q[0], ks & 63);
+    const double nps = (double)nmax - offset;                        // n' of k*
+    const double tt = (double)fmaxf(temp, 1e-6f);
+    double w[2]; bool el[2]; int cut_n = 0, cut_q = 0;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const bool star = r * kWave + lane == ks;
+        const double np = (double)n[r] - offset;
+        const bool has = ok[r] && !star && np > 0.0;
+        const bool good = cutoff == 0.0 || q[r] >= qs - cutoff;
+        cut_n += (ok[r] && !star && n[r] > 0 && !(np > 0.0)) ? 1 : 0;
+        cut_q += (has && !good) ? 1 : 0;
+        el[r] = nps > 0.0 && (star || (has && good));
+        w[r] = !el[r] ? 0.0 : (star ? 1.0 : exp((log(np) - log(nps)) / tt));
+    }
+    int pick = ks;
+    if (nps > 0.0) {
+        const double c0 = move_pick_scan(w[0], lane);
+        const double s0 = __shfl(c0, kWave - 1, kWave);
+        const double c1 = s0 + move_pick_scan(w[1], lane);
+        const double target = (double)uniforms[g] * __shfl(c1, kWave - 1, kWave);
+        const uint64_t h0 = __ballot(el[0] && c0 > target), h1 = __ballot(el[1] && c1 > target);
+        const uint64_t v0 = __ballot(el[0]), v1 = __ballot(el[1]);
+        // (the builtin, not __clzll: one more caller of that wrapper changes how the finish kernels' own call is compiled)
+        if (h0) pick = __ffsll((unsigned long long)h0) - 1;
+        else if (h1) pick = kWave + __ffsll((unsigned long long)h1) - 1;
+        else if (v1) pick = kWave + 63 - __builtin_clzll((unsigned long long)v1);
+        else pick = 63 - __builtin_clzll((unsigned long long)v0);    // k* is eligible: v0 | v1 is never empty
+    }
+    const int cn = lzw::wave_sum_i32(cut_n), cq = lzw::wave_sum_i32(cut_q);
+    const int a = lzw::lane_bcast(pick >= kWave ? act[1] : act[0], pick & 63);
+    const bool changed = a != chosen_index[g];
+    if (lane == 0) {
+        if (changed) {
+            const State rs = unpack(root.state);
+            int kd, p, q2, ex;
+            index_to_code(rs.phase, a, kd, p, q2, ex);
+            chosen_index[g] = a;
+            chosen_code[g] = make_int4(kd, p, q2, ex);
+        }
+        if (counters != nullptr) {
+            atomicAdd(counters + 0, 1ull);
+            if (cn > 0) atomicAdd(counters + 1, (unsigned long long)cn);
+            if (cq > 0) atomicAdd(counters + 2, (unsigned long long)cq);
+            if (changed) atomicAdd(counters + 3, 1ull);
+        }
+    }
+}
+
 // =================================================================================================================
 // Fused root-PUCT search (variant R, v1/python/mcts_gpu.py:1249-1457) on packed states: the host op chain
 // encode -> project -> root_pack -> noise -> batch_apply_moves -> ... with data-dependent shapes and two host syncs
@@ -1775,6 +1870,21 @@ int lz_tree_solver_pick(const LzTreeDesc* d, const uint8_t* force_uniform, int32
     if (!solver_set(d) || d->num_games == 0) return LZ_OK;
     hipLaunchKernelGGL(tree_solver_pick_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
                        force_uniform, chosen_index, reinterpret_cast<int4*>(chosen_code), chosen_valid, overrides);
+    return st();
+}
+
+int lz_tree_move_pick(const LzTreeDesc* d, const float* temperatures, const uint8_t* force_uniform, const float* uniforms,
+                      int sample_moves, double visit_offset, double value_cutoff, int32_t* chosen_index,
+                      int32_t* chosen_code, int64_t* counters, void* stream) {
+    if (!tree_ok(d) || !chosen_index || !chosen_code) return LZ_ERR_ARG;
+    if (!(visit_offset >= 0.0) || !(visit_offset < (double)INFINITY) || !(value_cutoff >= 0.0) || !(value_cutoff <= 2.0))
+        return LZ_ERR_ARG;
+    if (visit_offset == 0.0 && value_cutoff == 0.0) return LZ_OK;     // off: nothing is launched
+    if (!sample_moves || d->num_games == 0) return LZ_OK;             // the finish sampled no move: nothing to re-pick
+    if (!temperatures || !uniforms) return LZ_ERR_ARG;
+    hipLaunchKernelGGL(tree_move_pick_kernel, dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), make_tree(d),
+                       temperatures, force_uniform, uniforms, visit_offset, value_cutoff, chosen_index,
+                       reinterpret_cast<int4*>(chosen_code), reinterpret_cast<unsigned long long*>(counters));
     return st();
 }
 

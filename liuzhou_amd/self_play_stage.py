@@ -86,6 +86,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     shape_meta: Optional[Dict[str, Any]] = None
     resign_meta: Optional[Dict[str, Any]] = None
     kld_meta: Optional[Dict[str, Any]] = None
+    pick_meta: Optional[Dict[str, Any]] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -123,6 +124,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         wkl = (wm.get("metadata") or {}).get("kld_stop")
         if isinstance(wkl, dict) and kld_meta is None:
             kld_meta = {k: wkl.get(k) for k in ("threshold", "interval", "min_simulations")}
+        wmp = (wm.get("metadata") or {}).get("move_pick")
+        if isinstance(wmp, dict) and pick_meta is None:
+            pick_meta = {k: wmp.get(k) for k in ("visit_offset", "value_cutoff", "temperature_halflife")}
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -157,6 +161,10 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     if kld_meta is not None:            # KLD-gain early stopping: its settings, the stopped searches of all workers
         from .kld_stop import COUNTER_KEYS as KLD_COUNTER_KEYS
         meta["kld_stop"] = {**kld_meta, **{k: int(merged.mcts_counters.get(k, 0)) for k in KLD_COUNTER_KEYS}}
+    if pick_meta is not None:           # move selection: its settings, and the re-pick's counters where the re-pick ran
+        from .move_pick import COUNTER_KEYS as PICK_COUNTER_KEYS
+        meta["move_pick"] = {**pick_meta, **{k: int(merged.mcts_counters[k]) for k in PICK_COUNTER_KEYS
+                                             if k in merged.mcts_counters}}
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -187,7 +195,9 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         cpuct_base: float = 19652.0, resign_threshold: float = 0.0, resign_min_moves: int = 10,
                         resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
                         resign_streak: str = "side", kld_stop_threshold: float = 0.0, kld_stop_interval: int = 100,
-                        kld_stop_min_simulations: Optional[int] = None) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
+                        move_value_cutoff: float = 0.0,
+                        temperature_halflife: float = 0.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
@@ -202,7 +212,12 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
     of the two halves is on, and `resign_threshold` / `resign_min_moves` / `resign_consecutive` /
     `resign_playthrough_fraction` / `resign_streak` (tree backend, resignation with play-through calibration) only when
     resign_threshold < 0, and `kld_stop_threshold` / `kld_stop_interval` / `kld_stop_min_simulations` (tree backend, KLD-gain
-    early stopping of the searches) only when kld_stop_threshold > 0."""
+    early stopping of the searches) only when kld_stop_threshold > 0, and `move_visit_offset` / `move_value_cutoff` (tree
+    backend, visit-offset / value-cutoff move selection) only when one of the two is above 0, `temperature_halflife` (tree
+    backend, decaying move temperature) only when it is."""
+    from .move_pick import move_pick_kwargs, move_pick_refusal, refuse_backend as pick_refuse_backend
+    pick = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
+    pick_refuse_backend(bool(pick), search_backend)
     from .kld_stop import kld_stop_refusal, parse_kld_stop, refuse_backend as kld_refuse_backend
     kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
     kld_refuse_backend(kld.on, search_backend)
@@ -225,6 +240,10 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
         raise ValueError(f"TD(lambda) value targets need the tree backend, not the root-PUCT search ({search_backend!r}): "
                          "they blend the tree search's root values")
     gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
+    if "move_visit_offset" in pick:
+        why = move_pick_refusal(sample_moves=sample_moves, gumbel_considered=gumbel_considered if gumbel else 0)
+        if why is not None:
+            raise ValueError(f"visit-offset / value-cutoff move selection is not supported with {why}")
     if kld.on:
         why = kld_stop_refusal(gumbel_considered=gumbel_considered if gumbel else 0)
         if why is not None:
@@ -282,7 +301,7 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
                 "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
             **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-            **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign, **kld.kwargs())
+            **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign, **kld.kwargs(), **pick)
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

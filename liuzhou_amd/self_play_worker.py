@@ -590,7 +590,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          cpuct_base: float = 19652.0, resign_threshold: float = 0.0, resign_min_moves: int = 10,
                          resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
                          resign_streak: str = "side", kld_stop_threshold: float = 0.0, kld_stop_interval: int = 100,
-                         kld_stop_min_simulations: Optional[int] = None) -> Dict[str, Any]:
+                         kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
+                         move_value_cutoff: float = 0.0, temperature_halflife: float = 0.0) -> Dict[str, Any]:
     """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
     `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
     tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on.
@@ -612,7 +613,20 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
     tree_engine.self_play_tree_gpu.  The five values are recorded in the manifests' metadata["resign"] when on.
     `kld_stop_threshold` (tree backend only; 0 = off), `kld_stop_interval`, `kld_stop_min_simulations` (None = the
     interval): KLD-gain early stopping of the searches, see tree_engine.self_play_tree_gpu.  The three values are recorded
-    in the manifests' metadata["kld_stop"] when on."""
+    in the manifests' metadata["kld_stop"] when on.
+    `move_visit_offset` / `move_value_cutoff` (tree backend only; 0 = off): visit-offset / value-cutoff move selection;
+    `temperature_halflife` (tree backend only; 0 = off): the move temperature decays with this half-life below
+    `temperature_threshold`; see tree_engine.self_play_tree_gpu.  The three values are recorded in the manifests'
+    metadata["move_pick"] when any of them is on."""
+    from .move_pick import move_pick_kwargs, move_pick_meta, move_pick_refusal, refuse_backend as pick_refuse_backend
+    pick = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
+    pick_refuse_backend(bool(pick), search_backend)
+    if "move_visit_offset" in pick:
+        from .gumbel import gumbel_on as _gumbel_on
+        why = move_pick_refusal(sample_moves=sample_moves, gumbel_considered=gumbel_considered
+                                if _gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale) else 0)
+        if why is not None:
+            raise ValueError(f"visit-offset / value-cutoff move selection is not supported with {why}")
     from .kld_stop import kld_stop_refusal, parse_kld_stop, refuse_backend as kld_refuse_backend
     kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
     kld_refuse_backend(kld.on, search_backend)
@@ -730,7 +744,7 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                               "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
                                           **({"value_target_lambda": float(value_target_lambda)} if td else {}),
                                           **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign,
-                                          **kld.kwargs(),
+                                          **kld.kwargs(), **pick,
                                           **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
@@ -757,7 +771,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        **({"mcts_solver": True} if solver else {}),
                        **({"puct_shape": shape.meta()} if shape.on else {}),
                        **({"resign": resign_meta(resign)} if resign else {}),
-                       **({"kld_stop": kld.meta()} if kld.on else {})}
+                       **({"kld_stop": kld.meta()} if kld.on else {}),
+                       **({"move_pick": move_pick_meta(pick)} if pick else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

@@ -34,6 +34,8 @@ from .self_play_types import SelfPlayV1Stats
 from .streams import CAPTURE_MODE
 from .trajectory_buffer import TensorSelfPlayBatch, TensorTrajectoryBuffer
 from .kld_stop import INTERVAL_DEFAULT as KLD_INTERVAL_DEFAULT, KldStop, kld_stop_refusal, parse_kld_stop
+from .move_pick import (counters_from_block as move_pick_counters, move_pick_kwargs, move_pick_on, move_pick_refusal,
+                        temperature_table)
 from .resign import counters_from_block, resign_kwargs
 from .value_target import td_lambda_on
 
@@ -635,6 +637,26 @@ class TreeEngine:
                                                 L.ptr(self.chosen_code), L.ptr(self.chosen_valid),
                                                 L.ptr(self.solver_overrides), self._stream()), "tree_solver_pick")
 
+    def move_pick(self, temperatures: torch.Tensor, uniforms: Optional[torch.Tensor], visit_offset: float = 0.0,
+                  value_cutoff: float = 0.0, force_uniform: Optional[torch.Tensor] = None, sample_moves: bool = True,
+                  counters: Optional[torch.Tensor] = None) -> None:
+        """lz_tree_move_pick over the last finish()'s picks, with the temperatures / uniforms / force mask that finish was
+        given: the visit-offset / value-cutoff re-pick of the games whose move was sampled from the visits (move_pick.py,
+        DESIGN.md section 19).  `counters` int64[4] (optional): games applied to, children cut by the offset, children cut
+        by the value cutoff, picks changed.  Nothing is launched with both parameters 0 or without `sample_moves`; call it
+        before solver_pick()."""
+        if float(visit_offset) == 0.0 and float(value_cutoff) == 0.0:
+            return
+        if force_uniform is not None and force_uniform.dtype != torch.uint8:
+            force_uniform = force_uniform.to(torch.uint8)
+        if counters is not None and (counters.dtype != torch.int64 or counters.numel() < 4 or not counters.is_contiguous()):
+            raise ValueError("move_pick counters must be a contiguous int64 tensor of 4 entries")
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_tree_move_pick(C.byref(self.desc), L.ptr(temperatures), L.ptr(force_uniform), L.ptr(uniforms),
+                                              C.c_int(int(bool(sample_moves))), C.c_double(float(visit_offset)),
+                                              C.c_double(float(value_cutoff)), L.ptr(self.chosen_index),
+                                              L.ptr(self.chosen_code), L.ptr(counters), self._stream()), "tree_move_pick")
+
     _NODE_DT = [("w0", "<u8"), ("w1", "<u8"), ("w2", "<u8"), ("w3", "<u8"), ("edge_begin", "<i4"), ("nedges", "<i4"),
                 ("parent", "<i4"), ("old_begin", "<i4")]
     _EDGE_DT = [("W", "<f8"), ("P", "<f4"), ("n_info", "<u4"), ("child", "<i4"), ("cbegin", "<i4"),
@@ -939,7 +961,8 @@ class PortableTreeMCTS:
                  gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0, solver: bool = False,
                  fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
                  cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT,
-                 cpuct_table_len: int = CPUCT_TABLE_LEN, kld_stop: Optional[KldStop] = None) -> None:
+                 cpuct_table_len: int = CPUCT_TABLE_LEN, kld_stop: Optional[KldStop] = None,
+                 move_visit_offset: float = 0.0, move_value_cutoff: float = 0.0) -> None:
         """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
         searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
         FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
@@ -1004,7 +1027,14 @@ class PortableTreeMCTS:
         search left in it; `kld_counts` (int64[2]) sums the stopped searches and the simulations they did not run; parity
         runs hand every game its budget through `injected_sim_budget` (int32[B], honoured by any search that owns a budget
         array, after the cap's draw).  Searches then always use the compact lists.  Refused where the cap is refused and
-        with the Gumbel root search (ValueError)."""
+        with the Gumbel root search (ValueError).
+        `move_visit_offset` o (>= 0), `move_value_cutoff` c (in [0, 2]; both 0 = off): visit-offset / value-cutoff move
+        selection (move_pick.py).  Where the finish sampled a game's move from the visits, one kernel
+        behind it (TreeEngine.move_pick) draws the move again with the same uniform from the children that keep more than o
+        visits and whose mean value is within c of the most visited child's; the solver pick, if on, still has the last
+        word.  Training targets and every other output stay as the finish wrote them.  `move_pick_counts` (int64[4]):
+        games re-picked, children cut by the offset, children cut by the value test, picks changed.  Composes with
+        everything but the Gumbel root search and `sample_moves=False` (ValueError)."""
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
         self.solver = bool(solver)
@@ -1040,6 +1070,12 @@ class PortableTreeMCTS:
                                    gumbel_considered=gumbel_considered if self.gumbel else 0)
             if why is not None:
                 raise ValueError(f"KLD-gain early stopping is not supported with {why}")
+        self.move_pick = move_pick_on(move_visit_offset, move_value_cutoff)
+        self.move_visit_offset, self.move_value_cutoff = float(move_visit_offset), float(move_value_cutoff)
+        if self.move_pick:
+            why = move_pick_refusal(sample_moves=sample_moves, gumbel_considered=gumbel_considered if self.gumbel else 0)
+            if why is not None:
+                raise ValueError(f"visit-offset / value-cutoff move selection is not supported with {why}")
         self.cap = playout_cap_on(fast_simulations, full_prob, num_simulations)
         self.fast_simulations, self.full_prob = int(fast_simulations), float(full_prob)
         if self.cap:
@@ -1100,6 +1136,9 @@ class PortableTreeMCTS:
         self._roots_decided = torch.zeros((1,), dtype=torch.int64, device=self.engine.device)
         if self.solver:
             self.engine.set_solver(True)
+        # visit-offset / value-cutoff move selection: the counter block exists only when the rule is on
+        self._move_pick_counts = (torch.zeros((4,), dtype=torch.int64, device=self.engine.device)
+                                  if self.move_pick else None)
         if self.puct_shape.on:
             self.engine.set_puct_shape(**self.puct_shape.kwargs(), table_len=int(cpuct_table_len))
         if not self.fused:
@@ -1211,6 +1250,18 @@ class PortableTreeMCTS:
         e = self.engine
         return torch.cat((e.solver_count.sum(dtype=torch.int64).view(1), self._roots_decided,
                           e.solver_overrides.sum(dtype=torch.int64).view(1)))
+
+    @property
+    def move_pick_counts(self) -> torch.Tensor:
+        """int64[4] on the device: games the move re-pick applied to, children cut by the visit offset, children cut by the
+        value cutoff and picks that differ from the finish's, so far (zeros when off)."""
+        if not self.move_pick:
+            return torch.zeros((4,), dtype=torch.int64, device=self.engine.device)
+        return self._move_pick_counts
+
+    def _reset_move_pick_counts(self) -> None:
+        if self.move_pick:
+            self._move_pick_counts.zero_()
 
     def _reset_solver_counts(self) -> None:
         self._roots_decided.zero_()
@@ -1479,6 +1530,7 @@ class PortableTreeMCTS:
             self.engine.gumbel["count"].zero_()
         self._reset_solver_counts()
         self._reset_kld_counts()
+        self._reset_move_pick_counts()
         # refused expansions / fewest free chunks are per run too (a cached engine must not report an earlier run's)
         # (pool_stats[2], the chunks reserved for fresh roots, follows the trees' state and is NOT a per-run statistic)
         self.engine.buf["pool_stats"][:2].copy_(torch.tensor([0, self.engine.pool_chunks], dtype=torch.int32))
@@ -1507,6 +1559,7 @@ class PortableTreeMCTS:
             self.engine.gumbel["count"].zero_()
         self._reset_solver_counts()
         self._reset_kld_counts()
+        self._reset_move_pick_counts()
         self.get_timing(reset=True)
         if self.batch_k > 1:
             self.engine.wbuf["eval_total"].zero_(); self.engine.wbuf["eval_count"].zero_()
@@ -1595,6 +1648,9 @@ class PortableTreeMCTS:
             e.finish(temps, uniforms, tt, self.prior_pseudocount, force_uniform_random_mask, self.sample_moves)
             if self.forced:
                 self._pruned_total.add_(e.pruned_visits.sum(dtype=torch.int64))
+            if self.move_pick:            # re-pick of the sampled moves; in front of the solver, which keeps the last word
+                e.move_pick(temps, uniforms, self.move_visit_offset, self.move_value_cutoff, force_uniform_random_mask,
+                            self.sample_moves, self._move_pick_counts)
             if self.solver:               # a proven win is played, a proven loss is not while another move exists
                 e.solver_pick(force_uniform_random_mask)
                 self._roots_decided.add_((e.root_proven != 0).sum(dtype=torch.int64))
@@ -1652,6 +1708,7 @@ class DualStreamTreeMCTS:
         self.gumbel = self.parts[0].gumbel
         self.solver = self.parts[0].solver
         self.puct_shape = self.parts[0].puct_shape
+        self.move_pick = self.parts[0].move_pick
         self.full_search = None
         if self.cap:
             self.full_search = torch.zeros((self.B,), dtype=torch.uint8, device=dev)
@@ -1709,6 +1766,10 @@ class DualStreamTreeMCTS:
     @property
     def kld_counts(self) -> torch.Tensor:
         return sum(p.kld_counts for p in self.parts)
+
+    @property
+    def move_pick_counts(self) -> torch.Tensor:
+        return sum(p.move_pick_counts for p in self.parts)
 
     @property
     def last_sim_budget(self) -> Optional[torch.Tensor]:
@@ -1976,7 +2037,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        resign_min_moves: int = 10, resign_consecutive: int = 3,
                        resign_playthrough_fraction: float = 0.1, resign_streak: str = "side",
                        kld_stop_threshold: float = 0.0, kld_stop_interval: int = KLD_INTERVAL_DEFAULT,
-                       kld_stop_min_simulations: Optional[int] = None
+                       kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
+                       move_value_cutoff: float = 0.0, temperature_halflife: float = 0.0
                        ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
@@ -2031,8 +2093,22 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     apart.  mcts_counters gain kld_stopped_searches / kld_simulations_saved.  Fused network and batch_k = 1 only, not with
     the Gumbel root search or the persistent kernel (ValueError); composes with everything else -- with the playout cap the
     cap's draw sets the budget and the rule may only lower it.  Off, nothing is allocated or launched and every output is
-    byte-identical."""
+    byte-identical.
+    `move_visit_offset` o (0 = off), `move_value_cutoff` c (0 = off; at most 2): visit-offset / value-cutoff move selection
+    (move_pick.py, PortableTreeMCTS).  On the plies whose move is sampled from the visits, the move
+    is drawn again, with the same uniform, from the root children that keep more than o visits and whose mean value is
+    within c of the most visited child's; rows, targets and the RNG streams are untouched, so only the game paths change.
+    mcts_counters gain move_pick_applied / move_pick_cut_visits / move_pick_cut_value / move_pick_changed.  Not with the
+    Gumbel root search or `sample_moves=False` (ValueError); composes with everything else.
+    `temperature_halflife` h (0 = off): the move temperature of ply p below `temperature_threshold` is temperature_final
+    + (temperature_init - temperature_final) * 0.5^(p / h) instead of temperature_init, from a float32 table built once
+    on the host (move_pick.temperature_table).  Where the policy target follows the move temperature
+    (`policy_target_temperature` None) it follows the half-life too, exactly as it follows the step.  Off, nothing is
+    allocated or launched and every output is byte-identical."""
     dev = torch.device(device)
+    pick_kw = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
+    repick = "move_visit_offset" in pick_kw
+    halflife = float(pick_kw.get("temperature_halflife", 0.0))
     solver = bool(mcts_solver)
     kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
     resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
@@ -2091,6 +2167,10 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         why = kld_stop_refusal(batch_k=batch_k, fused=use_fused, gumbel_considered=gumbel_considered if gumbel else 0)
         if why is not None:
             raise ValueError(f"KLD-gain early stopping is not supported with {why}")
+    if repick:
+        why = move_pick_refusal(sample_moves=sample_moves, gumbel_considered=gumbel_considered if gumbel else 0)
+        if why is not None:
+            raise ValueError(f"visit-offset / value-cutoff move selection is not supported with {why}")
     if use_fused and persistent_search_available(net, batch_k) and eval_symmetry == "none":
         if cap:
             raise ValueError("playout cap randomization is not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
@@ -2117,6 +2197,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     kw.update(shape.kwargs())
     if kld.on:
         kw["kld_stop"] = kld
+    if repick:
+        kw.update(move_visit_offset=float(move_visit_offset), move_value_cutoff=float(move_value_cutoff))
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a
@@ -2161,6 +2243,11 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         if cap:
             tail.record_mask = mcts.full_search
     continuous = tail is not None and bool(continuous_waves)
+    # temperature half-life: the schedule as a table, indexed by the ply on the device (tail and host loop alike)
+    temp_table = None
+    if halflife > 0.0:
+        temp_table = torch.from_numpy(temperature_table(temperature_init, temperature_final, temperature_threshold,
+                                                        halflife, int(max_game_plies))).to(dev)
     wasted_plies = 0
     started = time.perf_counter()
     for base in range(0, wave if continuous else int(num_games), wave):
@@ -2191,7 +2278,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                          **({"compact": True} if (use_fused and tail.live_estimate <= lists_below) else {})),
                      states, plies, done, step_index, step_counts, lengths if continuous else lengths[base:base + g],
                      temperature_init, temperature_final, temperature_threshold,
-                     games_to_start=int(num_games) - wave if continuous else 0)
+                     games_to_start=int(num_games) - wave if continuous else 0,
+                     **({"temperature_table": temp_table} if temp_table is not None else {}))
 
             wasted_plies += 1
             continue
@@ -2199,8 +2287,11 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
             active = torch.nonzero(~done).view(-1)
             if int(active.numel()) == 0:
                 break
-            temps = torch.where(plies < int(temperature_threshold), float(temperature_init),
-                                float(temperature_final)).to(torch.float32)
+            if temp_table is not None:
+                temps = temp_table.index_select(0, plies.clamp(0, int(temp_table.numel()) - 1))
+            else:
+                temps = torch.where(plies < int(temperature_threshold), float(temperature_init),
+                                    float(temperature_final)).to(torch.float32)
             force = (plies < int(opening_random_moves)) if int(opening_random_moves) > 0 else None
             out = mcts.search_batch(states, temperatures=temps, active=~done, force_uniform_random_mask=force,
                                     rng_game_ids=slot_ids + base, rng_plies=plies)
@@ -2307,6 +2398,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        # KLD-gain early stopping: searches it ended early, simulations they did not run
                        **(dict(zip(("kld_stopped_searches", "kld_simulations_saved"),
                                    (int(x) for x in mcts.kld_counts.tolist()))) if kld.on else {}),
+                       # move re-pick: games it applied to, children cut by offset / value, picks it changed
+                       **(move_pick_counters(mcts.move_pick_counts.tolist()) if repick else {}),
                        # resignation: games that resigned, the play-through games and their false positives
                        **(counters_from_block(tail.resign_counters.tolist()) if resign else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))

@@ -234,7 +234,7 @@ class WaveTail:
 
     def run(self, search_fn, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, step_index: torch.Tensor,
             step_counts: torch.Tensor, lengths: torch.Tensor, t_init: float, t_final: float, t_threshold: int,
-            games_to_start: int = 0) -> int:
+            games_to_start: int = 0, temperature_table: Optional[torch.Tensor] = None) -> int:
         """The wave loop with nothing per ply on the host: `search_fn(states, temperatures, done, reseated)` ->
         RootSearchBatchOutput for all slots (finished ones are masked by `done`; `reseated` uint8 marks slots that
         have just started a new game), then record / move / finalise on the device.  `games_to_start` > 0: a slot
@@ -247,7 +247,9 @@ class WaveTail:
         With TD(lambda) value targets (`value_target_lambda` < 1) the order per ply is record -> note_value -> step_finish
         -> td_targets -> the log: the rows of a game that ends carry their final targets before they leave.
         With resignation (`resign_threshold` < 0) it is record -> note_value -> resign -> step_finish -> resign_book ->
-        td_targets -> the log."""
+        td_targets -> the log.
+        `temperature_table` (float32 on the device, move_pick.temperature_table: the half-life schedule): the temperature of
+        a slot is table[min(ply, len - 1)] instead of the t_init / t_final step at `t_threshold`."""
         dev, g = self.device, self.G
         log = self.row_log
         if (log is None) == (step_index is None):
@@ -276,7 +278,10 @@ class WaveTail:
                     log.poll(k)                                   # may switch log arenas (a segment leaves)
             if games_to_start > 0 and ply > 0:
                 self.start_next_games(states, plies, done, step_counts, budget, next_game, slot_game, reseated)
-            temps = torch.where(plies < int(t_threshold), float(t_init), float(t_final)).to(torch.float32)
+            if temperature_table is not None:
+                temps = temperature_table.index_select(0, plies.clamp(0, int(temperature_table.numel()) - 1))
+            else:
+                temps = torch.where(plies < int(t_threshold), float(t_init), float(t_final)).to(torch.float32)
             search = search_fn(states, temps, done, reseated)
             reseated.zero_()
             with self._bracket("finalize_ms"):

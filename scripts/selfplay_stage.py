@@ -89,6 +89,15 @@ def parse(argv=None):
     ap.add_argument("--kld_stop_interval", type=int, default=100, help="KLD-gain early stopping: simulations between checks")
     ap.add_argument("--kld_stop_min_simulations", type=int, default=None,
                     help="KLD-gain early stopping: no stop before this many simulations (default: the interval)")
+    ap.add_argument("--move_visit_offset", type=float, default=0.0,
+                    help="move selection (tree backend): visits subtracted from every root child before the move is "
+                         "sampled; children left with none are not played; 0 = off")
+    ap.add_argument("--move_value_cutoff", type=float, default=0.0,
+                    help="move selection (tree backend): children whose mean value is more than this below the most "
+                         "visited child's are not played; in [0, 2], 0 = off")
+    ap.add_argument("--temperature_halflife", type=float, default=0.0,
+                    help="move temperature (tree backend): below --temperature_threshold the excess over "
+                         "--temperature_final halves every this many plies; 0 = off (the step)")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -160,7 +169,10 @@ def main(argv=None) -> int:
         resign_playthrough_fraction=args.self_play_resign_playthrough_fraction,
         resign_streak=args.self_play_resign_streak,
         **({"kld_stop_threshold": args.kld_stop_threshold, "kld_stop_interval": args.kld_stop_interval,
-            "kld_stop_min_simulations": args.kld_stop_min_simulations} if args.kld_stop_threshold != 0.0 else {}))
+            "kld_stop_min_simulations": args.kld_stop_min_simulations} if args.kld_stop_threshold != 0.0 else {}),
+        **({"move_visit_offset": args.move_visit_offset, "move_value_cutoff": args.move_value_cutoff}
+           if (args.move_visit_offset != 0.0 or args.move_value_cutoff != 0.0) else {}),
+        **({"temperature_halflife": args.temperature_halflife} if args.temperature_halflife != 0.0 else {}))
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
