@@ -322,6 +322,41 @@ LZ_API int lz_wave_resign_book(const LzStateSoA* states, int64_t num_slots, cons
                                const int32_t* would_ply, const int64_t* slot_game, int64_t game_base, uint64_t seed,
                                float playthrough_fraction, int64_t* counters, void* stream);
 
+/* Policy surprise weighting of a finished game's rows (KataGo's policySurpriseDataWeight; off in the reference).
+ * Surprise of a recorded row: s = max(0, sum over legal actions with pi_a > 0 of pi_a (log pi_a - log max(p_a, 1e-30))),
+ * pi = the row's policy target, p = the noise-free network prior of the searched position; double arithmetic, stored as
+ * float32.  Weights of a finished game with N rows and S = sum s_j: w_j = (1 - alpha) + alpha N s_j / S if S > 1e-12 N,
+ * else 1 (sum w_j = N).  Systematic resampling: u = u01 of one Philox draw of lz_rng.h (purpose 3, ply 0, index 1022), a
+ * pure function of (seed, game id), game id = (slot_game ? slot_game[g] : g) + game_base; with C_j the running sum of
+ * the weights in double and C_N := N, row j is written floor(C_j + u) - floor(C_(j-1) + u) times, and output slot k holds
+ * source row src[k], non-decreasing in k.  The scalar arithmetic is csrc/lz_surprise.h (host and device).
+ *
+ * lz_wave_note_surprise: after lz_wave_record / lz_wave_note_value, before lz_wave_resign / lz_wave_step_finish.  One
+ * wave per slot.  A live slot that recorded a row this ply (rows[g] >= 0) gets surprise_hist[g, step_counts[g] - 1] = s
+ * from legal_mask uint8[num_slots, action_dim], policy_dense and prior float32[num_slots, action_dim]; every live slot
+ * gets was_live[g] = 1, a finished one was_live[g] = 0 and is otherwise untouched.  surprise_hist float32[num_slots,
+ * max_steps].  A step outside [1, max_steps] writes nothing and bumps *overflow.
+ *
+ * lz_wave_surprise_resample: after lz_wave_step_finish (reseat == 0), lz_wave_resign_book and lz_wave_td_targets, before
+ * lz_wave_log_finished.  One wave per slot whose game ended this ply (was_live[g] && done[g]) with N = step_counts[g] >
+ * 0: src[g, 0..N) is written (int32[num_slots, max_steps], scratch that stays readable) and the game's rows are
+ * rewritten in place, row_k <- row_src[k] in all six arena tensors (state float32[396], legal mask uint8[action_dim],
+ * policy float32[action_dim], value, soft value, sign), row_j = step_index_matrix[g, j], or g * max_steps + j when
+ * step_index_matrix == NULL.  counters int64[3] += {games, their rows, rows that got no slot (= extra copies written)},
+ * *surprise_sum (double) += S.  step_counts, other slots' rows and games that ended on an earlier ply are untouched.
+ * action_dim must be a multiple of 4, at most 256 (LZ_ERR_UNSUPPORTED); arena_state and arena_policy 16-byte, arena_legal
+ * 4-byte, surprise_sum 8-byte aligned (LZ_ERR_ALIGN); alpha in [0, 1] (LZ_ERR_ARG). */
+LZ_API int lz_wave_note_surprise(const uint8_t* done, int64_t num_slots, const int64_t* rows,
+                                 const int64_t* step_counts, const uint8_t* legal_mask, const float* policy_dense,
+                                 const float* prior, int64_t action_dim, float* surprise_hist, uint8_t* was_live,
+                                 int64_t max_steps, int32_t* overflow, void* stream);
+LZ_API int lz_wave_surprise_resample(const uint8_t* done, const uint8_t* was_live, int64_t num_slots, double alpha,
+                                     const float* surprise_hist, const int64_t* slot_game, int64_t game_base,
+                                     uint64_t seed, float* arena_state, uint8_t* arena_legal, float* arena_policy,
+                                     float* arena_value, float* arena_soft, int8_t* arena_sign, int64_t action_dim,
+                                     const int64_t* step_index_matrix, const int64_t* step_counts, int64_t max_steps,
+                                     int32_t* src, int64_t* counters, double* surprise_sum, void* stream);
+
 /* lz_wave_reseat: the wave loop of self_play_gpu_runner.py:84-90 starts the next `concurrent_games` games only when the
  * whole wave has finished; here finished slots (done[g] != 0, ascending g) restart from the empty board at once while
  * *budget (games not yet started) lasts: slot_game[g] = (*next_game)++, plies / step_counts = 0, done[g] = 0,

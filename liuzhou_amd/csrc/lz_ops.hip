@@ -15,6 +15,7 @@
 
 #include "lz_rng.h"
 #include "lz_soa.h"
+#include "lz_surprise.h"
 #include "lz_wave.h"
 
 using namespace lz;
@@ -1536,6 +1537,168 @@ __global__ __launch_bounds__(kBlock) void wave_resign_book_kernel(
     atomicAdd(&counters[7], (unsigned long long)(p - (int64_t)would_ply[g]));
 }
 
+// ---- policy surprise weighting (KataGo's policySurpriseDataWeight; lz_surprise.h holds the scalar arithmetic): a share
+// alpha of a finished game's total row weight is handed out in proportion to KL(policy target || network prior), and
+// the weights become copy counts by systematic resampling inside the game's own row slots.
+// one wave per slot, after wave_record_kernel / wave_note_value_kernel and before the resign / step kernels: the
+// surprise of the row this ply recorded.  Lanes stride the T actions, double arithmetic, one float32 rounding.
+__global__ __launch_bounds__(kBlock) void wave_note_surprise_kernel(
+    const uint8_t* __restrict__ done, int64_t G, const int64_t* __restrict__ rows,
+    const int64_t* __restrict__ step_counts, const uint8_t* __restrict__ legal, const float* __restrict__ policy,
+    const float* __restrict__ prior, int T, float* __restrict__ surprise_hist, uint8_t* __restrict__ was_live,
+    int64_t max_steps, int32_t* __restrict__ overflow) {
+    const int lane = lane_id();
+    const int64_t g = wave_item();
+    if (g >= G) return;
+    if (done[g] != 0) { if (lane == 0) was_live[g] = 0; return; }
+    if (lane == 0) was_live[g] = 1;
+    if (rows[g] < 0) return;                            // no row this ply (a fast search of the playout cap)
+    const int64_t n = step_counts[g];                   // wave_rows*_kernel has counted this ply's row already
+    if (n < 1 || n > max_steps) { if (lane == 0) atomicAdd(overflow, 1); return; }
+    double acc = 0.0;
+    for (int a = lane; a < T; a += kWave)
+        acc += lzsurprise::term(legal[g * T + a] != 0, policy[g * T + a], prior[g * T + a]);
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) acc += __shfl_xor(acc, d, kWave);
+    if (lane == 0) surprise_hist[g * max_steps + n - 1] = (float)(acc > 0.0 ? acc : 0.0);
+}
+
+// one lane's share of an arena row: state 99 x 16 B (lanes 0..63 and 0..34), policy and legal mask T / 4 pieces of 16 B and
+// 4 B (T / 4 <= 64), the three scalars on lane 0
+struct SurpriseRow { float4 s0, s1, p; uint32_t l; float v, sf; int8_t sg; };
+
+__device__ __forceinline__ SurpriseRow surprise_row_load(
+    int lane, int64_t row, int T4, const float* a_state, const uint8_t* a_legal, const float* a_policy,
+    const float* a_value, const float* a_soft, const int8_t* a_sign) {
+    constexpr int kIn4 = 11 * 36 / 4;
+    SurpriseRow r{};
+    const float4* st = reinterpret_cast<const float4*>(a_state) + row * kIn4;
+    r.s0 = st[lane];
+    if (lane + kWave < kIn4) r.s1 = st[lane + kWave];
+    if (lane < T4) {
+        r.p = (reinterpret_cast<const float4*>(a_policy) + row * T4)[lane];
+        r.l = (reinterpret_cast<const uint32_t*>(a_legal) + row * T4)[lane];
+    }
+    if (lane == 0) { r.v = a_value[row]; r.sf = a_soft[row]; r.sg = a_sign[row]; }
+    return r;
+}
+
+__device__ __forceinline__ void surprise_row_store(
+    const SurpriseRow& r, int lane, int64_t row, int T4, float* a_state, uint8_t* a_legal, float* a_policy,
+    float* a_value, float* a_soft, int8_t* a_sign) {
+    constexpr int kIn4 = 11 * 36 / 4;
+    float4* st = reinterpret_cast<float4*>(a_state) + row * kIn4;
+    st[lane] = r.s0;
+    if (lane + kWave < kIn4) st[lane + kWave] = r.s1;
+    if (lane < T4) {
+        (reinterpret_cast<float4*>(a_policy) + row * T4)[lane] = r.p;
+        (reinterpret_cast<uint32_t*>(a_legal) + row * T4)[lane] = r.l;
+    }
+    if (lane == 0) { a_value[row] = r.v; a_soft[row] = r.sf; a_sign[row] = r.sg; }
+}
+
+// one wave per slot whose game ended this ply, after wave_step_finish_kernel / wave_resign_book_kernel /
+// wave_td_targets_kernel and before the finished-row log.  S by a wave reduction, the running sums C_j by a 64-lane
+// Kogge-Stone scan per chunk of rows with a carry (C_N := N), the counts from lzsurprise::count; lane j writes
+// src[g, k] = j for its output slots k in [floor(C_(j-1) + u), floor(C_j + u)).  Then the rows move in place.
+// Why two passes are enough: src is non-decreasing.  Pass 1 visits the slots with src[k] > k in ascending k, pass 2 those
+// with src[k] < k in descending k.  Take a slot k of pass 1 and its source j = src[k] > k.  src[j] >= src[k] = j, so j is a
+// fixed point (never written) or itself a pass-1 slot, which pass 1 reaches after k: k reads j before anything is stored
+// there.  j is never a pass-2 slot (that needs src[j] < j), so pass 2 does not disturb what pass 1 read or wrote.  The
+// mirror argument (src[j] <= src[k] = j for j = src[k] < k) covers pass 2, and its sources are not pass-1 slots either,
+// so they still hold their original rows when pass 2 runs.  Within a pass the slots are taken kGroup at a time, all loads
+// before all stores: a source inside the group is read before the group stores anything, as the order above demands.
+// The arena pointers are deliberately not __restrict__: the loads and stores of successive groups alias.
+__global__ __launch_bounds__(kBlock) void wave_surprise_resample_kernel(
+    const uint8_t* __restrict__ done, const uint8_t* __restrict__ was_live, int64_t G, double alpha,
+    const float* __restrict__ surprise_hist, const int64_t* __restrict__ slot_game, int64_t game_base, uint64_t seed,
+    float* a_state, uint8_t* a_legal, float* a_policy, float* a_value, float* a_soft, int8_t* a_sign, int T4,
+    const int64_t* __restrict__ step_index, const int64_t* __restrict__ step_counts, int64_t max_steps, int32_t* src,
+    unsigned long long* __restrict__ counters, double* __restrict__ surprise_sum) {
+    constexpr int kGroup = 4;
+    const int lane = lane_id();
+    const int64_t g = wave_item();
+    if (g >= G) return;
+    if (was_live[g] == 0 || done[g] == 0) return;
+    int64_t n = step_counts[g];
+    if (n > max_steps) n = max_steps;
+    if (n <= 0) return;                                 // no recorded row: nothing to weigh
+    const float* sh = surprise_hist + g * max_steps;
+    int32_t* sg = src + g * max_steps;
+    double S = 0.0;
+    for (int64_t j = lane; j < n; j += kWave) S += (double)sh[j];
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) S += __shfl_xor(S, d, kWave);
+    const double u = (double)lzsurprise::game_u(seed, (slot_game ? slot_game[g] : g) + game_base);
+    double carry = 0.0;
+    int dropped = 0;
+    for (int64_t base = 0; base < n; base += kWave) {
+        const int64_t j = base + lane;
+        double incl = j < n ? lzsurprise::weight(alpha, n, (double)sh[j], S) : 0.0;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const double v = __shfl_up(incl, d, kWave);
+            if (lane >= d) incl += v;
+        }
+        double c_cur = carry + incl;
+        if (j == n - 1) c_cur = (double)n;
+        double c_prev = __shfl_up(c_cur, 1, kWave);
+        if (lane == 0) c_prev = carry;
+        carry = __shfl(c_cur, kWave - 1, kWave);
+        if (j < n) {
+            int64_t k0 = (int64_t)floor(c_prev + u), k1 = (int64_t)floor(c_cur + u);
+            if (k0 < 0) k0 = 0;
+            if (k1 > n) k1 = n;                         // both hold by construction; the writes stay inside src[g, 0..n)
+            if (k1 <= k0) ++dropped;
+            for (int64_t k = k0; k < k1; ++k) sg[k] = (int32_t)j;
+        }
+    }
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) dropped += __shfl_xor(dropped, d, kWave);
+    if (lane == 0) {
+        atomicAdd(&counters[0], 1ull);
+        atomicAdd(&counters[1], (unsigned long long)n);
+        atomicAdd(&counters[2], (unsigned long long)dropped);
+        atomicAdd(surprise_sum, S);
+    }
+    if (dropped == 0) return;                           // every count is 1: the identity, nothing moves
+    __threadfence();                                    // src[g, :] was written by other lanes of this wave
+    const int64_t* si = step_index ? step_index + g * max_steps : nullptr;
+    const int64_t first = g * max_steps;
+    for (int64_t k0 = 0; k0 < n; k0 += kGroup) {        // pass 1: sources above, ascending
+        SurpriseRow r[kGroup];
+        bool mv[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            const int64_t k = k0 + i;
+            const int64_t j = k < n ? (int64_t)sg[k] : -1;
+            mv[i] = j > k && j < n;
+            if (mv[i]) r[i] = surprise_row_load(lane, si ? si[j] : first + j, T4, a_state, a_legal, a_policy, a_value, a_soft, a_sign);
+        }
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            const int64_t k = k0 + i;
+            if (mv[i]) surprise_row_store(r[i], lane, si ? si[k] : first + k, T4, a_state, a_legal, a_policy, a_value, a_soft, a_sign);
+        }
+    }
+    for (int64_t k0 = n - 1; k0 >= 0; k0 -= kGroup) {   // pass 2: sources below, descending
+        SurpriseRow r[kGroup];
+        bool mv[kGroup];
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            const int64_t k = k0 - i;
+            const int64_t j = k >= 0 ? (int64_t)sg[k] : k;
+            mv[i] = j < k && j >= 0;
+            if (mv[i]) r[i] = surprise_row_load(lane, si ? si[j] : first + j, T4, a_state, a_legal, a_policy, a_value, a_soft, a_sign);
+        }
+#pragma unroll
+        for (int i = 0; i < kGroup; ++i) {
+            const int64_t k = k0 - i;
+            if (mv[i]) surprise_row_store(r[i], lane, si ? si[k] : first + k, T4, a_state, a_legal, a_policy, a_value, a_soft, a_sign);
+        }
+    }
+}
+
 // ---- finished-row log: the rows of a game leave the slot-major live arena for a game-major log the moment the game
 // has ended, so that a consumer can take finished samples away WHILE the wave goes on playing (the worker streams
 // them to the host; v1/python/self_play_worker.py:430-546 only sees its rows after a whole wave has drained).
@@ -2112,6 +2275,40 @@ int lz_wave_resign_book(const LzStateSoA* s, int64_t G, const uint8_t* done, con
     hipLaunchKernelGGL(wave_resign_book_kernel, dim3(grid_threads(G)), dim3(kBlock), 0, as_stream(stream), *s, G, done,
                        was_live, plies, terminal_out, chosen_valid_mask, resigned, would, would_ply, slot_game,
                        game_base, seed, playthrough_fraction, reinterpret_cast<unsigned long long*>(counters));
+    return launch_status();
+}
+
+int lz_wave_note_surprise(const uint8_t* done, int64_t G, const int64_t* rows, const int64_t* step_counts,
+                          const uint8_t* legal_mask, const float* policy_dense, const float* prior, int64_t T,
+                          float* surprise_hist, uint8_t* was_live, int64_t max_steps, int32_t* overflow, void* stream) {
+    if (G < 0 || T <= 0 || T > INT32_MAX || max_steps <= 0) return LZ_ERR_ARG;
+    if (G == 0) return LZ_OK;
+    if (!done || !rows || !step_counts || !legal_mask || !policy_dense || !prior || !surprise_hist || !was_live ||
+        !overflow)
+        return LZ_ERR_ARG;
+    hipLaunchKernelGGL(wave_note_surprise_kernel, dim3(grid_waves(G)), dim3(kBlock), 0, as_stream(stream), done, G, rows,
+                       step_counts, legal_mask, policy_dense, prior, (int)T, surprise_hist, was_live, max_steps,
+                       overflow);
+    return launch_status();
+}
+
+int lz_wave_surprise_resample(const uint8_t* done, const uint8_t* was_live, int64_t G, double alpha,
+                              const float* surprise_hist, const int64_t* slot_game, int64_t game_base, uint64_t seed,
+                              float* a_state, uint8_t* a_legal, float* a_policy, float* a_value, float* a_soft,
+                              int8_t* a_sign, int64_t T, const int64_t* step_index, const int64_t* step_counts,
+                              int64_t max_steps, int32_t* src, int64_t* counters, double* surprise_sum, void* stream) {
+    if (G < 0 || max_steps <= 0 || max_steps > INT32_MAX || !(alpha >= 0.0 && alpha <= 1.0)) return LZ_ERR_ARG;
+    if (T <= 0 || (T & 3) != 0 || T / 4 > kWave) return LZ_ERR_UNSUPPORTED;        // a row's policy / mask: one 16 B / 4 B piece per lane
+    if (G == 0) return LZ_OK;
+    if (!done || !was_live || !surprise_hist || !a_state || !a_legal || !a_policy || !a_value || !a_soft || !a_sign ||
+        !step_counts || !src || !counters || !surprise_sum)
+        return LZ_ERR_ARG;                                 // step_index == NULL: slot-major arena (row = g * max_steps + j)
+    if (!aligned(a_state, 16) || !aligned(a_policy, 16) || !aligned(a_legal, 4) || !aligned(surprise_sum, 8))
+        return LZ_ERR_ALIGN;
+    hipLaunchKernelGGL(wave_surprise_resample_kernel, dim3(grid_waves(G)), dim3(kBlock), 0, as_stream(stream), done,
+                       was_live, G, alpha, surprise_hist, slot_game, game_base, seed, a_state, a_legal, a_policy, a_value,
+                       a_soft, a_sign, (int)(T / 4), step_index, step_counts, max_steps, src,
+                       reinterpret_cast<unsigned long long*>(counters), surprise_sum);
     return launch_status();
 }
 

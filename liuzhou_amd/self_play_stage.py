@@ -87,6 +87,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     resign_meta: Optional[Dict[str, Any]] = None
     kld_meta: Optional[Dict[str, Any]] = None
     pick_meta: Optional[Dict[str, Any]] = None
+    surprise_weight: Optional[float] = None
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -127,6 +128,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         wmp = (wm.get("metadata") or {}).get("move_pick")
         if isinstance(wmp, dict) and pick_meta is None:
             pick_meta = {k: wmp.get(k) for k in ("visit_offset", "value_cutoff", "temperature_halflife")}
+        wps = (wm.get("metadata") or {}).get("policy_surprise")
+        if isinstance(wps, dict) and surprise_weight is None:
+            surprise_weight = float(wps.get("weight", 0.0))
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -165,6 +169,9 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
         from .move_pick import COUNTER_KEYS as PICK_COUNTER_KEYS
         meta["move_pick"] = {**pick_meta, **{k: int(merged.mcts_counters[k]) for k in PICK_COUNTER_KEYS
                                              if k in merged.mcts_counters}}
+    if surprise_weight is not None:     # policy surprise weighting: its weight, what the resampling did over all workers
+        from .policy_surprise import surprise_meta
+        meta["policy_surprise"] = surprise_meta(surprise_weight, merged.mcts_counters)
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -197,7 +204,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         resign_streak: str = "side", kld_stop_threshold: float = 0.0, kld_stop_interval: int = 100,
                         kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
                         move_value_cutoff: float = 0.0,
-                        temperature_halflife: float = 0.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        temperature_halflife: float = 0.0,
+                        policy_surprise_weight: float = 0.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
@@ -214,7 +222,11 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
     resign_threshold < 0, and `kld_stop_threshold` / `kld_stop_interval` / `kld_stop_min_simulations` (tree backend, KLD-gain
     early stopping of the searches) only when kld_stop_threshold > 0, and `move_visit_offset` / `move_value_cutoff` (tree
     backend, visit-offset / value-cutoff move selection) only when one of the two is above 0, `temperature_halflife` (tree
-    backend, decaying move temperature) only when it is."""
+    backend, decaying move temperature) only when it is, and `policy_surprise_weight` (tree backend, policy surprise
+    weighting of training rows; 0 = off) only when it is > 0."""
+    from .policy_surprise import policy_surprise_on, refuse_backend as surprise_refuse_backend
+    surprise = policy_surprise_on(policy_surprise_weight)
+    surprise_refuse_backend(surprise, search_backend)
     from .move_pick import move_pick_kwargs, move_pick_refusal, refuse_backend as pick_refuse_backend
     pick = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
     pick_refuse_backend(bool(pick), search_backend)
@@ -301,7 +313,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
                 "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
             **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-            **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign, **kld.kwargs(), **pick)
+            **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign, **kld.kwargs(), **pick,
+            **({"policy_surprise_weight": float(policy_surprise_weight)} if surprise else {}))
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

@@ -27,6 +27,8 @@ import torch
 
 from .net import ChessNet
 from .self_play_storage import estimate_bytes_per_sample, plan_sample_ranges, save_self_play_payload, slice_batch_cpu
+from .policy_surprise import derive_counters as derive_surprise_counters
+from .policy_surprise import surprise_meta
 from .resign import derive_counters
 from .self_play_types import SelfPlayV1Stats
 from .trajectory_buffer import TensorSelfPlayBatch
@@ -117,6 +119,7 @@ def merge_self_play_stats(stats_list: List[SelfPlayV1Stats], elapsed_sec: float)
         if s.device and s.device not in devices:
             devices.append(s.device)
     derive_counters(counters)                               # resignation: its two averages do not add up
+    derive_surprise_counters(counters)                      # policy surprise: nor does its mean
     busy_ms = sum(max(0.0, float(s.elapsed_sec)) for s in stats_list) * 1000.0
     return SelfPlayV1Stats(
         num_games=games, num_positions=positions, black_wins=sum(int(s.black_wins) for s in stats_list),
@@ -205,6 +208,8 @@ def write_worker_chunks(run_once, *, worker_idx: int, device: str, games: int, g
              "games_per_chunk": int(games_per_chunk), "num_selfplay_batches": len(stats_chunks),
              "saved_chunks": len(files)}
     wmeta.update(meta_common)
+    if "policy_surprise" in wmeta:      # policy surprise weighting: its weight and what the resampling did in this shard
+        wmeta["policy_surprise"] = surprise_meta(wmeta["policy_surprise"]["weight"], stats.mcts_counters)
     manifest = {
         "payload_format": "v1_worker_chunk_manifest", "version": 1, "num_samples": int(sum(sizes)),
         "num_shards": len(files), "shard_files": list(files), "shard_sizes": list(sizes),
@@ -455,6 +460,8 @@ class StreamedShardFiles:
                  "games_per_chunk": self.games_per_chunk, "num_selfplay_batches": int(num_batches),
                  "saved_chunks": len(self.files)}
         wmeta.update(self.meta_common)
+        if "policy_surprise" in wmeta:  # policy surprise weighting: its weight and what the resampling did in this shard
+            wmeta["policy_surprise"] = surprise_meta(wmeta["policy_surprise"]["weight"], stats.mcts_counters)
         manifest = {
             "payload_format": "v1_worker_chunk_manifest", "version": 1, "num_samples": int(sum(self.sizes)),
             "num_shards": len(self.files), "shard_files": list(self.files), "shard_sizes": list(self.sizes),
@@ -591,7 +598,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
                          resign_streak: str = "side", kld_stop_threshold: float = 0.0, kld_stop_interval: int = 100,
                          kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
-                         move_value_cutoff: float = 0.0, temperature_halflife: float = 0.0) -> Dict[str, Any]:
+                         move_value_cutoff: float = 0.0, temperature_halflife: float = 0.0,
+                         policy_surprise_weight: float = 0.0) -> Dict[str, Any]:
     """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
     `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
     tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on.
@@ -617,7 +625,10 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
     `move_visit_offset` / `move_value_cutoff` (tree backend only; 0 = off): visit-offset / value-cutoff move selection;
     `temperature_halflife` (tree backend only; 0 = off): the move temperature decays with this half-life below
     `temperature_threshold`; see tree_engine.self_play_tree_gpu.  The three values are recorded in the manifests'
-    metadata["move_pick"] when any of them is on."""
+    metadata["move_pick"] when any of them is on.
+    `policy_surprise_weight` (tree backend only; 0 = off, in [0, 1]): policy surprise weighting of training rows, see
+    tree_engine.self_play_tree_gpu.  The weight and what the resampling did (games, rows, rows_replaced, mean_surprise) are
+    recorded in the manifests' metadata["policy_surprise"] when on."""
     from .move_pick import move_pick_kwargs, move_pick_meta, move_pick_refusal, refuse_backend as pick_refuse_backend
     pick = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
     pick_refuse_backend(bool(pick), search_backend)
@@ -636,6 +647,9 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                if _gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale) else 0)
         if why is not None:
             raise ValueError(f"KLD-gain early stopping is not supported with {why}")
+    from .policy_surprise import policy_surprise_on, refuse_backend as refuse_surprise_backend
+    surprise = policy_surprise_on(policy_surprise_weight)
+    refuse_surprise_backend(surprise, search_backend)
     from .resign import refuse_backend, resign_kwargs, resign_meta
     resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
                            resign_streak)
@@ -745,6 +759,7 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                           **({"value_target_lambda": float(value_target_lambda)} if td else {}),
                                           **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign,
                                           **kld.kwargs(), **pick,
+                                          **({"policy_surprise_weight": float(policy_surprise_weight)} if surprise else {}),
                                           **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
@@ -772,7 +787,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        **({"puct_shape": shape.meta()} if shape.on else {}),
                        **({"resign": resign_meta(resign)} if resign else {}),
                        **({"kld_stop": kld.meta()} if kld.on else {}),
-                       **({"move_pick": move_pick_meta(pick)} if pick else {})}
+                       **({"move_pick": move_pick_meta(pick)} if pick else {}),
+                       **({"policy_surprise": {"weight": float(policy_surprise_weight)}} if surprise else {})}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

@@ -36,6 +36,8 @@ from .trajectory_buffer import TensorSelfPlayBatch, TensorTrajectoryBuffer
 from .kld_stop import INTERVAL_DEFAULT as KLD_INTERVAL_DEFAULT, KldStop, kld_stop_refusal, parse_kld_stop
 from .move_pick import (counters_from_block as move_pick_counters, move_pick_kwargs, move_pick_on, move_pick_refusal,
                         temperature_table)
+from .policy_surprise import counters_from_block as surprise_counters_from_block
+from .policy_surprise import policy_surprise_on, policy_surprise_refusal, root_prior
 from .resign import counters_from_block, resign_kwargs
 from .value_target import td_lambda_on
 
@@ -2038,8 +2040,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        resign_playthrough_fraction: float = 0.1, resign_streak: str = "side",
                        kld_stop_threshold: float = 0.0, kld_stop_interval: int = KLD_INTERVAL_DEFAULT,
                        kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
-                       move_value_cutoff: float = 0.0, temperature_halflife: float = 0.0
-                       ) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
+                       move_value_cutoff: float = 0.0, temperature_halflife: float = 0.0,
+                       policy_surprise_weight: float = 0.0) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
     `model` may also be a `PriorEvaluator` (states -> priors over the 220 actions + values, the reference's own
@@ -2104,8 +2106,23 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     + (temperature_init - temperature_final) * 0.5^(p / h) instead of temperature_init, from a float32 table built once
     on the host (move_pick.temperature_table).  Where the policy target follows the move temperature
     (`policy_target_temperature` None) it follows the half-life too, exactly as it follows the step.  Off, nothing is
+    allocated or launched and every output is byte-identical.
+    `policy_surprise_weight` alpha (0 = off; in [0, 1]; KataGo uses 0.5): policy surprise weighting of training rows
+    (policy_surprise.py).  A share alpha of a finished game's total row weight is handed out in
+    proportion to KL(the row's policy target || the network's noise-free root prior), and systematic resampling with one
+    seeded uniform per game turns the weights into copy counts inside the game's own row slots: game paths, RNG streams
+    and the rows per game stay as they are, only which of a game's rows fill its slots changes.  The root prior costs one
+    extra network launch of the wave per ply.  With the playout cap only recorded rows take part.  mcts_counters gain
+    surprise_games / surprise_rows / surprise_rows_replaced / surprise_mean (micro-nats per row; and the sum it derives
+    from).  Needs `device_tail`, not with a `PriorEvaluator` (ValueError); composes with everything else.  Off, nothing is
     allocated or launched and every output is byte-identical."""
     dev = torch.device(device)
+    surprise = policy_surprise_on(policy_surprise_weight)
+    if surprise:
+        why = policy_surprise_refusal(device_tail=bool(device_tail), prior_evaluator=isinstance(model, PriorEvaluator),
+                                      batch_k=batch_k)
+        if why is not None:
+            raise ValueError(f"policy surprise weighting is not supported with {why}")
     pick_kw = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
     repick = "move_visit_offset" in pick_kw
     halflife = float(pick_kw.get("temperature_halflife", 0.0))
@@ -2237,7 +2254,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         from .wave_tail import WaveTail
         tail = WaveTail(buffer, wave, int(max_game_plies), dev, soft_value_k=float(soft_value_k), row_log=row_log,
                         **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-                        **(dict(resign, seed=int(seed)) if resign else {}))
+                        **(resign or {}), **({"seed": int(seed)} if (resign or surprise) else {}),
+                        **({"policy_surprise_weight": float(policy_surprise_weight),
+                            "prior_fn": lambda search: root_prior(net, search, use_fused)} if surprise else {}))
         tail.collect_timing = bool(collect_timing)
         outcome, delta_hist = tail.outcome, tail.delta_hist
         if cap:
@@ -2269,7 +2288,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
             lists_below = wave - (samples_per_launch_pass(net) if use_fused else 0)
             if cap:
                 tail.game_plies = game_plies if continuous else game_plies[base:base + g]
-            if resign:
+            if resign or surprise:
                 tail.game_base = 0 if continuous else base
             tail.run(lambda st, temps, dn, reseated: mcts.search_batch(
                          st, temperatures=temps, active=~dn, reset=reseated,
@@ -2401,6 +2420,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        # move re-pick: games it applied to, children cut by offset / value, picks it changed
                        **(move_pick_counters(mcts.move_pick_counts.tolist()) if repick else {}),
                        # resignation: games that resigned, the play-through games and their false positives
-                       **(counters_from_block(tail.resign_counters.tolist()) if resign else {})},
+                       **(counters_from_block(tail.resign_counters.tolist()) if resign else {}),
+                       # policy surprise weighting: games resampled, their rows, rows replaced by a copy, mean surprise
+                       **(surprise_counters_from_block(tail.surprise_counters.tolist(), float(tail.surprise_sum.item()))
+                          if surprise else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))
     return batch, stats

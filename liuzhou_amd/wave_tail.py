@@ -1,7 +1,8 @@
 """Device-side tail of one ply of the v1 wave loop for a fixed wave of slots: trajectory rows, the move and the
 finalisation of finished games without a host round trip (`lz_wave_record`, `lz_wave_step_finish`), and optionally the
 TD(lambda) value targets from the searches' root values (`lz_wave_note_value`, `lz_wave_td_targets`; value_target.py)
-and resignation with play-through calibration (`lz_wave_resign`, `lz_wave_resign_book`; resign.py).
+and resignation with play-through calibration (`lz_wave_resign`, `lz_wave_resign_book`; resign.py) and policy surprise
+weighting of a finished game's rows (`lz_wave_note_surprise`, `lz_wave_surprise_resample`; policy_surprise.py).
 
 It replaces, for whole waves, the sequence `append_steps` -> `step_index[...] = rows` -> `self_play_step_inplace` ->
 `finalize_games_inplace` of v1/python/self_play_gpu_runner.py:205-247, whose `nonzero`-shaped outputs force one host
@@ -17,6 +18,7 @@ import torch
 from . import _lib as L
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput
 from .trajectory_buffer import TensorTrajectoryBuffer
+from .policy_surprise import policy_surprise_on, policy_surprise_refusal
 from .resign import COUNTER_KEYS, resign_kwargs
 from .value_target import td_lambda_on
 
@@ -27,7 +29,8 @@ class WaveTail:
     def __init__(self, buffer: TensorTrajectoryBuffer, num_slots: int, max_game_plies: int, device,
                  soft_value_k: float = 2.0, reseat: bool = False, row_log=None, value_target_lambda: float = 1.0,
                  resign_threshold: float = 0.0, resign_min_moves: int = 10, resign_consecutive: int = 3,
-                 resign_playthrough_fraction: float = 0.1, resign_streak: str = "side", seed: int = 0) -> None:
+                 resign_playthrough_fraction: float = 0.1, resign_streak: str = "side", seed: int = 0,
+                 policy_surprise_weight: float = 0.0, prior_fn=None) -> None:
         # TD(lambda) value targets (value_target.py; 1 = off: every row gets the game's result, nothing below exists)
         self.td_lambda = float(value_target_lambda) if td_lambda_on(value_target_lambda) else None
         if self.td_lambda is not None and reseat:
@@ -39,6 +42,12 @@ class WaveTail:
         if self.resign is not None and reseat:
             raise ValueError("WaveTail: resignation is not supported with the in-kernel re-seat (reseat=True): `done` is "
                              "never set there, so the games that end are never booked")
+        # policy surprise weighting (policy_surprise.py; 0 = off: nothing below exists, every game keeps its own rows)
+        self.surprise_alpha = float(policy_surprise_weight) if policy_surprise_on(policy_surprise_weight) else None
+        if self.surprise_alpha is not None:
+            why = policy_surprise_refusal(reseat=reseat)
+            if why is not None:
+                raise ValueError(f"WaveTail: policy surprise weighting is not supported with {why}")
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("WaveTail needs a HIP device (no CPU path)")
@@ -85,6 +94,20 @@ class WaveTail:
             self.terminal_out = z(self.G, torch.uint8)
             self.resigned = z(self.G, torch.uint8)
             self.resign_counters = z(len(COUNTER_KEYS), torch.int64)
+            if self.was_live is None:
+                self.was_live = z(self.G, torch.uint8)
+        # policy surprise weighting: the surprise of every recorded step, the source row of every row slot of the game
+        # that was resampled last (scratch, readable), the int64[3] counter block and the double sum of the surprises
+        # (8 B per slot and step + 32 B); `prior_fn(search)` -> the noise-free root priors float32[G, action_dim] of the
+        # searched positions (policy_surprise.root_prior; run() calls it once per ply)
+        self.surprise_hist = self.surprise_src = self.surprise_counters = self.surprise_sum = None
+        self.prior_fn = None
+        if self.surprise_alpha is not None:
+            self.prior_fn = prior_fn                     # run() refuses to start without one
+            self.surprise_hist = torch.zeros((self.G, self.max_plies), dtype=torch.float32, device=dev)
+            self.surprise_src = torch.zeros((self.G, self.max_plies), dtype=torch.int32, device=dev)
+            self.surprise_counters = z(3, torch.int64)
+            self.surprise_sum = z(1, torch.float64)
             if self.was_live is None:
                 self.was_live = z(self.G, torch.uint8)
         if row_log is not None:
@@ -222,6 +245,38 @@ class WaveTail:
                 C.c_float(self.resign["resign_playthrough_fraction"]), L.ptr(self.resign_counters),
                 L.stream_ptr(self.device)), "wave_resign_book")
 
+    def note_surprise(self, done: torch.Tensor, step_counts: torch.Tensor, search: RootSearchBatchOutput,
+                      prior: torch.Tensor) -> None:
+        """Policy surprise: keep KL(policy target || prior) of the row every live slot recorded this ply (after `record` /
+        `note_value`, before `resign_step` / `step_finish`).  `prior` float32[num_slots, action_dim]."""
+        lm, pol = search.legal_mask.contiguous(), search.policy_dense.contiguous()
+        T = int(pol.shape[1])
+        if pol.dtype != torch.float32 or lm.element_size() != 1 or tuple(lm.shape) != (self.G, T):
+            raise RuntimeError("WaveTail.note_surprise: policy_dense must be float32 and legal_mask one byte per action")
+        if prior.dtype != torch.float32 or tuple(prior.shape) != (self.G, T) or not prior.is_contiguous():
+            raise RuntimeError("WaveTail.note_surprise: prior must be contiguous float32[num_slots, action_dim]")
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_wave_note_surprise(
+                L.ptr(done), L.i64(self.G), L.ptr(self.rows), L.ptr(step_counts), L.ptr(lm), L.ptr(pol), L.ptr(prior),
+                L.i64(T), L.ptr(self.surprise_hist), L.ptr(self.was_live), L.i64(self.max_plies), L.ptr(self.overflow),
+                L.stream_ptr(self.device)), "wave_note_surprise")
+
+    def surprise_resample(self, done: torch.Tensor, step_index: torch.Tensor, step_counts: torch.Tensor,
+                          slot_game: Optional[torch.Tensor] = None) -> None:
+        """Policy surprise: resample, in place, the rows of the games that ended this ply (after `step_finish`,
+        `resign_book` and `td_targets`, before their rows leave for a finished-row log)."""
+        if step_index is not None and int(step_index.shape[1]) != self.max_plies:
+            raise RuntimeError("WaveTail.surprise_resample: the step_index matrix must have max_game_plies columns")
+        a_state, a_legal, a_policy, a_value, a_soft, a_sign = self.buffer.arena()
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_wave_surprise_resample(
+                L.ptr(done), L.ptr(self.was_live), L.i64(self.G), C.c_double(self.surprise_alpha),
+                L.ptr(self.surprise_hist), L.ptr(slot_game), L.i64(self.game_base), C.c_uint64(self.seed),
+                L.ptr(a_state), L.ptr(a_legal), L.ptr(a_policy), L.ptr(a_value), L.ptr(a_soft), L.ptr(a_sign),
+                L.i64(int(a_policy.shape[1])), L.ptr(step_index), L.ptr(step_counts), L.i64(self.max_plies),
+                L.ptr(self.surprise_src), L.ptr(self.surprise_counters), L.ptr(self.surprise_sum),
+                L.stream_ptr(self.device)), "wave_surprise_resample")
+
     def start_next_games(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, step_counts: torch.Tensor,
                          budget: torch.Tensor, next_game: torch.Tensor, slot_game: torch.Tensor,
                          reseated: Optional[torch.Tensor] = None) -> None:
@@ -248,12 +303,20 @@ class WaveTail:
         -> td_targets -> the log: the rows of a game that ends carry their final targets before they leave.
         With resignation (`resign_threshold` < 0) it is record -> note_value -> resign -> step_finish -> resign_book ->
         td_targets -> the log.
+        With policy surprise weighting (`policy_surprise_weight` > 0) the full order is record -> note_value ->
+        note_surprise -> resign -> step_finish -> resign_book -> td_targets -> surprise_resample -> the log: a game's rows
+        carry their final targets before they are resampled, and are resampled before they leave.  `prior_fn(search)` is
+        called once per ply, right after the search (one extra network launch).
         `temperature_table` (float32 on the device, move_pick.temperature_table: the half-life schedule): the temperature of
         a slot is table[min(ply, len - 1)] instead of the t_init / t_final step at `t_threshold`."""
         dev, g = self.device, self.G
         log = self.row_log
         if (log is None) == (step_index is None):
             raise ValueError("WaveTail.run: pass a step_index matrix, or build the tail with a finished-row log")
+        if self.surprise_alpha is not None and not callable(self.prior_fn):
+            raise RuntimeError("WaveTail.run: policy surprise weighting is on but the tail has no `prior_fn` (search -> the "
+                               "noise-free root priors float32[num_slots, action_dim]); pass WaveTail(prior_fn=...), e.g. "
+                               "a closure over policy_surprise.root_prior")
         flags = [torch.zeros((1,), dtype=torch.bool).pin_memory() for _ in range(2)]
         live = [torch.full((1,), g, dtype=torch.int64).pin_memory() for _ in range(2)]     # live slots, as of two plies ago
         self.live_estimate = g
@@ -288,6 +351,8 @@ class WaveTail:
                 self.record(states, done, step_index, step_counts, search)
                 if self.td_lambda is not None:
                     self.note_value(states, plies, done, step_counts, search)
+                if self.surprise_alpha is not None:
+                    self.note_surprise(done, step_counts, search, self.prior_fn(search))
             with self._bracket("self_play_step_ms"):
                 if self.resign is not None:
                     self.resign_step(states, plies, done, search, slot_game=slot_game)
@@ -297,6 +362,9 @@ class WaveTail:
             if self.td_lambda is not None:
                 with self._bracket("finalize_ms"):
                     self.td_targets(done, step_index, step_counts)
+            if self.surprise_alpha is not None:
+                with self._bracket("finalize_ms"):
+                    self.surprise_resample(done, step_index, step_counts, slot_game=slot_game)
             # all finished and nothing left to start (a finished slot restarts at the top of the next ply otherwise)
             if log is not None:
                 if ply == 0:

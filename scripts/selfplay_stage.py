@@ -98,6 +98,9 @@ def parse(argv=None):
     ap.add_argument("--temperature_halflife", type=float, default=0.0,
                     help="move temperature (tree backend): below --temperature_threshold the excess over "
                          "--temperature_final halves every this many plies; 0 = off (the step)")
+    ap.add_argument("--policy_surprise_weight", type=float, default=0.0,
+                    help="policy surprise weighting (tree backend): share of a game's total row weight handed out in "
+                         "proportion to KL(policy target || network prior); in [0, 1], 0 = off (KataGo uses 0.5)")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -172,7 +175,8 @@ def main(argv=None) -> int:
             "kld_stop_min_simulations": args.kld_stop_min_simulations} if args.kld_stop_threshold != 0.0 else {}),
         **({"move_visit_offset": args.move_visit_offset, "move_value_cutoff": args.move_value_cutoff}
            if (args.move_visit_offset != 0.0 or args.move_value_cutoff != 0.0) else {}),
-        **({"temperature_halflife": args.temperature_halflife} if args.temperature_halflife != 0.0 else {}))
+        **({"temperature_halflife": args.temperature_halflife} if args.temperature_halflife != 0.0 else {}),
+        **({"policy_surprise_weight": args.policy_surprise_weight} if args.policy_surprise_weight != 0.0 else {}))
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)
