@@ -1009,9 +1009,14 @@ LZ_API int lz_policy_value_loss_fwd_bwd(const float* log_p1, const float* log_p2
 
 /* A row of the 5-tensor trajectory contract (v1/python/trajectory_buffer.py:11-33; 2 692 B) as an exact 360-byte
  * record: u64[4] {own | phase<<36, opp, own-marked, opp-marked}, u32[7] legal bits, f32[72] policy of the legal
- * actions in ascending index order, f32 value, f32 soft value, 4 B pad.  unpack(pack(x)) reproduces every byte.
+ * actions in ascending index order (unused slots zero), f32 value, f32 soft value, 4 zero bytes.  unpack(pack(x))
+ * reproduces every byte, with one exception: -0.0 in a plane or in the policy off the legal set compares equal to
+ * zero, is packed as zero without a count and comes back as +0.0 (on a legal entry it is carried bit for bit, like
+ * NaN payloads, infinities and subnormals; a non-zero legal byte comes back as 1).
  * `not_representable` (device int32, add-only) counts rows whose planes are not 0/1, whose policy is non-zero off the
- * legal set, or that have more than 72 legal actions -- never the case for self-play output. */
+ * legal set, or that have more than 72 legal actions -- never the case for self-play output; the record of such a row
+ * is unspecified.  unpack is total: the phase is (w0 >> 36) & 7, bits the layout does not own are ignored, and a legal
+ * bit past the 72nd gets policy 0 (nothing outside the record is read). */
 #define LZ_TRAJECTORY_RECORD_BYTES 360
 LZ_API int lz_pack_trajectory_rows(const float* state_tensors, const uint8_t* legal_masks,
                                    const float* policy_targets, const float* value_targets,

@@ -193,7 +193,9 @@ extern "C" int lz_policy_value_loss_fwd_bwd(const float* log_p1, const float* lo
 // ---- compact trajectory records (wire format of the per-iteration gather) ----------------
 // A trajectory row of the reference contract is 2 692 B (f32[11,6,6] planes + bool[220] + f32[220] + 2 f32); its
 // information content is far smaller: the planes are 0/1 (4 bitboards + a phase), the policy is non-zero only on the
-// <= 72 legal entries.  Record = 360 B, exact (pack -> unpack reproduces every byte of the five tensors):
+// <= 72 legal entries.  Record = 360 B, exact (pack -> unpack reproduces every byte of the five tensors, but for one
+// exception: a -0.0 in a plane or in the policy off the legal set equals zero, is packed as zero, raises no count and
+// comes back as +0.0; on a legal entry -0.0 is carried like every other bit pattern):
 //   u64 w[4]   own | phase << 36, opp, own-marked, opp-marked        (planes 0..3 as bits, planes 4..10 one-hot)
 //   u32 m[7]   legal mask bits 0..219
 //   f32 p[72]  policy of the legal actions in ascending index order
@@ -283,7 +285,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void unpack_rows_kernel(
         const int slot = base + __popcll(bal & ((1ull << lane) - 1ull));
         if (a < kTotal) {
             legal[s * kTotal + a] = lg ? 1 : 0;
-            policy[s * kTotal + a] = lg ? pv[slot] : 0.f;
+            policy[s * kTotal + a] = (lg && slot < 72) ? pv[slot] : 0.f;   // a record with > 72 bits stays inside itself
         }
         base += __popcll(bal);
     }

@@ -1,6 +1,11 @@
 """Exact 360-byte records for trajectory rows (7.5x smaller than the 2 692-byte 5-tensor row): the wire format of
 `distributed.gather_trajectories` between GPUs.  HIP only; the on-disk shards keep the
-reference's tensor payload."""
+reference's tensor payload.
+
+Exact but for one exception: a -0.0 in a plane, or in the policy off the legal set, equals zero, is packed as zero
+without being counted and comes back as +0.0 (refusing such rows could make a production gather raise).  On legal
+entries every bit pattern survives (-0.0, NaN payloads, infinities, subnormals).  Unpacking is total: a record whose
+mask holds more than 72 bits gets policy 0 past the 72nd legal action."""
 from __future__ import annotations
 
 import torch

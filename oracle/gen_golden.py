@@ -18,6 +18,7 @@ Fixture groups:
   g7_ops.npz        pack / finalize / self-play-step / trajectory-finalize op vectors
   g8_selfplay.npz   4-game root-PUCT self-play trace of the reference v1 runner (CPU)
   g11_loss.npz      training-loss values and head gradients from the reference's own loss functions
+  g21_loss_edges.npz  the same functions on the edge batch of tests/train_loss_cases.py, three settings
   g10_tree_selfplay.npz  full-tree self-play traces of the reference portable runner (subtree reuse on every move)
   g9_net.npz        network outputs for seeded weights (tiny / 6x64 / 10x128)
   g14_eval_arena.npz  the reference's evaluation arena (two tiny checkpoints, deterministic): outcome, moves, evaluations
@@ -846,6 +847,58 @@ def gen_loss():
 
 
 # --------------------------------------------------------------------------------------------
+# G21: training loss at its numeric edges (the calls of gen_loss on the edge batch of tests/train_loss_cases.py)
+# --------------------------------------------------------------------------------------------
+def gen_loss_edges():
+    import importlib.util
+    from src.policy_batch import build_combined_logits, masked_log_softmax, batched_policy_loss
+    from src.neural_network import scalar_to_bucket_twohot, scalar_to_wdl
+    from v1.python.train_bridge import _bucket_logits_to_wdl_probs
+    # by path: the reference has a `tests` package of its own in front of ours on sys.path
+    spec = importlib.util.spec_from_file_location("train_loss_cases", os.path.join(REPO, "tests", "train_loss_cases.py"))
+    cases = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cases)
+    c = cases.edge_batch(cases.EDGE_B)
+    B = cases.EDGE_B
+    t = lambda k: torch.from_numpy(c[k].copy())
+    mask, target, value, soft = t("mask").bool(), t("target"), t("value"), t("soft")
+    out = {k: c[k] for k in cases.INPUT_KEYS}
+    out["mask"] = np.packbits(c["mask"] != 0, axis=1)
+    for tag, (alpha, anti, dw) in zip(cases.SETTING_TAGS, cases.SETTINGS):
+        l1, l2, l3, vl = (t(k).requires_grad_(True) for k in ("lp1", "lp2", "lpm", "vlogits"))
+        raw_v = value.view(-1, 1); bv = raw_v
+        draw = raw_v.abs().lt(1e-8)
+        if abs(anti) > 1e-9:
+            bv = bv.clone(); bv[draw] = anti
+        mixed = torch.clamp((1.0 - alpha) * bv + alpha * soft.view(-1, 1), -1.0, 1.0)
+        tgt = scalar_to_bucket_twohot(mixed, num_bins=101).float()
+        vlp = torch.log_softmax(vl.float(), dim=-1)
+        ce_v = -(tgt * vlp).sum(-1)
+        bucket = ce_v.mean()
+        wdl_aux = -(scalar_to_wdl(raw_v).float() * torch.log(_bucket_logits_to_wdl_probs(vl).clamp_min(1e-8))).sum(-1)
+        comb = build_combined_logits(l1, l2, l3, board_size=6)
+        logp = masked_log_softmax(comb, mask, dim=1)
+        pol = batched_policy_loss(logp, target, mask, raw_v, dw)
+        # per-sample KL through the same function: one row with weight 1 (1 + 1e-8 is 1 in float32)
+        ones = torch.ones((1, 1))
+        kl = torch.stack([batched_policy_loss(logp[i:i + 1].detach(), target[i:i + 1], mask[i:i + 1], ones, 1.0)
+                          for i in range(B)])
+        weight = torch.where(draw.view(-1), torch.tensor(float(dw)), torch.tensor(1.0))
+        (pol + bucket).backward()
+        grads = dict(g1=l1.grad, g2=l2.grad, g3=l3.grad, gv=vl.grad)
+        for k, gr in grads.items():                         # a row the reference cannot differentiate would be named, not dropped
+            rows = np.flatnonzero(~torch.isfinite(gr).all(dim=1).numpy())
+            assert rows.size == 0, f"[g21/{tag}] non-finite reference gradient {k} on rows {rows.tolist()}"
+        assert torch.isfinite(kl).all() and torch.isfinite(ce_v).all() and torch.isfinite(wdl_aux).all()
+        out.update({f"{tag}_params": np.array([alpha, anti, dw], np.float32), f"{tag}_kl": kl.numpy(),
+                    f"{tag}_weight": weight.numpy(), f"{tag}_ce_value": ce_v.detach().numpy(),
+                    f"{tag}_wdl_aux": wdl_aux.detach().numpy(), f"{tag}_policy_loss": pol.detach().numpy(),
+                    f"{tag}_bucket_loss": bucket.detach().numpy(), **{f"{tag}_{k}": gr.numpy() for k, gr in grads.items()}})
+        print(f"[g21/{tag}] policy={pol.item():.6f} bucket={bucket.item():.6f} weight_sum={float(weight.sum()):.2f}")
+    np.savez_compressed(os.path.join(OUT, "g21_loss_edges.npz"), **out)
+
+
+# --------------------------------------------------------------------------------------------
 # G9: network
 # --------------------------------------------------------------------------------------------
 def gen_net(chosen):
@@ -910,6 +963,8 @@ def main():
         gen_sparse_selfplay()
     if not which or "g11" in which:
         gen_loss()
+    if not which or "g21" in which:
+        gen_loss_edges()
     for f in sorted(os.listdir(OUT)):
         print(f"  {f}: {os.path.getsize(os.path.join(OUT, f)) / 1024:.1f} KiB")
 
