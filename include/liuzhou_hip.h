@@ -170,7 +170,16 @@ LZ_API int lz_root_puct_allocate_visits_ws(const float* priors, const float* lea
  * step (mcts_gpu.py:1410-1424).  `uniforms` float32[R] in [0,1) selects sampled picks from the
  * log-space stable policy (mcts_gpu.py:853-898) by inverse CDF; NULL = argmax (sample_moves=False).
  * Outputs are fully written: policy_dense float32[B,T] (0 fill), chosen_index int64[B] (-1),
- * chosen_codes int32[B,4] (-1), chosen_valid uint8[B] (0), root_value float32[R].  M <= 256. */
+ * chosen_codes int32[B,4] (-1), chosen_valid uint8[B] (0), root_value float32[R].  M <= 256.
+ * root_value[r] = sum(value_sum[r]) / max(sum(visits[r]), 1) for EVERY row; a row without a valid action (a terminal
+ * root of a padded layout) keeps the fill in the other four outputs.
+ * Overflow: policy = pow(max(visits, 1e-8), 1 / max(T, 1e-6)) over the valid slots, normalised (sum clamped at 1e-8), all
+ * in float32 like the reference.  Once a power exceeds FLT_MAX -- at T = 0.1 from about 7132 visits on one action, at the
+ * 1e-6 clamp (temperature 0) from 2 visits -- the reference's row is inf / inf = NaN on the overflowed slots and 0 on the
+ * others; policy_dense keeps those NaNs (parity), and the argmax pick follows torch's max: a NaN is the maximum, the
+ * first one wins, so the pick is the first overflowed action.  The sampled pick works in log space and does not overflow.
+ * Preconditions: valid_root_indices in [0, B), visits finite and 0 on slots that are not valid (the reference multiplies
+ * an overflowed inf by the mask's 0 there); columns of legal_index_mat outside [0, T) are not scattered. */
 LZ_API int lz_root_finalize_from_visits(const int64_t* legal_index_mat, const int32_t* action_code_mat,
                                         const uint8_t* valid_mask, const float* visits,
                                         const float* value_sum, const int64_t* valid_root_indices,

@@ -333,22 +333,30 @@ int lz_root_finalize_from_visits(const int64_t* lidx, const int32_t* codes, cons
         const int64_t b = roots[r];
         const float temp = temps[r] > 1e-6f ? temps[r] : 1e-6f;
         const float inv_t = 1.0f / temp;
-        float psum = 0.f, sv = 0.f, sw = 0.f;
+        float sv = 0.f, sw = 0.f;
+        double psum_wide = 0.0;               // one rounding, like a tree sum: 256 sequential float32 additions drop the 1e-8 terms
         bool any = false;
         for (int64_t a = 0; a < M; ++a) {
             const bool ok = valid[r * M + a] != 0;
             const float v = visits[r * M + a];
             pol[a] = ok ? std::pow(v > 1e-8f ? v : 1e-8f, inv_t) : 0.f;
-            psum += pol[a]; sv += v; sw += value_sum[r * M + a];
+            psum_wide += pol[a]; sv += v; sw += value_sum[r * M + a];
             any = any || ok;
         }
+        float psum = (float)psum_wide;
+        root_value[r] = sw / (sv > 1.0f ? sv : 1.0f);                  // module.cpp:497: every row
         if (!any) continue;
         psum = psum > 1e-8f ? psum : 1e-8f;
+        // argmax as torch's max (module.cpp:494): a NaN (inf / inf once visits^(1/T) overflows) is the maximum, the
+        // first one wins
         int64_t pick = 0;
         float best = -INFINITY;
+        bool nan_pick = false;
         for (int64_t a = 0; a < M; ++a) {
             pol[a] = pol[a] / psum;
-            if (pol[a] == pol[a] && pol[a] > best) { best = pol[a]; pick = a; }
+            if (nan_pick) continue;
+            if (pol[a] != pol[a]) { nan_pick = true; pick = a; }
+            else if (pol[a] > best) { best = pol[a]; pick = a; }
         }
         if (uniforms != nullptr && M > 1) {
             float mx = -INFINITY;
@@ -391,7 +399,6 @@ int lz_root_finalize_from_visits(const int64_t* lidx, const int32_t* codes, cons
         cidx[b] = lidx[r * M + pick];
         std::memcpy(ccodes + b * 4, codes + (r * M + pick) * 4, 16);
         cvalid[b] = 1;
-        root_value[r] = sw / (sv > 1.0f ? sv : 1.0f);
     }
     return LZ_OK;
 }

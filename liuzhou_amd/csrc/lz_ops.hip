@@ -983,25 +983,28 @@ __global__ __launch_bounds__(kBlock) void root_finalize_kernel(
         sv += v;
         sw += w;
     }
+    psum = fmaxf(wave_sum(psum), 1e-8f);
+    sv = wave_sum(sv);
+    sw = wave_sum(sw);
+    // module.cpp:497: the root value of every row, also of one without a valid action
+    if (lane == 0) root_value[r] = sw / fmaxf(sv, 1.0f);
     {   // a row without any valid action (a terminal root in the padded layout of the fused search) keeps the fill
-        // kernel's defaults: zero policy, index -1, not valid
+        // kernel's defaults in the other outputs: zero policy, index -1, not valid
         bool any = false;
 #pragma unroll
         for (int j = 0; j < SLOTS; ++j) any = any || ok[j];
         if (__ballot(any) == 0ull) return;
     }
-    psum = fmaxf(wave_sum(psum), 1e-8f);
-    sv = wave_sum(sv);
-    sw = wave_sum(sw);
-    // argmax of the normalised policy, first index wins (module.cpp:501)
+    // argmax of the normalised policy, first index wins (module.cpp:494,501).  Once visits^(1/T) overflows float32 the
+    // overflowed entries are inf / inf = NaN and the rest 0; like torch's max, a NaN is the maximum and the first one wins.
     unsigned long long key = 0ull;
 #pragma unroll
     for (int j = 0; j < SLOTS; ++j) {
         pol[j] = pol[j] / psum;
         const int a = j * kWave + lane;
-        if (a < M && pol[j] == pol[j]) {
-            const unsigned long long k = ((unsigned long long)float_order(pol[j]) << 32) |
-                                         (unsigned long long)(0xFFFFFFFFu - (uint32_t)a);
+        if (a < M) {
+            const uint32_t ord = pol[j] == pol[j] ? float_order(pol[j]) : 0xFFFFFFFFu;
+            const unsigned long long k = ((unsigned long long)ord << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)a);
             key = k > key ? k : key;
         }
     }
@@ -1075,7 +1078,6 @@ __global__ __launch_bounds__(kBlock) void root_finalize_kernel(
         cidx[b] = lidx[r * M + pick_local];
         ccodes[b] = codes[r * M + pick_local];
         cvalid[b] = 1;
-        root_value[r] = sw / fmaxf(sv, 1.0f);
     }
 }
 
