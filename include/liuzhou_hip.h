@@ -1063,6 +1063,34 @@ LZ_API int lz_symmetry_transform_states(const LzStateSoA* in, const void* sym, i
 LZ_API int lz_symmetry_transform_packed(const int64_t* in /*[B,4]*/, const void* sym, int32_t sym_width,
                                         int64_t* out /*[B,4]*/, int64_t batch, void* stream);
 
+/* ---- duplicate positions among training rows (csrc/lz_dedup.h) ---------------------------------
+ * A row whose planes 0..3 hold only +-0.0 / 1.0 and whose planes 4..10 are each constant at +-0.0 / 1.0 with at most one
+ * set is representable: four 36-bit boards and a phase 0..7.  Both builds export both entry points; neither allocates
+ * or synchronises. */
+
+/* Keys: keys[i] = {own' | phase<<36, opp', own_marked', opp_marked', legal bits of the image (4 words: bit b & 63 of
+ * word 4 + (b >> 6))} of row i's image under sym[i] = k*: 0 when `symmetric` is 0, else the lowest element whose image
+ * of the four boards is the smallest (compared word by word as unsigned numbers).  A row that is not representable
+ * gets {INT64_MIN | i, 0, ..., 0}, sym 0, and adds one to *not_representable (the caller zeroes it).  planes
+ * float32[n,11,36], masks uint8[n,220].  One wave per row. */
+LZ_API int lz_dedup_position_keys(const float* planes, const uint8_t* masks, int64_t n, int32_t symmetric,
+                                  int64_t* keys /*[n,8]*/, int8_t* sym /*[n]*/,
+                                  int32_t* not_representable /*add-only*/, void* stream);
+
+/* Merge: output row g is group g = rows order[group_begin[g] .. group_begin[g+1]) in the frame of its first member f:
+ * planes and mask bit copies of row f; policy[b] = (float)(S[b] / c_p) with S[P_e(a)] += (double)policy[m][a],
+ * e = sym[f]^-1 o sym[m], c_p the members whose policy has a non-zero entry (0 -> all zero); value and soft the mean
+ * over all c members; out_count[g] = c.  Sums: members in order in chunks of 256, a chunk summed sequentially from 0.0,
+ * the chunk sums added in order from 0.0, in double.  A group of one is a bit copy of its row.  An empty group, a
+ * range outside [0, n], an `order` entry outside [0, n) or a sym outside 0..7 gives an all-zero row with count 0.
+ * planes / out_planes 16-byte aligned.  One wave per group. */
+LZ_API int lz_dedup_merge_groups(const float* planes, const uint8_t* masks, const float* policy,
+                                 const float* value, const float* soft, int64_t n, const int8_t* sym,
+                                 const int64_t* order /*[n] rows by group, ascending inside a group*/,
+                                 const int64_t* group_begin /*[groups+1]*/, int64_t groups,
+                                 float* out_planes, uint8_t* out_masks, float* out_policy,
+                                 float* out_value, float* out_soft, int32_t* out_count, void* stream);
+
 /* The packed forward on the slots of a batch that are LIVE: slot g of packed_states[num_slots] is evaluated iff
  * leaf_kind[g] == 1 (device int32[num_slots]; the tree search's "leaf to expand"), and its outputs go to row g of the
  * output arrays, bit-identical to lz_net_forward_packed_f16 of that slot; rows of other slots are not written.

@@ -8,8 +8,9 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libliuzhou_hip.so")
-SOURCES = ("lz_ops.hip", "lz_engine.hip", "lz_net.hip", "lz_net_f32.hip", "lz_train.hip", "lz_search.hip", "lz_symmetry.hip")
-HEADERS = ("lz_rules.h", "lz_soa.h", "lz_symmetry.h", "lz_wave.h", "lz_rng.h", "lz_net_dev.h", "lz_live_index.h", "lz_surprise.h", "lz_tree_dev.h", os.path.join("..", "..", "include", "liuzhou_hip.h"))
+SOURCES = ("lz_ops.hip", "lz_engine.hip", "lz_net.hip", "lz_net_f32.hip", "lz_train.hip", "lz_search.hip", "lz_symmetry.hip",
+           "lz_dedup.hip")
+HEADERS = ("lz_rules.h", "lz_soa.h", "lz_symmetry.h", "lz_wave.h", "lz_rng.h", "lz_net_dev.h", "lz_live_index.h", "lz_surprise.h", "lz_tree_dev.h", "lz_dedup.h", os.path.join("..", "..", "include", "liuzhou_hip.h"))
 
 
 def hipcc_path() -> str:
@@ -22,7 +23,8 @@ def hipcc_path() -> str:
 HOST_LIB = os.path.join(PKG, "libliuzhou_host.so")
 HOST_SOURCE = os.path.join(CSRC, "lz_host.cpp")
 HOST_SOURCES = (HOST_SOURCE, os.path.join(CSRC, "lz_scalar.cpp"),      # the operator subset + the scalar rule surface
-                os.path.join(CSRC, "lz_symmetry_host.cpp"))             # + the board symmetries
+                os.path.join(CSRC, "lz_symmetry_host.cpp"),             # + the board symmetries
+                os.path.join(CSRC, "lz_dedup_host.cpp"))                # + the position dedup
 
 
 def build_host(force: bool = False, verbose: bool = False) -> str:

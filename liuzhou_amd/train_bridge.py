@@ -235,7 +235,15 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                                parallel_devices: Optional[List[str]] = None, parallel_strategy: str = "none",
                                ddp_pre_sharded: bool = False, optimizer_state_path: Optional[str] = None,
                                symmetry_augment: bool = False, symmetry_seed: int = 0,
-                               symmetry_set: Sequence[int] = tuple(range(8))) -> Tuple[Any, Dict[str, Any]]:
+                               symmetry_set: Sequence[int] = tuple(range(8)), dedup_positions: str = "off",
+                               dedup_max_copies: int = 1) -> Tuple[Any, Dict[str, Any]]:
+    dedup = None
+    if not (isinstance(dedup_positions, str) and dedup_positions == "off" and type(dedup_max_copies) is int
+            and dedup_max_copies == 1):                # the defaults reach nothing below, not even the module
+        from . import position_dedup as dedup_mod
+        dedup_mod.dedup_refusal(dedup_positions, dedup_max_copies, policy_draw_weight=policy_draw_weight,
+                                anti_draw_penalty=anti_draw_penalty)
+        dedup = dedup_mod if dedup_mod.dedup_on(dedup_positions, dedup_max_copies) else None
     if samples.num_samples <= 0:
         return model, {"epoch_stats": [], "num_samples": 0}
     strategy, dev, rank, world = _resolve_strategy(parallel_strategy, device)
@@ -266,6 +274,13 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
         if strategy == "ddp":
             raise RuntimeError("DDP received no local samples on one rank. Increase self-play samples or reduce world size.")
         return model, {"epoch_stats": [], "num_samples": 0}
+    n_filtered = n
+    dedup_stats = None
+    if dedup is not None:                             # duplicate positions merged once, each rank its own share
+        (states, masks, policy, values, soft), info = dedup.merge_duplicate_positions(
+            states, masks, policy, values, soft, mode=dedup_positions, max_copies=int(dedup_max_copies))
+        dedup_stats = dedup.stats_of(info)
+        n = int(states.shape[0])
 
     optimizer, opt_loaded, opt_err = _make_optimizer(model, lr, weight_decay, optimizer_state_path, dev)
     amp = bool(use_amp)
@@ -320,7 +335,7 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
         except Exception:
             pass
     out = {
-        "epoch_stats": epoch_stats, "num_samples": global_n, "num_samples_after_filter": n,
+        "epoch_stats": epoch_stats, "num_samples": global_n, "num_samples_after_filter": n_filtered,
         "filtered_non_finite_samples": filtered, "parallel_strategy": strategy, "ddp_world_size": world,
         "local_batch_count": int(local_batches), "synced_batch_count": int(synced),
         "dropped_samples_for_sync": int(dropped), "optimizer_loaded": opt_loaded, "optimizer_load_error": opt_err,
@@ -331,6 +346,8 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                    "first_batch_sec": float(first_batch_sec), "ddp_pre_sharded": bool(ddp_pre_sharded)}}
     if sym_draw is not None:
         out["symmetry_augment"] = sym_draw.metrics()
+    if dedup_stats is not None:
+        out["position_dedup"] = dedup_stats
     return model, out
 
 

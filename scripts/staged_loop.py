@@ -58,6 +58,9 @@ def main() -> int:
     ap.add_argument("--epochs", type=int, default=1)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--soft-label-alpha", type=float, default=0.3)
+    ap.add_argument("--dedup-positions", default="off", choices=("off", "exact", "symmetric"),
+                    help="merge duplicate positions among the iteration's rows before training (see train_stage.py)")
+    ap.add_argument("--dedup-max-copies", type=int, default=1)
     ap.add_argument("--overlap", type=int, default=0, choices=(0, 1),
                     help="1: lag-1 pipeline, the trainer trains on generation i-1 while generation i is played")
     ap.add_argument("--net-check", type=int, default=0,
@@ -117,8 +120,11 @@ def main() -> int:
         return [int(e.item()) for e in every]
 
     def train(model, data):
+        dedup = ({"dedup_positions": args.dedup_positions, "dedup_max_copies": args.dedup_max_copies}
+                 if args.dedup_positions != "off" else {})
         model, metrics = train_network_from_tensors(model, data, batch_size=args.batch_size, epochs=args.epochs,
-                                                    lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev))
+                                                    lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),
+                                                    **dedup)
         model.eval()
         e = metrics["epoch_stats"][-1] if metrics and metrics.get("epoch_stats") else {}
         # rows handed to the trainer; `samples_stepped` (epoch_stats.samples) can be lower: the AMP scaler skips the

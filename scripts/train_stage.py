@@ -51,6 +51,12 @@ def parse(argv=None):
     ap.add_argument("--symmetry-augment", dest="symmetry_augment", type=int, nargs="?", const=1, default=0,
                     help="show every training row under a random one of the 8 board symmetries (default off)")
     ap.add_argument("--symmetry-seed", dest="symmetry_seed", type=int, default=0)
+    ap.add_argument("--dedup_positions", "--dedup-positions", dest="dedup_positions", default="off",
+                    choices=["off", "exact", "symmetric"],
+                    help="merge rows with the same position (exact) or the same position up to the 8 board symmetries "
+                         "(symmetric) and train on the averaged targets (default off)")
+    ap.add_argument("--dedup_max_copies", "--dedup-max-copies", dest="dedup_max_copies", type=int, default=1,
+                    help="a merged position is kept min(its count, M) times (default 1: each position once)")
     args, ignored = ap.parse_known_args(argv)
     args.ignored = ignored
     return args
@@ -91,6 +97,13 @@ def main(argv=None) -> int:
                   parallel_strategy=strategy, optimizer_state_path=args.optimizer_state_path)
     if int(args.symmetry_augment):
         common.update(symmetry_augment=True, symmetry_seed=int(args.symmetry_seed))
+    if args.dedup_positions != "off" or int(args.dedup_max_copies) != 1:
+        from liuzhou_amd.position_dedup import dedup_on
+        if dedup_on(args.dedup_positions, args.dedup_max_copies):
+            if int(args.streaming_load):
+                raise SystemExit("--dedup_positions needs --streaming_load 0: the streaming trainer sees one batch at a "
+                                 "time, duplicate positions can only be merged over the whole set of rows")
+            common.update(dedup_positions=args.dedup_positions, dedup_max_copies=int(args.dedup_max_copies))
     t0 = time.perf_counter()
     if int(args.streaming_load):
         budget = int(args.replay_budget_per_file)
