@@ -799,7 +799,14 @@ LZ_API int lz_tree_expand(const LzTreeDesc* tree, int is_root, const float* log_
  *     inverse-CDF sample with uniforms[g]; 0: most visits -> Q -> prior -> lowest index; force_uniform[g] != 0
  *     (opening plies): uniform over the legal children, index floor(uniforms[g] * n).
  *   policy_dense (training target) = the same with `target_temperatures` (NULL: = temperatures) on the scores
- *     visits + prior_pseudocount * normalised priors  (policy_target_temperature / _prior_pseudocount). */
+ *     visits + prior_pseudocount * normalised priors  (policy_target_temperature / _prior_pseudocount).
+ * Precondition: wherever a softmax is taken (the temperature in force above 1e-6), a non-terminal root's scores have a
+ *   positive sum -- at least one visited child, or prior_pseudocount > 0 for the target.  The reference raises "no policy
+ *   mass" otherwise; here the row would be 0 / 0 and a sampled pick would leave chosen_index = -1 beside chosen_valid = 1,
+ *   and nothing on the device checks it (no synchronisation on this path).  The host keeps it: a search runs at least one
+ *   simulation (tree_engine.search_simulations refuses fewer; the playout cap and the KLD rule never lower a budget below
+ *   1), every simulation ends in a visit of one root child, and a root whose expansion found no edge is terminal here.
+ *   At a temperature <= 1e-6 such a root is defined: one-hot on the first maximum of the scores. */
 LZ_API int lz_tree_finish(const LzTreeDesc* tree, const float* temperatures, const float* target_temperatures,
                           float prior_pseudocount, const uint8_t* force_uniform, int sample_moves,
                           const float* uniforms,

@@ -242,6 +242,15 @@ def puct_shape_refusal(*, fpu_reduction=None, fpu_root_reduction=None, cpuct_log
     return shape
 
 
+def search_simulations(num_simulations) -> int:
+    """Validate the simulations of a search: an integer >= 1.  A root expanded and never searched has no visited child, and
+    the read-out (lz_tree_finish) has no policy for it at a temperature above 1e-6 -- the reference raises "no policy mass"
+    there; every smaller budget the searches can end with (playout cap, KLD-gain early stopping) is >= 1 too."""
+    if isinstance(num_simulations, bool) or int(num_simulations) != num_simulations or int(num_simulations) < 1:
+        raise ValueError(f"num_simulations must be an integer >= 1 (a root without a visit has no policy), got {num_simulations!r}")
+    return int(num_simulations)
+
+
 def forced_playouts_on(k) -> bool:
     """Validate `forced_playouts_k`: 0 = off, a positive finite number = on; negative or non-finite is a ValueError."""
     k = float(k)
@@ -1037,6 +1046,7 @@ class PortableTreeMCTS:
         word.  Training targets and every other output stay as the finish wrote them.  `move_pick_counts` (int64[4]):
         games re-picked, children cut by the offset, children cut by the value test, picks changed.  Composes with
         everything but the Gumbel root search and `sample_moves=False` (ValueError)."""
+        search_simulations(num_simulations)
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
         self.solver = bool(solver)
@@ -1675,6 +1685,7 @@ class DualStreamTreeMCTS:
     covers every CU.  Results are identical to one engine over all games (games are independent)."""
 
     def __init__(self, model, num_games: int, num_simulations: int, device, num_parts: Optional[int] = None, **kw) -> None:
+        search_simulations(num_simulations)
         dev = torch.device(device)
         self.B = int(num_games)
         k = 2 if num_parts is None else int(num_parts)      # 3 and 4 parts measured 34 % slower than 2 on C2

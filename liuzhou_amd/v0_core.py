@@ -198,7 +198,7 @@ def project_policy_logits_fast(log_p1, log_p2, log_pmc, legal_mask, placement_di
     return probs, ml
 
 
-PACK_CAP = 80   # >= max legal actions of any state (placement 36, movement <= 72)
+PACK_CAP = 80   # >= max legal actions of any state (placement and the selections 36, movement <= 60: the grid's adjacencies)
 
 
 def root_pack_rows(legal_mask, probs, metadata, cap: int = PACK_CAP):

@@ -19,6 +19,8 @@ Fixture groups:
   g8_selfplay.npz   4-game root-PUCT self-play trace of the reference v1 runner (CPU)
   g11_loss.npz      training-loss values and head gradients from the reference's own loss functions
   g21_loss_edges.npz  the same functions on the edge batch of tests/train_loss_cases.py, three settings
+  g22_finish_edges.npz  policy_from_visits_and_priors / deterministic_action_from_search on the finish rows of
+                    tests/readout_cases.py
   g10_tree_selfplay.npz  full-tree self-play traces of the reference portable runner (subtree reuse on every move)
   g9_net.npz        network outputs for seeded weights (tiny / 6x64 / 10x128)
   g14_eval_arena.npz  the reference's evaluation arena (two tiny checkpoints, deterministic): outcome, moves, evaluations
@@ -899,6 +901,46 @@ def gen_loss_edges():
 
 
 # --------------------------------------------------------------------------------------------
+# G22: the read-out's policy and deterministic pick at their edges (the finish rows of tests/readout_cases.py)
+# --------------------------------------------------------------------------------------------
+def gen_finish_edges():
+    import importlib
+    import importlib.util
+    from v1.python.portable_mcts import deterministic_action_from_search, policy_from_visits_and_priors
+    # our own `tests` package by path: the reference has one of its own in front of it on sys.path
+    spec = importlib.util.spec_from_file_location("tests", os.path.join(REPO, "tests", "__init__.py"),
+                                                  submodule_search_locations=[os.path.join(REPO, "tests")])
+    sys.modules["tests"] = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(sys.modules["tests"])
+    if REPO not in sys.path:
+        sys.path.append(REPO)
+    cases = importlib.import_module("tests.readout_cases")
+    launches = cases.finish_launches()
+    rows = list(cases.g22_rows())
+    out = dict(launch=np.array([i for i, _ in rows], np.int32), game=np.array([g for _, g in rows], np.int32),
+               visits=np.zeros((len(rows), 72), np.int32), policy=np.zeros((len(rows), 72), np.float32),
+               refused=np.zeros(len(rows), np.uint8), action=np.full(len(rows), -1, np.int32),
+               temperature=np.zeros(len(rows), np.float32), beta=np.zeros(len(rows), np.float32))
+    for k, (i, g) in enumerate(rows):
+        N, P, q, Tt, beta = cases.g22_inputs(launches[i], g)
+        n = len(N)
+        out["visits"][k, :n], out["temperature"][k], out["beta"][k] = N, Tt, beta
+        try:
+            pol = policy_from_visits_and_priors(torch.from_numpy(N.astype(np.float32)), torch.from_numpy(P.copy()),
+                                                temperature=Tt, prior_pseudocount=beta)
+            out["policy"][k, :n] = pol.numpy()
+        except RuntimeError:                                    # no policy mass: recorded, not dropped
+            out["refused"][k] = 1
+        except ValueError:                                      # a negative temperature
+            out["refused"][k] = 2
+        out["action"][k] = deterministic_action_from_search(torch.from_numpy(N), torch.from_numpy(q.copy()),
+                                                            torch.from_numpy(P.copy()), torch.ones(n, dtype=torch.bool))
+    print(f"[g22] rows={len(rows)} refused: no mass {int((out['refused'] == 1).sum())}, "
+          f"negative temperature {int((out['refused'] == 2).sum())}")
+    np.savez_compressed(os.path.join(OUT, "g22_finish_edges.npz"), **out)
+
+
+# --------------------------------------------------------------------------------------------
 # G9: network
 # --------------------------------------------------------------------------------------------
 def gen_net(chosen):
@@ -965,6 +1007,8 @@ def main():
         gen_loss()
     if not which or "g21" in which:
         gen_loss_edges()
+    if not which or "g22" in which:
+        gen_finish_edges()
     for f in sorted(os.listdir(OUT)):
         print(f"  {f}: {os.path.getsize(os.path.join(OUT, f)) / 1024:.1f} KiB")
 

@@ -21,6 +21,7 @@ import math
 import numpy as np
 
 from oracle import lz_oracle as O
+from tests import readout_ref as R
 
 
 class _Node:
@@ -258,36 +259,12 @@ class ForcedTree:
         N = [int(c.visit_count) for c in ch]
         if not (self.k > 0.0 and self.forced_on) or self.root_terminal():
             return np.array(N, np.int32)
-        T = max(int(r.visit_count), 1)
-        sq = math.sqrt(float(T))
-
-        def q_of(c):
-            if c.visit_count <= 0:
-                return 0.0
-            mv = c.value_sum / float(c.visit_count)
-            return mv if c.player == r.player else -mv
-
-        star = max(range(len(ch)), key=lambda j: (N[j], -j))
-        s_star = q_of(ch[star]) + self.c * float(ch[star].prior) * sq / (1.0 + float(N[star]))
-        out = list(N)
+        q = [0.0] * len(ch)
         for j, c in enumerate(ch):
-            if j == star or N[j] <= 0:
-                continue
-            thr = (self.k * float(c.prior)) * float(T)
-            F = max(0, int(math.isqrt(int(min(thr, 1e30)))) - 1)
-            while float(F) * float(F) < thr:
-                F += 1
-            while F > 0 and float(F - 1) * float(F - 1) >= thr:
-                F -= 1
-            gap = s_star - q_of(c)
-            if gap > 0.0:
-                x = (self.c * float(c.prior) * sq) / gap - 1.0
-                L = 0 if x < 0.0 else (N[j] if x >= float(N[j]) else int(math.floor(x)) + 1)
-            else:
-                L = N[j]
-            n2 = min(N[j], max(N[j] - F, L))
-            out[j] = 0 if n2 <= 1 else n2
-        return np.array(out, np.int32)
+            if c.visit_count > 0:
+                mv = c.value_sum / float(c.visit_count)
+                q[j] = mv if c.player == r.player else -mv
+        return R.prune_targets(N, [float(c.prior) for c in ch], q, int(r.visit_count), self.k, self.c)
 
 
 def target_policy(tree: ForcedTree, temperature: float, prior_pseudocount: float = 0.0) -> np.ndarray:

@@ -17,16 +17,11 @@ import math
 import numpy as np
 
 from liuzhou_amd.gumbel import considered_table
+from tests import readout_ref as R
 from tests.forced_tree import ForcedTree, _terminal_value
 
 
-def butterfly_sum(terms) -> float:
-    """Sum of up to 128 doubles in the device's order."""
-    ne = len(terms)
-    x = [(float(terms[l]) if l < ne else 0.0) + (float(terms[l + 64]) if l + 64 < ne else 0.0) for l in range(64)]
-    for o in (32, 16, 8, 4, 2, 1):
-        x = [x[l] + x[l ^ o] for l in range(64)]
-    return x[0]
+butterfly_sum = R.butterfly_sum          # the one definition: tests/readout_ref.py
 
 
 class GumbelTree(ForcedTree):
@@ -98,26 +93,9 @@ class GumbelTree(ForcedTree):
                 q.append(mv if c.player == r.player else -mv)
             else:
                 q.append(0.0)
-        Pv = butterfly_sum([P[k] if N[k] > 0 else 0.0 for k in range(len(ch))])
-        Pq = butterfly_sum([P[k] * q[k] if N[k] > 0 else 0.0 for k in range(len(ch))])
-        T = sum(N)
-        tm = float(T)
-        vmix = self.v0 if (T == 0 or Pv <= 0.0) else (self.v0 + tm * (Pq / Pv)) / (1.0 + tm)
-        scale = (self.c_visit + float(max(N))) * self.c_scale
-        sigma = [scale * (0.5 * (q[k] if N[k] > 0 else vmix)) for k in range(len(ch))]
-        score = [float(self.gl[k]) + sigma[k] for k in range(len(ch))]
-        L = [N[k] - self.base[k] for k in range(len(ch))]
-        return score, sigma, vmix, L
+        return R.gumbel_scores(N, P, q, self.gl, self.base, self.v0, self.c_visit, self.c_scale)
 
-    @staticmethod
-    def _argmax(score, cand):
-        best, best_k = -math.inf, -1
-        for k in cand:
-            if best_k < 0 or score[k] > best:
-                best, best_k = score[k], k
-        if best_k >= 0 and best != best:          # NaN
-            return -1
-        return best_k
+    _argmax = staticmethod(R.gumbel_argmax)
 
     def root_choice(self) -> int:
         """The child offset the Gumbel rule takes at the root right now."""
@@ -194,18 +172,15 @@ class GumbelTree(ForcedTree):
     def gumbel_finish(self):
         """(pick child offset, target float32[220], score float64[ne], vmix) of a Gumbel game with a live root."""
         r = self.nodes[self.root]
-        score, sigma, vmix, L = self.scores()
-        lmax = max(L)
-        pick = self._argmax(score, [k for k in range(r.n_children) if L[k] == lmax])
-        P = [float(self.nodes[r.first_child + k].prior) for k in range(r.n_children)]
-        lg = [math.log(P[k]) + sigma[k] if P[k] > 0.0 else -math.inf for k in range(r.n_children)]
-        mx = max(lg)
-        ex = [0.0 if x == -math.inf else math.exp(x - mx) for x in lg]
-        tot = butterfly_sum(ex)
+        ch = [self.nodes[r.first_child + k] for k in range(r.n_children)]
+        q = [(c.value_sum / float(c.visit_count)) * (1.0 if c.player == r.player else -1.0) if c.visit_count > 0 else 0.0
+             for c in ch]
+        pick, probs, score, vmix = R.gumbel_finish([int(c.visit_count) for c in ch], [float(c.prior) for c in ch], q, self.gl,
+                                                   self.base, self.v0, self.c_visit, self.c_scale)
         target = np.zeros(220, np.float32)
-        for k in range(r.n_children):
-            target[self.nodes[r.first_child + k].action_index] = np.float32(ex[k] / tot)
-        return pick, target, np.array(score, np.float64), float(vmix)
+        for k, c in enumerate(ch):
+            target[c.action_index] = probs[k]
+        return pick, target, score, vmix
 
 
 def rng_gumbel(seed: int, game, ply, count: int):

@@ -24,6 +24,7 @@ import math
 import numpy as np
 
 from oracle import lz_oracle as O
+from tests import readout_ref as R
 from tests.forced_tree import ForcedTree, _terminal_value
 
 INFO_WHITE, INFO_TERMINAL, INFO_PROVEN = 1, 2, 16
@@ -214,15 +215,8 @@ class SolverTree(ForcedTree):
             return int(picked_action)
         kids = list(range(r.first_child, r.first_child + r.n_children))
         xs = [self.x(self.root, c) if self.decided(c) else None for c in kids]
-        most = lambda cs: max(cs, key=lambda c: (self.nodes[c].visit_count, -c))
-        wins = [c for c, v in zip(kids, xs) if v == 1]
-        if wins:
-            return int(self.nodes[most(wins)].action_index)
-        lost = {self.nodes[c].action_index for c, v in zip(kids, xs) if v == -1}
-        rest = [c for c, v in zip(kids, xs) if v != -1]
-        if int(picked_action) in lost and rest:
-            return int(self.nodes[most(rest)].action_index)
-        return int(picked_action)
+        return R.solver_pick([self.nodes[c].action_index for c in kids], [self.nodes[c].visit_count for c in kids], xs,
+                             picked_action)
 
 
 # ---- exact values by brute force, and the test positions --------------------------------------------------------------

@@ -9,6 +9,7 @@ import torch
 
 from tests import move_pick as chk
 from tests.golden_utils import load, states, FIELDS
+from tests.hand_roots import _code
 from tests.tree_parity import to_gpu_batch, root_edges, EDGE_DT, NODE_DT
 
 DEV = torch.device("cuda:0")
@@ -72,20 +73,6 @@ def _positions(idx, terminal=()):
     for g in terminal:
         st["moves_since_capture"][g] = 36
     return to_gpu_batch(st, DEV), st
-
-
-def _code(phase, a):
-    """index_to_code of csrc/lz_rules.h."""
-    if a < 0:
-        return [0, -1, -1, -1]
-    if a < 36:
-        return [1, a, -1, -1]
-    if a < 180:
-        p, s = (a - 36) >> 2, (a - 36) & 3
-        return [2, p, s, p + (-6, 6, -1, 1)[s]]
-    if a < 216:
-        return [{2: 3, 5: 4, 6: 5, 7: 6, 4: 7}.get(int(phase), 0), a - 180, -1, -1]
-    return [8 if a == 216 else 0, -1, -1, -1]
 
 
 GUARD = 16

@@ -9,41 +9,16 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import lz_oracle as O
-from tests.tree_parity import EDGE_DT, NODE_DT, to_gpu_batch
+from tests.hand_roots import HandEngine, layout, one_root
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
 def _engine_with_root_edges(actions, visits, q_root_side, priors):
-    """A one-game arena whose root (the initial position, black to move) has the given children; q is given from the
-    root mover's side and the children are white-to-move positions, so W = -q * N in the child mover's perspective."""
-    from liuzhou_amd.tree_engine import TreeEngine
-    eng = TreeEngine(1, 64, DEV, 1.0)
-    eng.set_roots(to_gpu_batch(O.initial_states(1), DEV))
-    eng.begin()
-    n = len(actions)
-    edges = np.zeros(n, EDGE_DT)
-    edges["act"] = actions
-    edges["P"] = priors
-    edges["n_info"] = np.asarray(visits, np.uint32) | (np.uint32(1) << 24)          # info bit 0: child mover is white
-    edges["W"] = -np.asarray(q_root_side, np.float64) * np.asarray(visits, np.float64)
-    edges["child"] = -1
-    node = eng.buf["nodes"].view(1, eng.node_cap, 6)[0, :1].cpu().numpy().view(NODE_DT).copy()
-    # the root's run at the start of chunk 0 of the edge pool, booked as the game's first chunk
-    node["edge_begin"], node["nedges"], node["parent"] = 0, n, -1
-    eng.buf["nodes"].view(1, eng.node_cap, 6)[0, :1] = torch.from_numpy(node.view(np.int64).reshape(1, 6)).to(DEV)
-    eng.buf["edges"][:n] = torch.from_numpy(edges.view(np.int64).reshape(n, 4)).to(DEV)
-    eng.buf["n_edges"].fill_(n)
-    eng.buf["chunk_list"][0] = 0
-    eng.buf["n_chunks"].fill_(1)
-    eng.buf["free_chunks"].copy_(torch.roll(torch.arange(eng.pool_chunks, dtype=torch.int32, device=DEV), -1))
-    eng.buf["pool_top"].fill_(eng.pool_chunks - 1)
-    eng.buf["root_visits"].fill_(int(np.sum(visits)))
-    eng.buf["root_w"].fill_(float(np.sum(np.asarray(q_root_side) * np.asarray(visits))))
-    eng.buf["root_terminal"].zero_()
-    return eng
+    """A one-game arena whose root (the initial position, black to move) has the given children, written by the hand-built
+    roots harness (tests/hand_roots.py)."""
+    return HandEngine(layout([one_root(actions, visits, q_root_side, priors)]), DEV).engine
 
 
 def test_deterministic_action_breaks_visit_ties_by_q_then_prior_then_index():
