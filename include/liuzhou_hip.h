@@ -1042,6 +1042,23 @@ LZ_API int lz_unpack_trajectory_rows(const void* records, int64_t rows, float* s
                                      float* policy_targets, float* value_targets, float* soft_value_targets,
                                      void* stream);
 
+/* Replay window (liuzhou_amd/replay_window.py): a training batch decoded straight out of a ring
+ * of `capacity` records.  Output row j is byte for byte what lz_unpack_trajectory_rows of record slot[j] followed by
+ * lz_symmetry_gather_samples with sym[j] writes (sym int8 / int32 by sym_width 1 / 4; NULL = the identity for every
+ * row, sym_width then ignored); value and soft value are copied.  A slot[j] outside [0, capacity) or a sym[j] outside
+ * 0..7 gives an all-zero row (planes, mask, policy, value, soft): the convention of lz_symmetry_gather_samples.
+ * Unpacking is total as above: the phase is (w0 >> 36) & 7, bits the layout does not own are ignored, a legal bit past
+ * the 72nd gets policy 0, nothing outside the 360 bytes of a record is read.  Policy, value and soft value are bit
+ * copies (NaN payloads, -0.0 on a legal entry, infinities, subnormals).  m == 0: LZ_OK without a launch; m < 0,
+ * capacity < 0, sym_width not 1 or 4 with sym != NULL, or a NULL required pointer: LZ_ERR_ARG; records 8-byte and the
+ * float outputs 4-byte aligned, else LZ_ERR_ALIGN.  One wave per row; no allocation, no synchronisation, capturable.
+ * HIP build only, like the codec. */
+LZ_API int lz_replay_gather_rows(const void* records, int64_t capacity, const int64_t* slot /*[m]*/,
+                                 const void* sym /*[m] or NULL*/, int32_t sym_width, int64_t m,
+                                 float* out_planes /*[m,11,36]*/, uint8_t* out_masks /*[m,220]*/,
+                                 float* out_policy /*[m,220]*/, float* out_value /*[m]*/, float* out_soft /*[m]*/,
+                                 void* stream);
+
 /* ---- board symmetries (the dihedral group D4 of the 6x6 square; csrc/lz_symmetry.h) --------------------------------
  * Element ids 0..7: identity, rotate 90 (r,c)->(c,5-r), rotate 180, rotate 270 (r,c)->(5-c,r), flip left-right
  * (r,c)->(r,5-c), flip up-down (r,c)->(5-r,c), transpose (r,c)->(c,r), anti-transpose (r,c)->(5-c,5-r).  A transformed

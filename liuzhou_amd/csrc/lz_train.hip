@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/liuzhou_hip.h"
+#include "lz_symmetry.h"
 #include "lz_wave.h"
 
 namespace {
@@ -294,6 +295,71 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void unpack_rows_kernel(
         value[s] = vq[0]; soft[s] = vq[1];
     }
 }
+
+// ---- replay window: records -> symmetric training batch in one pass ----------------------
+// Output row j = unpack_rows_kernel of record slot[j] followed by lz_symmetry.hip:gather_samples_kernel with sym[j],
+// without the 2 692-byte row in between.  One wave per output row.  The 11 header words of the record (4 boards, 7 mask
+// words) have a wave-uniform address: scalar loads, once per row.  Output cell q of plane p < 4 is bit sigma^-1(q) of
+// board p; output action b reads source action a = kSym.action[inv][b], whose policy sits at the rank of a among the
+// legal bits: the prefix counts of the three full mask words once per row, one popcount per lane.  Every store is a
+// contiguous run of the output row; the 72 policy floats are the only per-lane loads (inside one 288-byte run).
+__device__ __forceinline__ uint64_t pick4(int i, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+    return i == 0 ? a : i == 1 ? b : i == 2 ? c : d;            // selects: no private array indexed by a lane
+}
+
+__global__ __launch_bounds__(kWave * kWavesPerBlock) void replay_gather_rows_kernel(
+    const uint8_t* __restrict__ in, int64_t capacity, const int64_t* __restrict__ slot, const void* __restrict__ sym,
+    int width, int64_t m, float* __restrict__ planes, uint8_t* __restrict__ legal, uint32_t* __restrict__ policy,
+    uint32_t* __restrict__ value, uint32_t* __restrict__ soft) {
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t j = (int64_t)blockIdx.x * kWavesPerBlock + wv;
+    if (j >= m) return;
+    int k = 0;
+    if (sym != nullptr) {
+        k = width == 1 ? (int)reinterpret_cast<const int8_t*>(sym)[j] : (int)reinterpret_cast<const int32_t*>(sym)[j];
+        k = __builtin_amdgcn_readfirstlane(k >= 0 && k < lz::kSyms ? k : -1);
+    }
+    const int64_t s = slot[j];
+    float* pl = planes + j * 396;
+    uint8_t* mout = legal + j * kTotal;
+    uint32_t* qout = policy + j * kTotal;
+    if (k < 0 || s < 0 || s >= capacity) {                      // invalid id or slot: the whole output row is zeroed
+        for (int q = lane; q < 396; q += kWave) pl[q] = 0.f;
+        for (int b = lane; b < kTotal; b += kWave) { mout[b] = 0; qout[b] = 0u; }
+        if (lane == 0) { value[j] = 0u; soft[j] = 0u; }
+        return;
+    }
+    const uint8_t* rec = in + s * kRecBytes;
+    const uint64_t* wq = reinterpret_cast<const uint64_t*>(rec);
+    const uint32_t* mq = reinterpret_cast<const uint32_t*>(rec + 32);
+    const uint32_t* pv = reinterpret_cast<const uint32_t*>(rec + 60);
+    const uint64_t w0 = wq[0], w1 = wq[1], w2 = wq[2], w3 = wq[3];
+    const uint64_t b0 = (uint64_t)mq[0] | ((uint64_t)mq[1] << 32), b1 = (uint64_t)mq[2] | ((uint64_t)mq[3] << 32),
+                   b2 = (uint64_t)mq[4] | ((uint64_t)mq[5] << 32), b3 = (uint64_t)mq[6];
+    const int phase = (int)((w0 >> 36) & 7);
+    const int inv = lz::sym_inverse(k);
+    for (int q = lane; q < 396; q += kWave) {
+        const int p = q / 36, c = q - p * 36;
+        const bool bit = p < 4 ? (pick4(p, w0, w1, w2, w3) >> lz::sym_cell(inv, c)) & 1 : (phase == p - 3);
+        pl[q] = bit ? 1.f : 0.f;
+    }
+    const int c1 = __popcll(b0), c2 = c1 + __popcll(b1), c3 = c2 + __popcll(b2);
+    for (int b = lane; b < kTotal; b += kWave) {
+        const int a = lz::kSym.action[inv][b];                  // out[P(a)] = in[a]
+        const int wi = a >> 6, bi = a & 63;
+        const uint64_t bal = pick4(wi, b0, b1, b2, b3);
+        const bool lg = (bal >> bi) & 1;
+        const int rank = (wi == 0 ? 0 : wi == 1 ? c1 : wi == 2 ? c2 : c3) + __popcll(bal & ((1ull << bi) - 1ull));
+        mout[b] = lg ? 1 : 0;
+        const uint32_t pw = pv[rank < 72 ? rank : 71];          // always inside the record, whatever its mask holds
+        qout[b] = (lg && rank < 72) ? pw : 0u;                  // bit copy; a legal bit past the 72nd gets 0
+    }
+    if (lane == 0) {
+        const uint32_t* vq = reinterpret_cast<const uint32_t*>(rec + 348);
+        value[j] = vq[0]; soft[j] = vq[1];
+    }
+}
 }  // namespace
 
 extern "C" int lz_pack_trajectory_rows(const float* state_tensors, const uint8_t* legal_masks,
@@ -323,5 +389,23 @@ extern "C" int lz_unpack_trajectory_rows(const void* records, int64_t rows, floa
     hipLaunchKernelGGL(unpack_rows_kernel, dim3(grid), dim3(kWave * kWavesPerBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint8_t*>(records), rows,
                        state_tensors, legal_masks, policy_targets, value_targets, soft_value_targets);
+    return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
+}
+
+extern "C" int lz_replay_gather_rows(const void* records, int64_t capacity, const int64_t* slot, const void* sym,
+                                     int32_t sym_width, int64_t m, float* out_planes, uint8_t* out_masks,
+                                     float* out_policy, float* out_value, float* out_soft, void* stream) {
+    if (m < 0 || capacity < 0 || (sym != nullptr && sym_width != 1 && sym_width != 4)) return LZ_ERR_ARG;
+    if (m == 0) return LZ_OK;
+    if (!records || !slot || !out_planes || !out_masks || !out_policy || !out_value || !out_soft) return LZ_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(records) % 8 ||
+        (reinterpret_cast<uintptr_t>(out_planes) | reinterpret_cast<uintptr_t>(out_policy) |
+         reinterpret_cast<uintptr_t>(out_value) | reinterpret_cast<uintptr_t>(out_soft)) % 4)
+        return LZ_ERR_ALIGN;
+    const unsigned grid = (unsigned)((m + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL(replay_gather_rows_kernel, dim3(grid), dim3(kWave * kWavesPerBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint8_t*>(records), capacity, slot,
+                       sym, (int)sym_width, m, out_planes, out_masks, reinterpret_cast<uint32_t*>(out_policy),
+                       reinterpret_cast<uint32_t*>(out_value), reinterpret_cast<uint32_t*>(out_soft));
     return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
 }

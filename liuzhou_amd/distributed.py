@@ -43,11 +43,13 @@ def _free_device_bytes(dev: torch.device) -> int:
     return int(free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
 
 
-def _gather_compact(batch: TensorSelfPlayBatch, dst: int, group) -> Optional[TensorSelfPlayBatch]:
+def _gather_compact(batch: TensorSelfPlayBatch, dst: int, group, as_records: bool = False):
     """HIP path: rows travel as exact 360-byte records (trajectory_codec.py), 7.5x less xGMI traffic than the five
     tensors, packed / unpacked by one kernel each side.  The row count and the number of rows the record format cannot
     hold travel together in the one all-gather that precedes the transfers, so a bad row on any rank makes EVERY rank
-    raise before a single send / receive is posted (no rank is left waiting in a collective)."""
+    raise before a single send / receive is posted (no rank is left waiting in a collective).
+    `as_records`: `dst` keeps the received uint8[n, 360] records (for a `replay_window.ReplayWindow`) instead of
+    expanding them, and only their 360 bytes per row have to fit."""
     from .trajectory_codec import RECORD_BYTES, pack_batch, unpack_records
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     dev = batch.state_tensors.device
@@ -71,7 +73,13 @@ def _gather_compact(batch: TensorSelfPlayBatch, dst: int, group) -> Optional[Ten
     # the destination expands every rank's records to the 2 692-byte five-tensor rows next to whatever else lives on
     # its device (at C4 rank 0 still holds its own tree arenas): refuse -- on every rank -- before anything moves
     need, free_dst = sum(counts) * (EXPANDED_ROW_BYTES + RECORD_BYTES), int(every[dst, 2])
-    if free_dst >= 0 and need > free_dst:
+    if as_records:
+        need = sum(counts) * RECORD_BYTES
+        if free_dst >= 0 and need > free_dst:
+            raise RuntimeError(f"gather_trajectories: rank {dst} needs {need / 2**30:.1f} GiB to receive the records of "
+                               f"{sum(counts)} rows but only {free_dst / 2**30:.1f} GiB of its device memory are free; "
+                               "every rank raises, nothing was sent")
+    elif free_dst >= 0 and need > free_dst:
         raise RuntimeError(f"gather_trajectories: rank {dst} needs {need / 2**30:.1f} GiB to receive and expand "
                            f"{sum(counts)} rows but only {free_dst / 2**30:.1f} GiB of its device memory are free; release "
                            "the search engines (arenas) first or gather in several pieces; every rank raises, nothing was "
@@ -98,21 +106,30 @@ def _gather_compact(batch: TensorSelfPlayBatch, dst: int, group) -> Optional[Ten
         for req in dist.batch_isend_irecv(ops):
             req.wait()
     buf = buf.to(dev)
-    return unpack_records(buf)
+    return buf if as_records else unpack_records(buf)
 
 
 def gather_trajectories(batch: TensorSelfPlayBatch, dst: int = 0, group=None,
-                        compact: Optional[bool] = None, force: bool = False) -> Optional[TensorSelfPlayBatch]:
+                        compact: Optional[bool] = None, force: bool = False, as_records: bool = False):
     """Concatenate every rank's samples on `dst` (rank order).  Returns None on the other ranks.
     `compact` (default: on for HIP tensors) sends 360-byte records instead of the five tensors.
     `force`: run the protocol (counts all-gather, pack / unpack) even in a group of one -- what a 1-GPU box can execute
-    of the RCCL path (tests/test_gpu_distributed.py)."""
+    of the RCCL path (tests/test_gpu_distributed.py).
+    `as_records` (compact path only): `dst` gets the uint8[n, 360] records themselves, not the five tensors -- what a
+    `replay_window.ReplayWindow` stores; without a gather to run that is `pack_batch(batch)`."""
+    if as_records and compact is not None and not compact:
+        raise ValueError("as_records=True returns compact records: it cannot be combined with compact=False")
     if not dist.is_initialized() or (dist.get_world_size(group) == 1 and not force):
+        if as_records:
+            from .trajectory_codec import pack_batch
+            return pack_batch(batch)
         return batch
     if compact is None:
         compact = batch.state_tensors.is_cuda
     if compact:
-        return _gather_compact(batch, dst, group)
+        return _gather_compact(batch, dst, group, as_records) if as_records else _gather_compact(batch, dst, group)
+    if as_records:
+        raise ValueError("as_records=True needs the compact path (HIP tensors)")
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     dev = batch.state_tensors.device
     n_local = torch.tensor([batch.num_samples], dtype=torch.int64, device=dev)

@@ -453,3 +453,94 @@ def train_network_streaming(model, dataloader, *, total_samples: int, batch_size
     if sym_draw is not None:
         out["symmetry_augment"] = sym_draw.metrics()
     return model, out
+
+
+def train_network_from_window(model, window, *, batch_size: int = 512, epochs: int = 1, lr: float = 1e-3,
+                              weight_decay: float = 1e-4, soft_label_alpha: float = 0.0,
+                              anti_draw_penalty: float = 0.0, policy_draw_weight: float = 1.0, device: str = "cuda:0",
+                              use_amp: bool = True, grad_clip_norm: float = 1.0, warmup_steps: int = 0,
+                              parallel_devices: Optional[List[str]] = None, parallel_strategy: str = "none",
+                              ddp_pre_sharded: bool = False, optimizer_state_path: Optional[str] = None,
+                              symmetry_augment: bool = False, symmetry_seed: int = 0,
+                              symmetry_set: Sequence[int] = tuple(range(8)), replay_budget_per_generation: int = 0,
+                              replay_seed: int = 0) -> Tuple[Any, Dict[str, Any]]:
+    """One training pass over a `replay_window.ReplayWindow`: `train_network_from_tensors` with the rows left where they
+    are, as 360-byte records in the window's ring.  `window.select(replay_budget_per_generation, replay_seed)` is made
+    once per call (every row of the newest generation, then at most the budget of each older one; a budget <= 0 gives
+    the older generations together the weight of the newest); every batch is decoded out of the ring by one kernel that
+    also applies the board symmetries of `symmetry_augment`.  The shuffle, the symmetry draw, the optimiser and the
+    metrics are those of `train_network_from_tensors`; the metrics gain `replay_window`.  Non-finite rows were dropped
+    when their generation entered the window.  One trainer rank: no DDP, no duplicate merging."""
+    strategy = {"dp": "none", "data_parallel": "none", "none": "none", "single": "none", "ddp": "ddp"}.get(
+        str(parallel_strategy).strip().lower())
+    if strategy != "none":
+        raise ValueError(f"train_network_from_window trains on one rank: parallel_strategy={parallel_strategy!r} is not "
+                         "supported (expected none)")
+    if window.num_rows <= 0:
+        return model, {"epoch_stats": [], "num_samples": 0}
+    strategy, dev, rank, world = _resolve_strategy(parallel_strategy, device)
+    if dev != window.device:
+        raise ValueError(f"the window lives on {window.device}, the trainer on {dev}")
+    sym_draw = _SymmetryDraw(symmetry_set, symmetry_seed, rank, dev) if symmetry_augment else None
+    train_model = _wrap(model, strategy, dev)
+    t0 = time.perf_counter()
+    slots = window.select(int(replay_budget_per_generation), int(replay_seed))
+    replay = window.metrics(int(replay_budget_per_generation))
+    replay["select_sec"] = float(time.perf_counter() - t0)
+    n = int(slots.numel())
+    filtered = int(replay["filtered_non_finite_rows"])
+
+    optimizer, opt_loaded, opt_err = _make_optimizer(model, lr, weight_decay, optimizer_state_path, dev)
+    amp = bool(use_amp)
+    scaler = torch.amp.GradScaler("cuda", enabled=True) if amp else None
+    alpha = float(max(0.0, min(1.0, soft_label_alpha)))
+    draw_w = float(max(0.0, policy_draw_weight))
+    bsz = max(1, int(batch_size))
+    synced = local_batches = (n + bsz - 1) // bsz
+    n_epochs = max(1, int(epochs))
+    total_steps = synced * n_epochs
+    warm = min(max(0, int(warmup_steps)), total_steps // 2)
+    scheduler = torch.optim.lr_scheduler.LambdaLR(
+        optimizer, lambda step: (step + 1) / max(1, warm) if (warm > 0 and step < warm) else 1.0)
+    lr_start = float(optimizer.param_groups[0]["lr"])
+    epoch_stats: List[Dict[str, Any]] = []
+    first_batch_sec, first_done = 0.0, False
+    stepper = _Stepper(model, train_model, optimizer, scheduler, scaler, amp=amp, alpha=alpha,
+                       anti_draw=float(anti_draw_penalty), draw_w=draw_w, grad_clip_norm=grad_clip_norm, ddp=False, dev=dev)
+    stepper._nominal_rows = bsz                       # the one batch size worth a MIOpen kernel search (see _conv_mode)
+    for epoch in range(n_epochs):
+        perm = torch.randperm(n, device=dev)
+        stepper.reset()
+        for step_idx in range(synced):
+            start = step_idx * bsz
+            tb = time.perf_counter()
+            idx = perm[start:min(start + bsz, n)]
+            sym = sym_draw.draw(int(idx.numel())) if sym_draw is not None else None
+            stepper.step(*window.gather(slots.index_select(0, idx), sym))     # unpack + gather + transform in one pass
+            if not first_done:
+                first_batch_sec, first_done = time.perf_counter() - tb, True
+        st, _ = stepper.epoch_stats(epoch + 1, {"parallel_strategy": strategy, "ddp_world_size": world,
+                                                "local_batch_count": int(local_batches), "synced_batch_count": int(synced),
+                                                "dropped_samples_for_sync": 0,
+                                                "filtered_non_finite_samples": filtered})
+        epoch_stats.append(st)
+    lr_final = float(optimizer.param_groups[0]["lr"])
+    if optimizer_state_path:
+        try:
+            torch.save(optimizer.state_dict(), optimizer_state_path)
+        except Exception:
+            pass
+    out = {
+        "epoch_stats": epoch_stats, "num_samples": n, "num_samples_after_filter": n,
+        "filtered_non_finite_samples": filtered, "parallel_strategy": strategy, "ddp_world_size": world,
+        "local_batch_count": int(local_batches), "synced_batch_count": int(synced),
+        "dropped_samples_for_sync": 0, "optimizer_loaded": opt_loaded, "optimizer_load_error": opt_err,
+        "optimizer_lr_start": lr_start, "optimizer_lr_final": lr_final, "device": str(dev),
+        "device_fallback_count": 0, "device_fallback_reasons": [], "anti_draw_penalty": float(anti_draw_penalty),
+        "wdl_aux_loss_weight": 0.0, "warmup_steps": int(warm), "total_train_steps": int(total_steps),
+        "timing": {"cpu_shard_sec": 0.0, "h2d_copy_sec": 0.0,         # nothing is sharded or copied: the rows stay put
+                   "first_batch_sec": float(first_batch_sec), "ddp_pre_sharded": False}}
+    if sym_draw is not None:
+        out["symmetry_augment"] = sym_draw.metrics()
+    out["replay_window"] = replay
+    return model, out

@@ -17,6 +17,12 @@ Schedules (one iteration = one generation of games on every player):
                 generations anyway, `v1/train.py:1486-1735`).  After the last iteration the trainer trains on the
                 last generation ("tail"), so both schedules end with the same number of training passes.
 
+Replay window (--replay-generations G > 1): the trainer rank keeps the last G generations on its device as 360-byte
+records (`liuzhou_amd/replay_window.py`) and every training pass takes all rows of the newest generation plus at most
+--replay-budget rows of each older one (0: the older ones together weigh as much as the newest); with several ranks the
+gathered records enter the window without being expanded.  Each iteration's log entry then gains `replay`.  G = 1 (the
+default) is the code path and the JSON line without a window.
+
 With one process everything runs on the same GPU (self-play, then training; --overlap has nothing to overlap).
 Tests rehearse the multi-rank branches with several ranks on ONE GPU: `LZ_DIST_BACKEND=gloo LZ_SHARE_GPU=1` (RCCL
 refuses two ranks per device; the gather then stages its records through host memory, same protocol and kernels).
@@ -61,6 +67,14 @@ def main() -> int:
     ap.add_argument("--dedup-positions", default="off", choices=("off", "exact", "symmetric"),
                     help="merge duplicate positions among the iteration's rows before training (see train_stage.py)")
     ap.add_argument("--dedup-max-copies", type=int, default=1)
+    ap.add_argument("--replay-generations", type=int, default=1,
+                    help="train on a window of this many past generations kept on the trainer's device as 360-byte records "
+                         "(liuzhou_amd/replay_window.py); 1: every iteration trains on its own generation alone")
+    ap.add_argument("--replay-budget", type=int, default=0,
+                    help="rows each older generation of the window contributes to a pass; 0: the newest generation's "
+                         "count divided by the number of older generations (train_stage.py --replay_budget_per_file)")
+    ap.add_argument("--replay-capacity-rows", type=int, default=0,
+                    help="slots of the window's ring; 0: generations x players x games-per-gpu x min(max-game-plies, 144)")
     ap.add_argument("--overlap", type=int, default=0, choices=(0, 1),
                     help="1: lag-1 pipeline, the trainer trains on generation i-1 while generation i is played")
     ap.add_argument("--net-check", type=int, default=0,
@@ -70,6 +84,8 @@ def main() -> int:
                     help="after every hand-off compare an exact digest of each player's packed device weights with the "
                          "trainer's (outside the timed part of the iteration)")
     args = ap.parse_args()
+    if args.replay_generations > 1 and args.dedup_positions != "off":  # every rank refuses, before any collective
+        ap.error("--replay-generations > 1 does not merge duplicate positions: leave --dedup-positions off")
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     backend = os.environ.get("LZ_DIST_BACKEND", "nccl")
@@ -119,7 +135,29 @@ def main() -> int:
         dist.all_gather(every, t)
         return [int(e.item()) for e in every]
 
-    def train(model, data):
+    window = None
+    if trains and args.replay_generations > 1:
+        from liuzhou_amd.replay_window import ReplayWindow
+        from liuzhou_amd.train_bridge import train_network_from_window
+        rows = args.replay_capacity_rows or (args.replay_generations * max(1, world - 1) * args.games_per_gpu *
+                                             min(args.max_game_plies, 144))   # a game records at most 144 rows
+        window = ReplayWindow(dev, max_generations=args.replay_generations, capacity_rows=rows)
+
+    def train_window(model, data, generation):
+        n_new = int(data.shape[0]) if isinstance(data, torch.Tensor) else int(data.num_samples)
+        if n_new > 0:
+            window.add_generation(data, generation=generation)
+        model, metrics = train_network_from_window(model, window, batch_size=args.batch_size, epochs=args.epochs,
+                                                   lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),
+                                                   replay_budget_per_generation=args.replay_budget, replay_seed=0)
+        model.eval()
+        e = metrics["epoch_stats"][-1] if metrics and metrics.get("epoch_stats") else {}
+        return model, int(metrics.get("num_samples", 0)), {"avg_loss": e.get("avg_loss"), "samples_stepped": int(e.get("samples", 0)),
+                                                           "replay": metrics.get("replay_window")}
+
+    def train(model, data, generation=None):
+        if window is not None:
+            return train_window(model, data, generation)
         dedup = ({"dedup_positions": args.dedup_positions, "dedup_max_copies": args.dedup_max_copies}
                  if args.dedup_positions != "off" else {})
         model, metrics = train_network_from_tensors(model, data, batch_size=args.batch_size, epochs=args.epochs,
@@ -158,12 +196,15 @@ def main() -> int:
             z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)
             batch = TensorSelfPlayBatch(z(0, 11, 6, 6), z(0, 220, dt=torch.bool), z(0, 220), z(0), z(0))
             if overlap and pending is not None:                        # generation it-1, while the players play `it`
-                model, trained, loss = train(model, pending)
+                model, trained, loss = train(model, pending, it - 1)
                 pending = None
                 torch.cuda.synchronize(dev)
                 t_train = time.perf_counter() - t0
         t1 = time.perf_counter()
-        gathered = gather_trajectories(batch, dst=trainer) if world > 1 else batch
+        if world > 1 and args.replay_generations > 1:                 # the window stores the records as they arrive
+            gathered = gather_trajectories(batch, dst=trainer, as_records=True)
+        else:
+            gathered = gather_trajectories(batch, dst=trainer) if world > 1 else batch
         torch.cuda.synchronize(dev)
         t_gather = time.perf_counter() - t1
         if trains:
@@ -171,7 +212,7 @@ def main() -> int:
                 pending = gathered
             else:
                 t2 = time.perf_counter()
-                model, trained, loss = train(model, gathered)
+                model, trained, loss = train(model, gathered, it)
                 torch.cuda.synchronize(dev)
                 t_train = time.perf_counter() - t2
         t3 = time.perf_counter()
@@ -226,13 +267,17 @@ def main() -> int:
                         "train_samples": trained, "avg_loss": (loss or {}).get("avg_loss"),
                         "samples_stepped": (loss or {}).get("samples_stepped"), "weights_equal_on_all_ranks": same,
                         "weights_digest": digests_seen[-1] if digests_seen else None, "net_check": net_check})
+            if window is not None:
+                log[-1]["replay"] = (loss or {}).get("replay")
     tail = None
     if trains and overlap and pending is not None:                     # the last generation, nothing left to overlap with
         t0 = time.perf_counter()
-        model, trained, loss = train(model, pending)
+        model, trained, loss = train(model, pending, args.iterations)
         torch.cuda.synchronize(dev)
         tail = {"train_samples": trained, "avg_loss": (loss or {}).get("avg_loss"),
                 "samples_stepped": (loss or {}).get("samples_stepped"), "train_sec": round(time.perf_counter() - t0, 3)}
+        if window is not None:
+            tail["replay"] = (loss or {}).get("replay")
     if trains:
         steady = log[1:] if len(log) > 1 else log
         out = {"workload": f"C5 staged loop: {max(1, world - 1)} self-play GPU(s) x {args.games_per_gpu} games, "
