@@ -1127,6 +1127,48 @@ LZ_API int lz_net_forward_packed_gather_f16(const LzNetDesc* net, const void* pa
                                             int64_t num_slots, int64_t* count_out, float* log_p1, float* log_p2,
                                             float* log_pmc, float* value_logits, float* value, void* stream);
 
+/* ---- validation metrics (csrc/lz_valid.h) --------------------------------------------------------
+ * Per-row metrics of the network's outputs against the targets of rows it was not trained on, and their sums by phase and
+ * calibration bin.  None of the entry points allocates or synchronises; batch == 0 is LZ_OK without a launch, batch < 0
+ * or a NULL pointer LZ_ERR_ARG. */
+
+/* Rows: the inputs of lz_policy_value_loss_fwd_bwd (same shapes, same combined logits, masked log-softmax and two-hot
+ * target, no anti-draw substitution) plus planes float32[batch,11,6,6], read only at cell 0 of planes 4..10.
+ * rows float32[batch,12] = kl (the loss's terms[:,0]), ce, h_target, h_net (entropy of the network's policy over the
+ * legal actions), top1, p_top (the network's probability of the target's best action), bucket_ce (terms[:,2]), v_hat
+ * (sum of softmax(value_logits)[k] * (-1 + k / 50)), sq_err = (v_hat - z)^2, sign_ok (z not a hard draw and
+ * v_hat * z > 0), decisive (z is not a hard draw: not |z| < 1e-8), policy_valid (sum of the 220 target entries > 1e-8
+ * and at least one legal action).  Columns 0..5 are 0 where policy_valid is 0.
+ * cls int32[batch,4] = phase (lowest k whose plane 4 + k is non-zero at cell 0, -1: none), calibration bin
+ * min(9, max(0, floor((v_hat + 1) * 5))), the network's top action (-1: no legal action), the target's top action (-1
+ * where policy_valid is 0).  Both arg-maxima run over the legal actions, NaN compares as -inf, ties go to the lowest
+ * action.  Total: every bit pattern of every input gives defined outputs (NaN allowed).  One wave per row.  HIP build
+ * only. */
+LZ_API int lz_valid_row_metrics(const float* log_p1, const float* log_p2, const float* log_pmc,
+                                const float* value_logits, const uint8_t* legal_mask, const float* policy_target,
+                                const float* value_target, const float* soft_value_target, const float* planes,
+                                int64_t batch, float soft_label_alpha, float* rows /*[batch,12]*/,
+                                int32_t* cls /*[batch,4]*/, void* stream);
+
+/* Sums: acc float64[18,14] += the batch.  Group 0 is every row, groups 1..7 the phases 0..6, groups 8..17 the calibration
+ * bins 0..9 (cls columns 0 and 1; other values belong to group 0 only).  Columns 0..11 are the sums of the row columns,
+ * column 12 the rows counted, column 13 the rows skipped: a row with a non-finite entry among its 12 floats is skipped in
+ * each of its groups.  Association: lane l of 64 adds its rows l, l + 64, ... in order from 0.0, the 64 partial sums are
+ * combined by a butterfly (distance 32, 16, ..., 1), the total is added to acc; all double, identical in both builds.
+ * value float32[batch] and zsum float64[18] are optional, both or neither (LZ_ERR_ARG otherwise): zsum[g] += the value
+ * targets of the rows counted in group g, by the same association (the mean z of the calibration table).
+ * One wave per group; calls accumulate in stream order. */
+LZ_API int lz_valid_reduce(const float* rows /*[batch,12]*/, const int32_t* cls /*[batch,4]*/,
+                           const float* value /*[batch] or NULL*/, int64_t batch, double* acc /*[18,14]*/,
+                           double* zsum /*[18] or NULL*/, void* stream);
+
+/* Classification alone: phase_bin int32[batch,2] = {phase of planes float32[batch,11,6,6], calibration bin of
+ * v_hat[i * v_hat_stride]} by the rules above (v_hat_stride >= 1, in floats: 12 for column 7 of a rows array).  Meant for
+ * CPU arrays (the host build); the device build exports it because both libraries carry every declared symbol, and
+ * lz_valid_row_metrics writes the same two values itself. */
+LZ_API int lz_valid_classify(const float* planes, const float* v_hat, int64_t v_hat_stride, int64_t batch,
+                             int32_t* phase_bin /*[batch,2]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,11 @@ gathered records enter the window without being expanded.  Each iteration's log 
 default) is the code path and the JSON line without a window.
 
 With one process everything runs on the same GPU (self-play, then training; --overlap has nothing to overlap).
+Validation (--validate 1): on the trainer rank generation i is evaluated with the weights as they stand before the
+training pass on it (test-then-train: the rows are unseen, `liuzhou_amd/validation.py`), in both schedules; with a window
+the rows are read from the ring.  The log entry of the iteration that trains on the generation gains `validation`.  With
+--validate 0 (the default) nothing is imported, allocated or launched and the JSON line has the keys it always had.
+
 Tests rehearse the multi-rank branches with several ranks on ONE GPU: `LZ_DIST_BACKEND=gloo LZ_SHARE_GPU=1` (RCCL
 refuses two ranks per device; the gather then stages its records through host memory, same protocol and kernels).
 One JSON line per run (printed by the trainer rank).
@@ -52,7 +57,7 @@ def _digest_pack(wfrag: torch.Tensor, fparams: torch.Tensor) -> int:
     return int(((a * (ia % 8191 + 1)).sum() + (b % 1000003 * (ib % 8191 + 1)).sum()).item())
 
 
-def main() -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iterations", type=int, default=3)
     ap.add_argument("--games-per-gpu", type=int, default=256)
@@ -83,9 +88,39 @@ def main() -> int:
     ap.add_argument("--check-digests", type=int, default=1,
                     help="after every hand-off compare an exact digest of each player's packed device weights with the "
                          "trainer's (outside the timed part of the iteration)")
-    args = ap.parse_args()
-    if args.replay_generations > 1 and args.dedup_positions != "off":  # every rank refuses, before any collective
+    ap.add_argument("--validate", type=int, default=0, choices=(0, 1),
+                    help="1: before every training pass the trainer rank evaluates the generation it is about to train on "
+                         "with the weights as they stand (liuzhou_amd/validation.py); the iteration's log entry gains "
+                         "`validation`")
+    ap.add_argument("--validate-evaluator", default=None, choices=("module", "fused"),
+                    help="forward pass of --validate 1: the PyTorch module under autocast (default) or the fp16 kernels "
+                         "self-play runs")
+    return ap
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """Every rank parses and refuses the same way, before any collective."""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.replay_generations > 1 and args.dedup_positions != "off":
         ap.error("--replay-generations > 1 does not merge duplicate positions: leave --dedup-positions off")
+    if not args.validate and args.validate_evaluator is not None:
+        ap.error("--validate-evaluator needs --validate 1")
+    return args
+
+
+def iteration_entry(base: dict, *, replay=None, window_on: bool = False, validation=None, validate_on: bool = False) -> dict:
+    """An iteration's log entry: `replay` only with a window, `validation` only with --validate 1."""
+    entry = dict(base)
+    if window_on:
+        entry["replay"] = replay
+    if validate_on:
+        entry["validation"] = validation
+    return entry
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     backend = os.environ.get("LZ_DIST_BACKEND", "nccl")
@@ -143,23 +178,36 @@ def main() -> int:
                                              min(args.max_game_plies, 144))   # a game records at most 144 rows
         window = ReplayWindow(dev, max_generations=args.replay_generations, capacity_rows=rows)
 
+    def validate(model, data, generation):
+        """Generation `generation` on the weights as they stand, before the training pass on it.  With a window the rows
+        are read from the ring (the generation has just been added), else from the tensors."""
+        from liuzhou_amd.validation import validate_network
+        n_new = int(data.shape[0]) if isinstance(data, torch.Tensor) else int(data.num_samples)
+        if n_new <= 0:
+            return None
+        source = (window, [generation]) if window is not None else data
+        return validate_network(model, source, batch_size=args.batch_size, evaluator=args.validate_evaluator or "module",
+                                soft_label_alpha=args.soft_label_alpha, device=str(dev))
+
     def train_window(model, data, generation):
         n_new = int(data.shape[0]) if isinstance(data, torch.Tensor) else int(data.num_samples)
         if n_new > 0:
             window.add_generation(data, generation=generation)
+        validation = validate(model, data, generation) if args.validate else None
         model, metrics = train_network_from_window(model, window, batch_size=args.batch_size, epochs=args.epochs,
                                                    lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),
                                                    replay_budget_per_generation=args.replay_budget, replay_seed=0)
         model.eval()
         e = metrics["epoch_stats"][-1] if metrics and metrics.get("epoch_stats") else {}
         return model, int(metrics.get("num_samples", 0)), {"avg_loss": e.get("avg_loss"), "samples_stepped": int(e.get("samples", 0)),
-                                                           "replay": metrics.get("replay_window")}
+                                                           "replay": metrics.get("replay_window"), "validation": validation}
 
     def train(model, data, generation=None):
         if window is not None:
             return train_window(model, data, generation)
         dedup = ({"dedup_positions": args.dedup_positions, "dedup_max_copies": args.dedup_max_copies}
                  if args.dedup_positions != "off" else {})
+        validation = validate(model, data, generation) if args.validate else None
         model, metrics = train_network_from_tensors(model, data, batch_size=args.batch_size, epochs=args.epochs,
                                                     lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),
                                                     **dedup)
@@ -167,7 +215,8 @@ def main() -> int:
         e = metrics["epoch_stats"][-1] if metrics and metrics.get("epoch_stats") else {}
         # rows handed to the trainer; `samples_stepped` (epoch_stats.samples) can be lower: the AMP scaler skips the
         # batches whose scaled gradients overflow, exactly as the reference's loop does (train_bridge.py:388-420)
-        return model, int(metrics.get("num_samples", 0)), {"avg_loss": e.get("avg_loss"), "samples_stepped": int(e.get("samples", 0))}
+        return model, int(metrics.get("num_samples", 0)), {"avg_loss": e.get("avg_loss"), "samples_stepped": int(e.get("samples", 0)),
+                                                           "validation": validation}
 
     model = ChessNet(**MODEL_CONFIGS[args.model])
     stable_resnet_init(model, 20260314)                               # MODEL_INIT_SEED (big_train_v1.sh:24)
@@ -260,15 +309,16 @@ def main() -> int:
             same = len(set(every)) == 1
             digests_seen.append(every[trainer])
         if trains:
-            log.append({"iteration": it, "positions": int(n), "self_play_sec": round(play_max, 3),
-                        "gather_sec": round(gather_max, 3), "train_sec": round(t_train, 3),
-                        "handoff_sec": round(t_handoff, 3), "iteration_sec": round(t_total, 3),
-                        "positions_per_sec": round(n / max(t_total, 1e-9), 1),
-                        "train_samples": trained, "avg_loss": (loss or {}).get("avg_loss"),
-                        "samples_stepped": (loss or {}).get("samples_stepped"), "weights_equal_on_all_ranks": same,
-                        "weights_digest": digests_seen[-1] if digests_seen else None, "net_check": net_check})
-            if window is not None:
-                log[-1]["replay"] = (loss or {}).get("replay")
+            log.append(iteration_entry(
+                {"iteration": it, "positions": int(n), "self_play_sec": round(play_max, 3),
+                 "gather_sec": round(gather_max, 3), "train_sec": round(t_train, 3),
+                 "handoff_sec": round(t_handoff, 3), "iteration_sec": round(t_total, 3),
+                 "positions_per_sec": round(n / max(t_total, 1e-9), 1),
+                 "train_samples": trained, "avg_loss": (loss or {}).get("avg_loss"),
+                 "samples_stepped": (loss or {}).get("samples_stepped"), "weights_equal_on_all_ranks": same,
+                 "weights_digest": digests_seen[-1] if digests_seen else None, "net_check": net_check},
+                replay=(loss or {}).get("replay"), window_on=window is not None,
+                validation=(loss or {}).get("validation"), validate_on=bool(args.validate)))
     tail = None
     if trains and overlap and pending is not None:                     # the last generation, nothing left to overlap with
         t0 = time.perf_counter()
@@ -276,8 +326,8 @@ def main() -> int:
         torch.cuda.synchronize(dev)
         tail = {"train_samples": trained, "avg_loss": (loss or {}).get("avg_loss"),
                 "samples_stepped": (loss or {}).get("samples_stepped"), "train_sec": round(time.perf_counter() - t0, 3)}
-        if window is not None:
-            tail["replay"] = (loss or {}).get("replay")
+        tail = iteration_entry(tail, replay=(loss or {}).get("replay"), window_on=window is not None,
+                               validation=(loss or {}).get("validation"), validate_on=bool(args.validate))
     if trains:
         steady = log[1:] if len(log) > 1 else log
         out = {"workload": f"C5 staged loop: {max(1, world - 1)} self-play GPU(s) x {args.games_per_gpu} games, "
