@@ -1725,24 +1725,6 @@ int lz_tree_begin(const LzTreeDesc* d, void* stream) {
     return st();
 }
 
-// the select kernel of the descriptor's root-level rule (forced playouts, Gumbel or neither), with or without the solver
-extern "C++" template <bool SOLVER>
-static void tree_select_launch(const LzTreeDesc* d, void* stream) {
-    const Tree t = no_share(make_tree(d));
-    const dim3 grid(gw(d->num_games)), block(kBlock);
-    if (shape_set(d)) {                                            // (shape_check refused a Gumbel descriptor)
-        if (forced_set(d))
-            hipLaunchKernelGGL((tree_select_kernel<true, false, SOLVER, true>), grid, block, 0, as_stream(stream), t, make_forced(d), GumbelArgs{}, make_shape(d));
-        else
-            hipLaunchKernelGGL((tree_select_kernel<false, false, SOLVER, true>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, GumbelArgs{}, make_shape(d));
-    } else if (gumbel_set(d))
-        hipLaunchKernelGGL((tree_select_kernel<false, true, SOLVER>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, make_gumbel(d), ShapeArgs{});
-    else if (forced_set(d))
-        hipLaunchKernelGGL((tree_select_kernel<true, false, SOLVER>), grid, block, 0, as_stream(stream), t, make_forced(d), GumbelArgs{}, ShapeArgs{});
-    else
-        hipLaunchKernelGGL((tree_select_kernel<false, false, SOLVER>), grid, block, 0, as_stream(stream), t, ForcedArgs{}, GumbelArgs{}, ShapeArgs{});
-}
-
 int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (!tree_ok(d)) return LZ_ERR_ARG;
     if (cap_set(d)) return LZ_ERR_UNSUPPORTED;                     // the playout cap: lz_tree_search only
@@ -1751,23 +1733,41 @@ int lz_tree_select(const LzTreeDesc* d, void* stream) {
     if (const int rc = solver_check(d)) return rc;
     if (const int rc = shape_check(d)) return rc;
     if (d->num_games == 0) return LZ_OK;
-    if (solver_set(d)) tree_select_launch<true>(d, stream);
-    else tree_select_launch<false>(d, stream);
+    // the select kernel of the descriptor's root-level rule (forced playouts, Gumbel or neither), solver and PUCT shape
+    const TreeOptions o = make_options(d);
+    const Tree t = no_share(make_tree(d));
+    with_options<kOptAll & ~kOptCap>(option_bits(o), [&](auto opt) {
+        constexpr unsigned O = decltype(opt)::value;
+        hipLaunchKernelGGL((tree_select_kernel<has_option(O, kOptForced), has_option(O, kOptGumbel), has_option(O, kOptSolver),
+                                               has_option(O, kOptShape)>),
+                           dim3(gw(d->num_games)), dim3(kBlock), 0, as_stream(stream), t, o.forced, o.gumbel, o.shape);
+        return LZ_OK;
+    });
     return st();
 }
 
-// the stand-alone expand (+ backup) kernel of a step, with or without the solver
-extern "C++" template <bool SOLVER>
-static void tree_expand_launch(const Tree& t, int is_root, const float* lp1, const float* lp2, const float* lpmc,
-                               const float* priors220, const float* values, const float* noise, int64_t noise_stride,
-                               float epsilon, const SolverArgs& sv, void* stream) {
+extern "C++" {
+// What a tree step reads besides the tree and the options: the evaluator's outputs (priors220: the dense priors of
+// lz_tree_expand's callers, nullptr in the searches), the Dirichlet mix of a root step, the stream.
+struct StepArgs {
+    const float *lp1, *lp2, *lpmc, *priors220, *values, *noise;
+    int64_t noise_stride;
+    float epsilon;
+    void* stream;
+};
+
+// the stand-alone expand (+ backup) kernel behind launch `step`; only a root step gets the noise
+template <bool COMPACT, bool CAP, bool SOLVER>
+static void tree_expand_launch(const Tree& t, bool is_root, const StepArgs& a, int step, const TreeOptions& o) {
+    const dim3 grid(gw(t.B)), block(kBlock);
     if (is_root)
-        hipLaunchKernelGGL((tree_expand_kernel<true, false, false, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                           t, lp1, lp2, lpmc, priors220, values, noise, (int)noise_stride, epsilon, -1, CapArrays{}, sv);
+        hipLaunchKernelGGL((tree_expand_kernel<true, COMPACT, CAP, SOLVER>), grid, block, 0, as_stream(a.stream), t, a.lp1, a.lp2,
+                           a.lpmc, a.priors220, a.values, a.noise, (int)a.noise_stride, a.epsilon, step, o.cap, o.solver);
     else
-        hipLaunchKernelGGL((tree_expand_kernel<false, false, false, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                           t, lp1, lp2, lpmc, priors220, values, (const float*)nullptr, 0, 0.f, -1, CapArrays{}, sv);
+        hipLaunchKernelGGL((tree_expand_kernel<false, COMPACT, CAP, SOLVER>), grid, block, 0, as_stream(a.stream), t, a.lp1, a.lp2,
+                           a.lpmc, a.priors220, a.values, (const float*)nullptr, 0, 0.f, step, o.cap, o.solver);
 }
+}  // extern "C++"
 
 int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const float* lp2, const float* lpmc,
                    const float* priors220, const float* values, const float* noise, int64_t noise_stride,
@@ -1778,17 +1778,20 @@ int lz_tree_expand(const LzTreeDesc* d, int is_root, const float* lp1, const flo
     if (const int rc = gumbel_check(d)) return rc;
     if (const int rc = solver_check(d)) return rc;
     if (d->num_games == 0) return LZ_OK;
+    const TreeOptions o = make_options(d);
     const Tree t = no_share(make_tree(d));
-    if (is_root && gumbel_set(d)) noise = nullptr;                 // a Gumbel search never mixes Dirichlet noise in
-    if (solver_set(d))
-        tree_expand_launch<true>(t, is_root, lp1, lp2, lpmc, priors220, values, noise, noise_stride, epsilon, make_solver(d), stream);
-    else
-        tree_expand_launch<false>(t, is_root, lp1, lp2, lpmc, priors220, values, noise, noise_stride, epsilon, SolverArgs{}, stream);
-    if (is_root && gumbel_set(d))
-        hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, make_gumbel(d),
+    const bool gumbel_root = is_root && o.gumbel_set;              // a Gumbel search never mixes Dirichlet noise in
+    const StepArgs a{lp1, lp2, lpmc, priors220, values, gumbel_root ? nullptr : noise, noise_stride, epsilon, stream};
+    with_options<kOptSolver>(option_bits(o) & kOptSolver, [&](auto opt) {   // of the options, the expansion knows the solver alone
+        tree_expand_launch<false, false, has_option(decltype(opt)::value, kOptSolver)>(t, is_root != 0, a, -1, o);
+        return LZ_OK;
+    });
+    if (gumbel_root)
+        hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, o.gumbel,
                            (const uint8_t*)nullptr);
     return st();
 }
+
 
 extern "C++" template <bool PRUNE>
 static int tree_finish_impl(const LzTreeDesc* d, const float* temperatures, const float* target_temperatures,
@@ -1957,121 +1960,73 @@ static bool tree_gather_path(const LzNetDesc* net, int64_t B) {
     return (B + samples - 1) / samples > max_blocks && !split_step(B);
 }
 
+extern "C++" {
+// The tree of a whole search.  Shared leaves (position index) only in the one-wave step, whose evaluator is the search's
+// network: its outputs are a function of the packed state alone.  The step-by-step entry points (external evaluators) and
+// the two-wave split step (where the descent runs beside the expansion that inserts into the index) keep the index but do
+// not look it up.  With the solver or the PUCT shape the step is always the one-wave kernel (tree_step_launch), so the
+// index is looked up at every launch size.
+static Tree search_tree(const LzTreeDesc* d, const TreeOptions& o) {
+    return !o.solver_set && !o.shape_set && split_step(d->num_games) ? no_share(make_tree(d)) : make_tree(d);
+}
+
+// The tree step behind network launch s of a search of `sims` simulations, and the one place that chooses its kernel:
+//   s == sims : expand + backup alone (nothing is left to select)
+//   s == 0    : the root's expansion, with the Dirichlet mix, + the first selection
+//   otherwise : expand + backup of simulation s + selection of simulation s + 1, on two waves per game where the launch
+//               leaves room for them (split_step) -- the solver and the PUCT shape have no two-wave form -- else on one
+// O: the option bits (with_options), which pick the kernels' CAP / FORCED / GUMBEL / SOLVER / SHAPE forms; the launch
+// sequence is the same for all of them.  COMPACT: the evaluator's rows are those of the compact list (Tree::live_row).
+template <unsigned O, bool COMPACT>
+static void tree_step_launch(const Tree& t, const TreeOptions& o, const StepArgs& a, int64_t s, int64_t sims) {
+    constexpr bool CAP = has_option(O, kOptCap), FORCED = has_option(O, kOptForced), GUMBEL = has_option(O, kOptGumbel),
+                   SOLVER = has_option(O, kOptSolver), SHAPE = has_option(O, kOptShape);
+    const dim3 grid(gw(t.B)), block(kBlock);
+    if (s == sims)
+        tree_expand_launch<COMPACT, CAP, SOLVER>(t, s == 0, a, (int)s, o);
+    else if (s == 0)
+        hipLaunchKernelGGL((tree_expand_select_kernel<true, COMPACT, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), grid, block, 0,
+                           as_stream(a.stream), t, a.lp1, a.lp2, a.lpmc, a.values, a.noise, (int)a.noise_stride, a.epsilon, (int)s,
+                           o.cap, o.forced, o.gumbel, o.solver, o.shape);
+    else if (!SOLVER && !SHAPE && split_step(t.B))
+        hipLaunchKernelGGL((tree_expand_select_split_kernel<COMPACT, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), block, 0,
+                           as_stream(a.stream), t, a.lp1, a.lp2, a.lpmc, a.values, (int)s, o.cap, o.forced, o.gumbel);
+    else
+        hipLaunchKernelGGL((tree_expand_select_kernel<false, COMPACT, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), grid, block, 0,
+                           as_stream(a.stream), t, a.lp1, a.lp2, a.lpmc, a.values, (const float*)nullptr, 0, 0.f, (int)s,
+                           o.cap, o.forced, o.gumbel, o.solver, o.shape);
+}
+
 // Whole search of one move, enqueued from C++ (no Python in the simulation loop, hipGraph-capturable):
-//   begin -> [net -> expand_root + select] -> (sims-1) x [net -> expand+backup + select] -> net -> expand+backup
-// `continue_trees`: the roots were prepared by lz_tree_advance (kept subtrees or fresh roots), so no begin.
-// CAP: the kernels of the playout cap (LzTreeDesc.sim_budget / root_noise), the same launch sequence.
-// FORCED: the select kernels of forced playouts (LzTreeDesc.forced_k), the same launch sequence.
-// GUMBEL: the kernels of the Gumbel root search (LzTreeDesc.gumbel_*), the same launch sequence.
-// SOLVER: the kernels of the MCTS-Solver (LzTreeDesc.solver), the same launch sequence with the one-wave step throughout.
-// SHAPE: the select steps of first-play urgency and the visit-scaled c (LzTreeDesc.puct_shape), likewise the one-wave step.
-extern "C++" template <bool CAP, bool FORCED, bool GUMBEL = false, bool SOLVER = false, bool SHAPE = false>
-static int tree_search_launch(const LzTreeDesc* d, const Tree& t, const CapArrays& cap, const ForcedArgs& fa, const GumbelArgs& ga, const SolverArgs& sv, const ShapeArgs& sh, const LzNetDesc* net, int64_t sims, float* lp1,
-                              float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
-                              float epsilon, void* stream) {
-    const int64_t B = d->num_games;
-    int rc = LZ_OK;
-    if (t.live_count != nullptr && d->live_count_cap < sims + 2) return LZ_ERR_ARG;
-    // gathering launch: the network kernel takes simulation s's live leaves out of leaf_state by their leaf_kind and writes
-    // live_count[s]; outputs lie at the game's own row, so the step kernels are the dense branch's and nothing scans
-    const bool gather = t.live_count != nullptr && tree_gather_path(net, B);
-    // KLD-gain early stopping: the snapshot behind launch 0, a check behind every launch s = k * kld_interval that is not
-    // one of the search's last two (s + 1 < sims: a stop there would save nothing)
-    const bool kld = CAP && kld_set(d);
-    const KldArgs ka = kld ? make_kld(d) : KldArgs{};
-    auto kld_after = [&](int64_t s) {
-        if (kld && s + 1 < sims && s % ka.interval == 0)
-            hipLaunchKernelGGL(tree_kld_check_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, ka, (int)s);
-    };
-    if (t.live_count != nullptr && !gather) {
-        // compact evaluation lists: simulation s evaluates live_count[s] leaves (see LzTreeDesc.live_*)
-        hipLaunchKernelGGL(tree_live_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t, t.live_count);   // the roots
-        for (int64_t s = 0; s <= sims; ++s) {
-            rc = lz_net_forward_packed_counted_f16(net, d->live_state, B, d->live_count + s, lp1, lp2, lpmc, nullptr, values,
-                                                   stream);
-            if (rc) return rc;
-            if (s == sims) {
-                if (s == 0)
-                    hipLaunchKernelGGL((tree_expand_kernel<true, true, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                       lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, cap, sv);
-                else
-                    hipLaunchKernelGGL((tree_expand_kernel<false, true, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                       lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap, sv);
-            } else if (s == 0) {
-                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga, sv, sh);
-            } else {
-                (void)lz_prof_aux_begin(0, stream);
-                if (!SOLVER && !SHAPE && split_step(t.B))
-                    hipLaunchKernelGGL((tree_expand_select_split_kernel<true, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), dim3(kBlock), 0,
-                                       as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, cap, fa, ga);
-                else
-                    hipLaunchKernelGGL((tree_expand_select_kernel<false, true, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                       t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv, sh);
-                (void)lz_prof_aux_end(0, stream, B);
-            }
-            kld_after(s);
-            if (s < sims)                                           // the leaves of simulation s + 1
-                hipLaunchKernelGGL(tree_live_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t,
-                                   t.live_count + (s + 1));
-        }
-        if (GUMBEL && sims == 0)                                    // a search of the root step alone: its snapshot
-            hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, ga, cap.root_noise);
-        return st();
-    }
+//   [net -> expand_root + select] -> (sims-1) x [net -> expand+backup + select] -> net -> expand+backup
+// net(s) enqueues the network launch of simulation s and returns its code; scan(s) enqueues what lays out the evaluation
+// list of simulation s, or nothing where the launch needs no list.  `prof`: the non-root select steps are bracketed for
+// the profile (no-ops unless lz_prof_enable(1), never in a capture).
+// KLD-gain early stopping: the snapshot behind launch 0, a check behind every launch s = k * kld_interval that is not one
+// of the search's last two (s + 1 < sims: a stop there would save nothing), before the scan that reads the budgets.
+template <unsigned O, bool COMPACT, class Net, class Scan>
+static int tree_search_launch(const Tree& t, const TreeOptions& o, const StepArgs& a, int64_t sims, bool prof, Net&& net,
+                              Scan&& scan) {
+    const dim3 grid(gw(t.B)), block(kBlock);
+    const bool kld = has_option(O, kOptCap) && o.kld_set;
+    scan(0);                                                        // the roots
     for (int64_t s = 0; s <= sims; ++s) {
-        rc = gather ? lz_net_forward_packed_gather_f16(net, d->leaf_state, t.leaf_kind, B, d->live_count + s, lp1, lp2, lpmc,
-                                                       nullptr, values, stream)
-                    : lz_net_forward_packed_f16(net, d->leaf_state, B, lp1, lp2, lpmc, nullptr, values, stream);
-        if (rc) return rc;
-        if (s == sims) {   // last simulation: nothing left to select
-            if (s == 0)
-                hipLaunchKernelGGL((tree_expand_kernel<true, false, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                                   lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, cap, sv);
-            else
-                hipLaunchKernelGGL((tree_expand_kernel<false, false, CAP, SOLVER>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1, lp2,
-                                   lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, cap, sv);
-        } else if (s == 0) {
-            hipLaunchKernelGGL((tree_expand_select_kernel<true, false, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                               lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, cap, fa, ga, sv, sh);
-        } else {
-            (void)lz_prof_aux_begin(0, stream);                      // no-ops unless lz_prof_enable(1) (never in a capture)
-            if (!SOLVER && !SHAPE && split_step(t.B))
-                hipLaunchKernelGGL((tree_expand_select_split_kernel<false, CAP, FORCED, GUMBEL>), dim3(gw2(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, (int)s, cap, fa, ga);
-            else
-                hipLaunchKernelGGL((tree_expand_select_kernel<false, false, CAP, FORCED, GUMBEL, SOLVER, SHAPE>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, lp1,
-                                   lp2, lpmc, values, nullptr, 0, 0.f, (int)s, cap, fa, ga, sv, sh);
-            (void)lz_prof_aux_end(0, stream, B);
-        }
-        kld_after(s);
+        if (const int rc = net(s)) return rc;
+        const bool bracket = prof && 0 < s && s < sims;
+        if (bracket) (void)lz_prof_aux_begin(0, a.stream);
+        tree_step_launch<O, COMPACT>(t, o, a, s, sims);
+        if (bracket) (void)lz_prof_aux_end(0, a.stream, t.B);
+        if (kld && s + 1 < sims && s % o.kld.interval == 0)
+            hipLaunchKernelGGL(tree_kld_check_kernel, grid, block, 0, as_stream(a.stream), t, o.kld, (int)s);
+        if (s < sims) scan(s + 1);                                  // the leaves of simulation s + 1
     }
-    if (GUMBEL && sims == 0)
-        hipLaunchKernelGGL(gumbel_root_kernel, dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t, ga, cap.root_noise);
+    if (has_option(O, kOptGumbel) && sims == 0)                     // a search of the root step alone: its snapshot
+        hipLaunchKernelGGL(gumbel_root_kernel, grid, block, 0, as_stream(a.stream), t, o.gumbel, o.cap.root_noise);
     return st();
 }
+}  // extern "C++"
 
-// tree_search_launch for the descriptor's options: cap x (forced | Gumbel | neither), with or without the solver, with or
-// without the PUCT shape (never with Gumbel: shape_check)
-extern "C++" template <bool SOLVER, bool SHAPE = false>
-static int tree_search_dispatch(const LzTreeDesc* d, const Tree& t, const SolverArgs& sv, const ShapeArgs& sh, const LzNetDesc* net, int64_t sims,
-                                float* lp1, float* lp2, float* lpmc, float* values, const float* noise,
-                                int64_t noise_stride, float epsilon, void* stream) {
-    if (!SHAPE && gumbel_set(d)) {                                 // (a Gumbel search never mixes Dirichlet noise in)
-        if (cap_set(d))
-            return tree_search_launch<true, false, !SHAPE, SOLVER, false>(d, t, make_cap(d), ForcedArgs{}, make_gumbel(d), sv, sh, net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
-        return tree_search_launch<false, false, !SHAPE, SOLVER, false>(d, t, CapArrays{}, ForcedArgs{}, make_gumbel(d), sv, sh, net, sims, lp1, lp2, lpmc, values, nullptr, 0, 0.f, stream);
-    }
-    if (forced_set(d)) {
-        if (cap_set(d))
-            return tree_search_launch<true, true, false, SOLVER, SHAPE>(d, t, make_cap(d), make_forced(d), GumbelArgs{}, sv, sh, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-        return tree_search_launch<false, true, false, SOLVER, SHAPE>(d, t, CapArrays{}, make_forced(d), GumbelArgs{}, sv, sh, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    }
-    if (cap_set(d))
-        return tree_search_launch<true, false, false, SOLVER, SHAPE>(d, t, make_cap(d), ForcedArgs{}, GumbelArgs{}, sv, sh, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    return tree_search_launch<false, false, false, SOLVER, SHAPE>(d, t, CapArrays{}, ForcedArgs{}, GumbelArgs{}, sv, sh, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-}
-
+// `continue_trees`: the roots were prepared by lz_tree_advance (kept subtrees or fresh roots), so no begin.
 static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t sims, float* planes, float* lp1,
                             float* lp2, float* lpmc, float* values, const float* noise, int64_t noise_stride,
                             float epsilon, bool continue_trees, void* stream) {
@@ -2082,22 +2037,35 @@ static int tree_search_impl(const LzTreeDesc* d, const LzNetDesc* net, int64_t s
     if (const int krc = kld_check(d)) return krc;
     const int64_t B = d->num_games;
     if (B == 0) return LZ_OK;
-    int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
+    const int rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
     if (rc) return rc;
     (void)planes;   // the network kernel stages its input straight from the 32-byte packed leaf states
-    // Shared leaves (position index) only in the one-wave step, whose evaluator is this network: its outputs are a
-    // function of the packed state alone.  The step-by-step entry points (external evaluators) and the two-wave split
-    // step (where the descent runs beside the expansion that inserts into the index) keep the index but do not look it up.
-    // with the solver always the one-wave step (so the position index is looked up at every launch size)
-    // ... and likewise with the PUCT shape
-    if (shape_set(d)) {
-        if (solver_set(d))
-            return tree_search_dispatch<true, true>(d, make_tree(d), make_solver(d), make_shape(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-        return tree_search_dispatch<false, true>(d, make_tree(d), SolverArgs{}, make_shape(d), net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    }
-    if (solver_set(d))
-        return tree_search_dispatch<true>(d, make_tree(d), make_solver(d), ShapeArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
-    return tree_search_dispatch<false>(d, split_step(B) ? no_share(make_tree(d)) : make_tree(d), SolverArgs{}, ShapeArgs{}, net, sims, lp1, lp2, lpmc, values, noise, noise_stride, epsilon, stream);
+    const TreeOptions o = make_options(d);
+    const Tree t = search_tree(d, o);
+    if (t.live_count != nullptr && d->live_count_cap < sims + 2) return LZ_ERR_ARG;
+    // compact evaluation lists: simulation s evaluates live_count[s] leaves (see LzTreeDesc.live_*), laid out by the scan
+    // kernel -- or, on the gathering launch, taken by the network kernel itself out of leaf_state by their leaf_kind (it
+    // writes live_count[s]); its outputs lie at the game's own row, so the steps are the dense ones and nothing scans
+    const bool gather = t.live_count != nullptr && tree_gather_path(net, B);
+    const bool lists = t.live_count != nullptr && !gather;
+    StepArgs a{lp1, lp2, lpmc, nullptr, values, noise, noise_stride, epsilon, stream};
+    if (o.gumbel_set) { a.noise = nullptr; a.noise_stride = 0; a.epsilon = 0.f; }   // a Gumbel search never mixes Dirichlet noise in
+    auto net_counted = [&](int64_t s) {
+        return lz_net_forward_packed_counted_f16(net, d->live_state, B, d->live_count + s, lp1, lp2, lpmc, nullptr, values, stream);
+    };
+    auto net_slots = [&](int64_t s) {
+        return gather ? lz_net_forward_packed_gather_f16(net, d->leaf_state, t.leaf_kind, B, d->live_count + s, lp1, lp2, lpmc,
+                                                         nullptr, values, stream)
+                      : lz_net_forward_packed_f16(net, d->leaf_state, B, lp1, lp2, lpmc, nullptr, values, stream);
+    };
+    auto scan = [&](int64_t s) {
+        hipLaunchKernelGGL(tree_live_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t, t.live_count + s);
+    };
+    return with_options<kOptAll>(option_bits(o), [&](auto opt) {
+        constexpr unsigned O = decltype(opt)::value;
+        return lists ? tree_search_launch<O, true>(t, o, a, sims, true, net_counted, scan)
+                     : tree_search_launch<O, false>(t, o, a, sims, true, net_slots, [](int64_t) {});
+    });
 }
 
 // lz_net.hip (internal): the checks of lz_net_forward_packed_multi_f16 on its networks
@@ -2116,8 +2084,6 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
     if (gumbel_set(d)) return LZ_ERR_UNSUPPORTED;                  // the Gumbel root search: likewise
     if (solver_set(d)) return LZ_ERR_UNSUPPORTED;                  // the MCTS-Solver: likewise
     if (const int hrc = shape_check(d)) return hrc;
-    const bool shaped = shape_set(d);                               // the PUCT shape: the one-wave step's two COMPACT forms
-    const ShapeArgs sh = shaped ? make_shape(d) : ShapeArgs{};
     int rc = lz_net_multi_validate(nets, num_nets);
     if (rc) return rc;
     const int64_t B = d->num_games, G = d->seg_games;
@@ -2126,46 +2092,23 @@ static int tree_search_multi_impl(const LzTreeDesc* d, const LzNetDesc* const* n
     if (d->sym_mode != 0) return LZ_ERR_UNSUPPORTED;                // symmetric evaluation: one network per search only
     rc = continue_trees ? LZ_OK : lz_tree_begin(d, stream);
     if (rc) return rc;
-    const Tree t = !shaped && split_step(B) ? no_share(make_tree(d)) : make_tree(d);
+    const TreeOptions o = make_options(d);                          // of the options, only the PUCT shape gets here
+    const Tree t = search_tree(d, o);
+    const StepArgs a{lp1, lp2, lpmc, nullptr, values, noise, noise_stride, epsilon, stream};
     const int64_t R = num_nets + 1;
+    auto net = [&](int64_t s) {
+        return lz_net_forward_packed_multi_f16(nets, num_nets, d->live_state, B, d->seg_off + s * R, lp1, lp2, lpmc, nullptr,
+                                               values, stream);
+    };
     auto scan = [&](int64_t s) {
         hipLaunchKernelGGL(tree_live_scan_seg_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), t, (int)G, num_nets,
                            t.live_count + s, reinterpret_cast<long long*>(d->seg_off + s * R));
     };
-    scan(0);                                                        // the roots
-    for (int64_t s = 0; s <= sims; ++s) {
-        rc = lz_net_forward_packed_multi_f16(nets, num_nets, d->live_state, B, d->seg_off + s * R, lp1, lp2, lpmc, nullptr,
-                                             values, stream);
-        if (rc) return rc;
-        if (s == sims) {
-            if (s == 0)
-                hipLaunchKernelGGL((tree_expand_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                   lp1, lp2, lpmc, (const float*)nullptr, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, SolverArgs{});
-            else
-                hipLaunchKernelGGL((tree_expand_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream), t,
-                                   lp1, lp2, lpmc, (const float*)nullptr, values, (const float*)nullptr, 0, 0.f, (int)s, CapArrays{}, SolverArgs{});
-        } else if (shaped) {
-            if (s == 0)
-                hipLaunchKernelGGL((tree_expand_select_kernel<true, true, false, false, false, false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{}, sh);
-            else
-                hipLaunchKernelGGL((tree_expand_select_kernel<false, true, false, false, false, false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{}, sh);
-        } else if (s == 0) {
-            hipLaunchKernelGGL((tree_expand_select_kernel<true, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                               t, lp1, lp2, lpmc, values, noise, (int)noise_stride, epsilon, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{}, ShapeArgs{});
-        } else {
-            if (split_step(t.B))
-                hipLaunchKernelGGL((tree_expand_select_split_kernel<true>), dim3(gw2(t.B)), dim3(kBlock), 0,
-                                   as_stream(stream), t, lp1, lp2, lpmc, values, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{});
-            else
-                hipLaunchKernelGGL((tree_expand_select_kernel<false, true>), dim3(gw(t.B)), dim3(kBlock), 0, as_stream(stream),
-                                   t, lp1, lp2, lpmc, values, nullptr, 0, 0.f, (int)s, CapArrays{}, ForcedArgs{}, GumbelArgs{}, SolverArgs{}, ShapeArgs{});
-        }
-        if (s < sims) scan(s + 1);                                  // the leaves of simulation s + 1
-    }
-    return st();
+    return with_options<kOptShape>(option_bits(o), [&](auto opt) {
+        return tree_search_launch<decltype(opt)::value, true>(t, o, a, sims, false, net, scan);
+    });
 }
+
 
 #ifdef LZ_EXP_TREE_STAMPS
 LZ_API int lz_exp_tree_stamps(unsigned long long* out32, int reset) {

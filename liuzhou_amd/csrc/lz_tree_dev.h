@@ -7,6 +7,7 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "lz_rng.h"
 #include "lz_soa.h"
@@ -1266,6 +1267,45 @@ inline int kld_check(const LzTreeDesc* d) {
 inline KldArgs make_kld(const LzTreeDesc* d) {
     return KldArgs{d->kld_threshold, d->kld_interval, d->kld_min_sims, d->kld_snapshot, d->kld_budget,
                    reinterpret_cast<long long*>(d->kld_stops), reinterpret_cast<long long*>(d->kld_saved), d->kld_trace};
+}
+// The descriptor's options, read once per entry point (after its checks): the switches, and for each the record its kernels
+// take -- default-constructed when the switch is off, so that a launch site passes all of them whatever the options.
+struct TreeOptions {
+    bool cap_set, forced_set, gumbel_set, solver_set, shape_set, kld_set;
+    CapArrays cap; ForcedArgs forced; GumbelArgs gumbel; SolverArgs solver; ShapeArgs shape; KldArgs kld;
+};
+inline TreeOptions make_options(const LzTreeDesc* d) {
+    TreeOptions o{cap_set(d), forced_set(d), gumbel_set(d), solver_set(d), shape_set(d), kld_set(d), {}, {}, {}, {}, {}, {}};
+    if (o.cap_set) o.cap = make_cap(d);
+    if (o.forced_set) o.forced = make_forced(d);
+    if (o.gumbel_set) o.gumbel = make_gumbel(d);
+    if (o.solver_set) o.solver = make_solver(d);
+    if (o.shape_set) o.shape = make_shape(d);
+    if (o.kld_set) o.kld = make_kld(d);
+    return o;
+}
+// The switches that are template parameters of the tree kernels, as bits (KLD stopping has a kernel of its own instead).
+enum : unsigned { kOptCap = 1, kOptForced = 2, kOptGumbel = 4, kOptSolver = 8, kOptShape = 16, kOptAll = 31 };
+constexpr bool has_option(unsigned bits, unsigned opt) { return (bits & opt) != 0; }
+inline unsigned option_bits(const TreeOptions& o) {
+    return (o.cap_set ? kOptCap : 0u) | (o.forced_set ? kOptForced : 0u) | (o.gumbel_set ? kOptGumbel : 0u) |
+           (o.solver_set ? kOptSolver : 0u) | (o.shape_set ? kOptShape : 0u);
+}
+// The combinations that have kernels: the Gumbel root search goes neither with forced playouts (gumbel_check: two rules for
+// the same root level) nor with the PUCT shape (shape_check).
+constexpr bool options_valid(unsigned bits) { return !(has_option(bits, kOptGumbel) && (bits & (kOptForced | kOptShape))); }
+// Run time -> compile time: f(std::integral_constant<unsigned, M>{}) for the M equal to `bits`, among the valid subsets of
+// ALLOWED (the options the caller has kernels for) -- these are the instantiations, and there are no others.  The entry
+// points' checks refuse every other descriptor before they get here.
+template <unsigned ALLOWED, unsigned M = 0, class F>
+inline int with_options(unsigned bits, F&& f) {
+    if constexpr (M > kOptAll) {
+        return LZ_ERR_UNSUPPORTED;
+    } else {
+        if constexpr ((M & ~ALLOWED) == 0 && options_valid(M))
+            if (bits == M) return f(std::integral_constant<unsigned, M>{});
+        return with_options<ALLOWED, M + 1>(bits, f);
+    }
 }
 bool tree_ok(const LzTreeDesc* d) {
     return d && d->num_games >= 0 && d->node_cap >= 2 && d->path_cap >= 3 &&

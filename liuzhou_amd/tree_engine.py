@@ -796,34 +796,20 @@ class TreeEngine:
         sample = uniforms is not None if sample_moves is None else bool(sample_moves)
         if force_uniform is not None and force_uniform.dtype != torch.uint8:
             force_uniform = force_uniform.to(torch.uint8)
+        # the arguments the three entry points share; each appends its own outputs and the stream
+        head = (C.byref(self.desc), L.ptr(temperatures), L.ptr(target_temperatures), C.c_float(float(prior_pseudocount)),
+                L.ptr(force_uniform), C.c_int(int(sample)), L.ptr(uniforms), L.ptr(self.policy_dense),
+                L.ptr(self.chosen_index), L.ptr(self.chosen_code), L.ptr(self.chosen_valid), L.ptr(self.terminal_mask),
+                L.ptr(self.root_value), L.ptr(self.child_count), L.ptr(self.child_action), L.ptr(self.child_visits),
+                L.ptr(self.child_prior), L.i64(OUT_CAP))
         if self.gumbel_m > 0:               # Gumbel root search: the plain finish, then pick and target of the Gumbel games
-            with torch.cuda.device(self.device):
-                L.check(L.lib().lz_tree_finish_gumbel(
-                    C.byref(self.desc), L.ptr(temperatures), L.ptr(target_temperatures), C.c_float(float(prior_pseudocount)),
-                    L.ptr(force_uniform), C.c_int(int(sample)), L.ptr(uniforms), L.ptr(self.policy_dense),
-                    L.ptr(self.chosen_index), L.ptr(self.chosen_code), L.ptr(self.chosen_valid), L.ptr(self.terminal_mask),
-                    L.ptr(self.root_value), L.ptr(self.child_count), L.ptr(self.child_action), L.ptr(self.child_visits),
-                    L.ptr(self.child_prior), L.i64(OUT_CAP), L.ptr(self.gumbel["score"]), L.ptr(self.gumbel["vmix"]),
-                    self._stream()), "tree_finish_gumbel")
-            return
-        if (self.forced_k > 0.0) if pruned is None else bool(pruned):   # policy target pruning: the same outputs + N' / the cut
-            with torch.cuda.device(self.device):
-                L.check(L.lib().lz_tree_finish_pruned(
-                    C.byref(self.desc), L.ptr(temperatures), L.ptr(target_temperatures), C.c_float(float(prior_pseudocount)),
-                    L.ptr(force_uniform), C.c_int(int(sample)), L.ptr(uniforms), L.ptr(self.policy_dense),
-                    L.ptr(self.chosen_index), L.ptr(self.chosen_code), L.ptr(self.chosen_valid), L.ptr(self.terminal_mask),
-                    L.ptr(self.root_value), L.ptr(self.child_count), L.ptr(self.child_action), L.ptr(self.child_visits),
-                    L.ptr(self.child_prior), L.i64(OUT_CAP), L.ptr(self.child_target_visits), L.ptr(self.pruned_visits),
-                    self._stream()), "tree_finish_pruned")
-            return
+            name, tail = "tree_finish_gumbel", (L.ptr(self.gumbel["score"]), L.ptr(self.gumbel["vmix"]))
+        elif (self.forced_k > 0.0) if pruned is None else bool(pruned):   # policy target pruning: the same outputs + N' / the cut
+            name, tail = "tree_finish_pruned", (L.ptr(self.child_target_visits), L.ptr(self.pruned_visits))
+        else:
+            name, tail = "tree_finish", ()
         with torch.cuda.device(self.device):
-            L.check(L.lib().lz_tree_finish(C.byref(self.desc), L.ptr(temperatures), L.ptr(target_temperatures),
-                                           C.c_float(float(prior_pseudocount)), L.ptr(force_uniform), C.c_int(int(sample)),
-                                           L.ptr(uniforms),
-                                           L.ptr(self.policy_dense), L.ptr(self.chosen_index), L.ptr(self.chosen_code),
-                                           L.ptr(self.chosen_valid), L.ptr(self.terminal_mask), L.ptr(self.root_value),
-                                           L.ptr(self.child_count), L.ptr(self.child_action), L.ptr(self.child_visits),
-                                           L.ptr(self.child_prior), L.i64(OUT_CAP), self._stream()), "tree_finish")
+            L.check(getattr(L.lib(), "lz_" + name)(*head, *tail, self._stream()), name)
 
     def advance(self, played_action: Optional[torch.Tensor] = None, reset: Optional[torch.Tensor] = None,
                 next_sims: Optional[int] = None) -> None:

@@ -9,12 +9,16 @@ import torch
 
 GAMES, SIMS, MOVES = 70, 24, 3
 DEV = "cuda:0"
-#            name        model      split  graph  playout cap  states
+#            name        model      split  graph  playout cap  states      [further PortableTreeMCTS keywords]
 SCENARIOS = (("plain",    "b6c64",   "0",   True,  False,       "mixed"),
              ("direct",   "b6c64",   "0",   False, False,       "mixed"),
              ("split",    "b10c128", "1",   True,  False,       "mixed"),
              ("cap",      "b6c64",   "0",   True,  True,        "mixed"),
-             ("terminal", "b6c64",   "0",   True,  False,       "terminal"))
+             ("terminal", "b6c64",   "0",   True,  False,       "terminal"),
+             ("forced",   "b6c64",   "0",   True,  False,       "mixed",    dict(forced_playouts_k=2.0)),
+             ("gumbel",   "b6c64",   "0",   True,  False,       "mixed",    dict(gumbel_considered=8)),
+             # a check behind launches 4, 8, ..., 20 of the 24-simulation searches, a stop allowed from the first of them
+             ("kld",      "b6c64",   "0",   True,  True,        "mixed",    dict(kld_stop=(0.02, 4, 4))))
 
 
 def start_states(kind):
@@ -31,7 +35,7 @@ def start_states(kind):
     return {f: np.ascontiguousarray(np.asarray(st[f])[idx]) for f in FIELDS}
 
 
-def run(name, model, split, graph, cap, kind, rec):
+def run(rec, name, model, split, graph, cap, kind, extra=None):
     from liuzhou_amd.net import ChessNet, MODEL_CONFIGS
     from liuzhou_amd.net_hip import FusedNet
     from liuzhou_amd.tree_engine import PortableTreeMCTS
@@ -44,6 +48,7 @@ def run(name, model, split, graph, cap, kind, rec):
               compact_evals=True, use_graph=graph)
     if cap:
         kw.update(fast_simulations=6, full_prob=0.5)
+    kw.update(extra or {})
     mcts = PortableTreeMCTS(net, GAMES, SIMS, DEV, **kw)
     e = mcts.engine
     cur = start_states(kind)
@@ -88,7 +93,7 @@ def run(name, model, split, graph, cap, kind, rec):
 def main():
     rec = {}
     for sc in SCENARIOS:
-        run(*sc, rec)
+        run(rec, *sc)
     np.savez(sys.argv[1], **rec)
     print("ok", len(rec))
 

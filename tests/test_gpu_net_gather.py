@@ -197,11 +197,12 @@ def _same(a, b, prefix):
         assert a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
 
 
-@pytest.mark.parametrize("scenario", ["plain", "split"])
+@pytest.mark.parametrize("scenario", ["plain", "split", "forced", "gumbel"])
 def test_search_on_the_gathering_launch_equals_the_scan_path(children, scenario):
     """70 games, 24 simulations, kept subtrees over 3 moves, LZ_TREE_GATHER=1 against 0: the same trees (every node's state
     and parent, every edge run's visits, value sums, priors; root values, policies and chosen moves after every move) and
     the same live_count[: sims + 1].  "plain": the one-wave step; "split": the two-wave step and the 128-channel network.
+    "forced": forced playouts at the root; "gumbel": the Gumbel root search over 8 considered moves.
     The gathering side never ran the scan (live_row and live_state untouched), the other side did."""
     got, ref = children
     _same(got, ref, scenario)
@@ -223,6 +224,13 @@ def test_search_with_the_playout_cap_on_the_gathering_launch(children):
     assert full > 0 and fast > 0
     c = got["cap.m0.live_count"]
     assert c[8:].max() < c[:6].max()                                 # the fast searches have left
+
+
+def test_search_with_kld_stopping_on_the_gathering_launch(children):
+    """The playout cap's budgets with KLD-gain early stopping on top (a check every 4 simulations): the checks lower the
+    budgets between the launches on both paths alike."""
+    got, ref = children
+    _same(got, ref, "kld")
 
 
 def test_search_of_finished_games_launches_nothing(children):
