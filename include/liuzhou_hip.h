@@ -1021,6 +1021,24 @@ LZ_API int lz_policy_value_loss_fwd_bwd(const float* log_p1, const float* log_p2
                                         float* grad_log_p1, float* grad_log_p2, float* grad_log_pmc,
                                         float* grad_value_logits, void* stream);
 
+/* The same loss with a per-row weight rw = row_weight[b] (float32 [B]): the second instantiation
+ * of the same kernel.  rw multiplies the row's policy weight and its value gradient as an absolute factor;
+ * policy_weight_sum (the sum of the draw weights, without rw) and B stay the denominators:
+ *   terms[b] = {KL_b, draw weight_b * rw, bucket CE_b, WDL aux_b}   (KL, CE and aux do not depend on rw)
+ *   policy gradients scale with grad_scale * draw weight_b * rw / (policy_weight_sum + 1e-8),
+ *   grad_value_logits with (grad_scale / B) * rw.
+ * A weight of 1.0f gives every byte of the unweighted entry's outputs; a weight of 0 and finite inputs give +-0 in
+ * every gradient entry of the row.  Same argument checks (NULL row_weight: LZ_ERR_ARG). */
+LZ_API int lz_policy_value_loss_weighted_fwd_bwd(const float* log_p1, const float* log_p2, const float* log_pmc,
+                                                 const float* value_logits, const uint8_t* legal_mask,
+                                                 const float* policy_target, const float* value_target,
+                                                 const float* soft_value_target, const float* row_weight,
+                                                 int64_t batch, float soft_label_alpha, float anti_draw_penalty,
+                                                 float policy_draw_weight, const float* policy_weight_sum,
+                                                 float grad_scale, float* terms, float* grad_log_p1,
+                                                 float* grad_log_p2, float* grad_log_pmc, float* grad_value_logits,
+                                                 void* stream);
+
 /* ---- compact trajectory records: wire format of the per-iteration gather ---- */
 
 /* A row of the 5-tensor trajectory contract (v1/python/trajectory_buffer.py:11-33; 2 692 B) as an exact 360-byte

@@ -33,13 +33,17 @@ __device__ __forceinline__ int move_dest_cell(int from, int dir) {      // DIREC
     return (nr < 0 || nr > 5 || nc < 0 || nc > 5) ? -1 : nr * 6 + nc;
 }
 
+// WEIGHTED: a per-row weight rw = row_weight[s] multiplies the row's policy weight and its value gradient (absolute
+// multipliers: weight_sum and B stay the denominators the caller chose).  The unweighted instantiation never reads the
+// pointer, which is the last argument so that the kernel arguments in front of it keep their offsets.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kWave * kWavesPerBlock) void policy_value_loss_kernel(
     const float* __restrict__ lp1, const float* __restrict__ lp2, const float* __restrict__ lpm,
     const float* __restrict__ vlogits, const uint8_t* __restrict__ legal, const float* __restrict__ target,
     const float* __restrict__ value, const float* __restrict__ soft, int64_t B, float alpha, float anti_draw,
     float draw_weight, const float* __restrict__ weight_sum, float grad_scale,
     float* __restrict__ terms /*[B,4]: kl, weight, bucket CE, wdl aux*/, float* __restrict__ g1, float* __restrict__ g2,
-    float* __restrict__ gm, float* __restrict__ gv) {
+    float* __restrict__ gm, float* __restrict__ gv, const float* __restrict__ row_weight) {
     __shared__ float s_dc[kWavesPerBlock][256];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -48,7 +52,12 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void policy_value_loss_kern
     float* dc = s_dc[wv];
     const float raw_v = value[s];
     const bool hard_draw = fabsf(raw_v) < 1e-8f;
-    const float w = hard_draw ? draw_weight : 1.0f;
+    float w = hard_draw ? draw_weight : 1.0f;
+    float rw = 1.0f;
+    if constexpr (WEIGHTED) {
+        rw = row_weight[s];                              // wave-uniform, like value[s]
+        w *= rw;
+    }
     const float wn = grad_scale * w / (weight_sum[0] + 1e-8f);
 
     // ---- policy ----
@@ -146,7 +155,8 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void policy_value_loss_kern
     float cev = -(tg0 * (v0 - vlse)) - (has1 ? tg1 * (v1 - vlse) : 0.f);
     cev = lzw::wave_sum(cev);
     const float sm0 = e0 / vs, sm1 = e1 / vs;
-    const float gvs = grad_scale / (float)B;
+    float gvs = grad_scale / (float)B;
+    if constexpr (WEIGHTED) gvs *= rw;
     gv[s * kBins + lane] = (sm0 - tg0) * gvs;
     if (has1) gv[s * kBins + lane + 64] = (sm1 - tg1) * gvs;
     // WDL auxiliary term (reported only).  Bins are classed by torch.linspace(-1, 1, 101) against +-1e-8
@@ -168,6 +178,32 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void policy_value_loss_kern
 
 }  // namespace
 
+namespace {
+
+template <bool WEIGHTED>
+int launch_policy_value_loss(const float* log_p1, const float* log_p2, const float* log_pmc, const float* value_logits,
+                             const uint8_t* legal_mask, const float* policy_target, const float* value_target,
+                             const float* soft_value_target, const float* row_weight, int64_t batch,
+                             float soft_label_alpha, float anti_draw_penalty, float policy_draw_weight,
+                             const float* policy_weight_sum, float grad_scale, float* terms, float* grad_log_p1,
+                             float* grad_log_p2, float* grad_log_pmc, float* grad_value_logits, void* stream) {
+    if (batch < 0) return LZ_ERR_ARG;
+    if (batch == 0) return LZ_OK;
+    if (!log_p1 || !log_p2 || !log_pmc || !value_logits || !legal_mask || !policy_target || !value_target ||
+        !soft_value_target || !policy_weight_sum || !terms || !grad_log_p1 || !grad_log_p2 || !grad_log_pmc ||
+        !grad_value_logits || (WEIGHTED && !row_weight))
+        return LZ_ERR_ARG;
+    const unsigned grid = (unsigned)((batch + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL(policy_value_loss_kernel<WEIGHTED>, dim3(grid), dim3(kWave * kWavesPerBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), log_p1, log_p2, log_pmc, value_logits, legal_mask,
+                       policy_target, value_target, soft_value_target, batch, soft_label_alpha, anti_draw_penalty,
+                       policy_draw_weight, policy_weight_sum, grad_scale, terms, grad_log_p1, grad_log_p2, grad_log_pmc,
+                       grad_value_logits, row_weight);
+    return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
+}
+
+}  // namespace
+
 extern "C" int lz_policy_value_loss_fwd_bwd(const float* log_p1, const float* log_p2, const float* log_pmc,
                                             const float* value_logits, const uint8_t* legal_mask,
                                             const float* policy_target, const float* value_target,
@@ -176,19 +212,25 @@ extern "C" int lz_policy_value_loss_fwd_bwd(const float* log_p1, const float* lo
                                             const float* policy_weight_sum, float grad_scale, float* terms,
                                             float* grad_log_p1, float* grad_log_p2, float* grad_log_pmc,
                                             float* grad_value_logits, void* stream) {
-    if (batch < 0) return LZ_ERR_ARG;
-    if (batch == 0) return LZ_OK;
-    if (!log_p1 || !log_p2 || !log_pmc || !value_logits || !legal_mask || !policy_target || !value_target ||
-        !soft_value_target || !policy_weight_sum || !terms || !grad_log_p1 || !grad_log_p2 || !grad_log_pmc ||
-        !grad_value_logits)
-        return LZ_ERR_ARG;
-    const unsigned grid = (unsigned)((batch + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL(policy_value_loss_kernel, dim3(grid), dim3(kWave * kWavesPerBlock), 0,
-                       reinterpret_cast<hipStream_t>(stream), log_p1, log_p2, log_pmc, value_logits, legal_mask,
-                       policy_target, value_target, soft_value_target, batch, soft_label_alpha, anti_draw_penalty,
-                       policy_draw_weight, policy_weight_sum, grad_scale, terms, grad_log_p1, grad_log_p2, grad_log_pmc,
-                       grad_value_logits);
-    return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
+    return launch_policy_value_loss<false>(log_p1, log_p2, log_pmc, value_logits, legal_mask, policy_target, value_target,
+                                           soft_value_target, nullptr, batch, soft_label_alpha, anti_draw_penalty,
+                                           policy_draw_weight, policy_weight_sum, grad_scale, terms, grad_log_p1,
+                                           grad_log_p2, grad_log_pmc, grad_value_logits, stream);
+}
+
+extern "C" int lz_policy_value_loss_weighted_fwd_bwd(const float* log_p1, const float* log_p2, const float* log_pmc,
+                                                     const float* value_logits, const uint8_t* legal_mask,
+                                                     const float* policy_target, const float* value_target,
+                                                     const float* soft_value_target, const float* row_weight,
+                                                     int64_t batch, float soft_label_alpha, float anti_draw_penalty,
+                                                     float policy_draw_weight, const float* policy_weight_sum,
+                                                     float grad_scale, float* terms, float* grad_log_p1,
+                                                     float* grad_log_p2, float* grad_log_pmc, float* grad_value_logits,
+                                                     void* stream) {
+    return launch_policy_value_loss<true>(log_p1, log_p2, log_pmc, value_logits, legal_mask, policy_target, value_target,
+                                          soft_value_target, row_weight, batch, soft_label_alpha, anti_draw_penalty,
+                                          policy_draw_weight, policy_weight_sum, grad_scale, terms, grad_log_p1,
+                                          grad_log_p2, grad_log_pmc, grad_value_logits, stream);
 }
 
 // ---- compact trajectory records (wire format of the per-iteration gather) ----------------

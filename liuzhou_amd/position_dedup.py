@@ -4,7 +4,8 @@ Every game starts from the empty board, so one iteration's rows hold the same ea
 copy with its own noised visit distribution and its own single-game outcome.  The mean of those targets is what the
 search bought: `merge_duplicate_positions` groups the rows by position (mode "exact") or by position up to the eight
 board symmetries (mode "symmetric") and returns one row per group -- the first member's planes and mask, the members'
-policy, value and soft value averaged in the first member's frame.  `max_copies` M emits a group min(count, M) times.
+policy, value and soft value averaged in the first member's frame.  `max_copies` M emits a group min(count, M) times;
+with `weighting="weight"` a group leaves once and min(count, M) is its row weight instead.
 
 The keys and the merged rows come from the kernels of csrc/lz_dedup.hip for HIP tensors and from the host build of the
 same C ABI for CPU tensors (csrc/lz_dedup_host.cpp); both compile the scalar arithmetic of csrc/lz_dedup.h.  The exact
@@ -20,6 +21,7 @@ import torch
 from . import _lib as L
 
 MODES = ("off", "exact", "symmetric")
+WEIGHTINGS = ("copies", "weight")
 NUM_ACTIONS = 220
 STAT_KEYS = ("rows_in", "rows_out", "groups", "merged_groups", "merged_rows", "largest_group", "not_representable")
 
@@ -37,6 +39,24 @@ def dedup_on(mode, max_copies=1) -> bool:
     if not whole or int(max_copies) < 1:
         raise ValueError(f"dedup_max_copies must be an integer >= 1, got {max_copies!r}")
     return mode != "off"
+
+
+def weighting_on(weighting, mode="off", max_copies=1) -> bool:
+    """Validate `dedup_weighting` (dedup on or off alike) and say whether groups leave once with a row weight."""
+    if not isinstance(weighting, str) or weighting not in WEIGHTINGS:
+        raise ValueError(f"dedup_weighting must be one of {WEIGHTINGS}, got {weighting!r}")
+    if weighting == "weight" and not dedup_on(mode, max_copies):
+        raise ValueError("dedup_weighting='weight' needs dedup_positions 'exact' or 'symmetric': with dedup_positions="
+                         f"{mode!r} there are no groups to weigh")
+    return weighting == "weight"
+
+
+def group_weights(count: torch.Tensor, max_copies: int = 1) -> torch.Tensor:
+    """float64[groups]: the row weight of each merged group before normalisation, min(count, max_copies) -- what
+    `max_copies` copies of the group's row weigh together.  `count` is `info["count"]`."""
+    if isinstance(max_copies, bool) or int(max_copies) != max_copies or int(max_copies) < 1:
+        raise ValueError(f"dedup_max_copies must be an integer >= 1, got {max_copies!r}")
+    return count.to(torch.int64).clamp(max=int(max_copies)).to(torch.float64)
 
 
 def dedup_refusal(mode, max_copies=1, *, policy_draw_weight: float = 1.0, anti_draw_penalty: float = 0.0) -> None:
@@ -110,15 +130,17 @@ def group_rows(keys: torch.Tensor):
 
 
 def merge_duplicate_positions(planes: torch.Tensor, masks: torch.Tensor, policy: torch.Tensor, values: torch.Tensor,
-                              soft: torch.Tensor, *, mode: str, max_copies: int = 1):
+                              soft: torch.Tensor, *, mode: str, max_copies: int = 1, weighting: str = "copies"):
     """((planes, masks, policy, values, soft), info): the rows with duplicate positions merged.
 
     planes float32[n,11,6,6] (or [n,11,36]); masks bool / uint8 [n,220]; policy float32[n,220]; values and soft
     float32[n].  mode "exact" or "symmetric".  Groups leave in the order of their first members, each min(count,
     max_copies) times.  `info` holds the stats (`STAT_KEYS`, "mode", "max_copies"; one host read), `group_of_row`
-    int64[n] and `count` int32[groups]."""
+    int64[n] and `count` int32[groups].  weighting "weight": each group leaves once, and `info` gains "weighting" and
+    "weights" = `group_weights(count, max_copies)`, one per row that leaves."""
     if not dedup_on(mode, max_copies):
         raise ValueError("merge_duplicate_positions needs mode 'exact' or 'symmetric'")
+    weighted = weighting_on(weighting, mode, max_copies)
     copies = int(max_copies)
     pl, mk, n = _rows(planes, masks)
     dev = pl.device
@@ -145,7 +167,7 @@ def merge_duplicate_positions(planes: torch.Tensor, masks: torch.Tensor, policy:
             L.i64(groups), L.ptr(out_planes), L.ptr(out_masks), L.ptr(out_policy), L.ptr(out_values), L.ptr(out_soft),
             L.ptr(count), L.stream_ptr(dev))
     L.check(st, "position_dedup.merge_duplicate_positions")
-    reps = count64.clamp(max=copies)
+    reps = count64.clamp(max=1 if weighted else copies)
     merged = count64 > 1
     zero = torch.zeros((), dtype=torch.int64, device=dev)
     stats = torch.stack([reps.sum(), merged.sum(), (count64 * merged).sum(), count64.max() if groups else zero,
@@ -158,9 +180,12 @@ def merge_duplicate_positions(planes: torch.Tensor, masks: torch.Tensor, policy:
                             "merged_rows": int(stats[2]), "largest_group": int(stats[3]),
                             "not_representable": int(stats[4]), "mode": mode, "max_copies": copies,
                             "group_of_row": group_of_row, "count": count}
+    if weighted:
+        info["weighting"] = "weight"
+        info["weights"] = group_weights(count, copies)
     return outs, info
 
 
 def stats_of(info: Dict[str, Any]) -> Dict[str, Any]:
     """The plain-number part of `info` (what the trainer's metrics carry)."""
-    return {k: info[k] for k in STAT_KEYS + ("mode", "max_copies")}
+    return {k: info[k] for k in STAT_KEYS + ("mode", "max_copies") + (("weighting",) if "weighting" in info else ())}

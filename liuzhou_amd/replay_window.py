@@ -83,18 +83,20 @@ def _draw_seed(seed: int, newest: int, generation: int) -> int:
 
 
 def select_slots(table: GenerationTable, budget_per_old_generation: int, seed: int, device,
-                 generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                 generator: Optional[torch.Generator] = None, return_ages: bool = False):
     """int64 slots of one training pass: every row of the newest generation in row order, then the older generations
     from newest to oldest, `min(count, budget)` rows each, drawn uniformly without replacement and listed in ascending
     row order.  The draw of a generation is seeded by (seed, newest id, its id) on a generator of its own: the default
-    generator's stream is not touched."""
+    generator's stream is not touched.  `return_ages`: (slots, ages), ages int64 -- for every slot, how many generations
+    of the table its generation lies behind the newest (0 for the newest, whether or not the ones between gave rows)."""
     dev = torch.device(device)
     shares = table.shares(budget_per_old_generation)
     if not shares:
-        return torch.zeros((0,), dtype=torch.int64, device=dev)
+        empty = torch.zeros((0,), dtype=torch.int64, device=dev)
+        return (empty, empty.clone()) if return_ages else empty
     gen = generator if generator is not None else torch.Generator(device=dev)
     newest = shares[0][0]
-    parts = []
+    parts, ages = [], []
     for i, (gid, first, count, take) in enumerate(shares):
         if take <= 0:
             continue
@@ -104,7 +106,11 @@ def select_slots(table: GenerationTable, budget_per_old_generation: int, seed: i
             gen.manual_seed(_draw_seed(seed, newest, gid))
             rows = torch.randperm(count, generator=gen, device=dev)[:take].sort().values
         parts.append((rows + first) % table.capacity_rows)
-    return torch.cat(parts)
+        ages.append(i)
+    slots = torch.cat(parts)
+    if not return_ages:
+        return slots
+    return slots, torch.cat([torch.full((int(p.numel()),), a, dtype=torch.int64, device=dev) for p, a in zip(parts, ages)])
 
 
 class ReplayWindow:
@@ -196,8 +202,8 @@ class ReplayWindow:
         return dict(info)
 
     # ---- reading -----------------------------------------------------------------------------------------------------
-    def select(self, budget_per_old_generation: int = 0, seed: int = 0) -> torch.Tensor:
-        return select_slots(self.table, budget_per_old_generation, seed, self.device, self._gen)
+    def select(self, budget_per_old_generation: int = 0, seed: int = 0, return_ages: bool = False):
+        return select_slots(self.table, budget_per_old_generation, seed, self.device, self._gen, return_ages)
 
     def gather(self, slots: torch.Tensor, sym: Optional[torch.Tensor] = None):
         """(planes f32[m,11,6,6], masks bool[m,220], policy f32[m,220], value f32[m], soft f32[m]) of the records at

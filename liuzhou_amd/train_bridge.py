@@ -52,6 +52,7 @@ class _Stepper:
         self.acc = torch.zeros(9, dtype=torch.float64, device=self.dev)
         self.mix_abs_dev = torch.zeros((), dtype=torch.float64, device=self.dev)
         self.batches, self.skip_loss, self.skip_grad = 0, 0, 0
+        self.rw_sum: Optional[torch.Tensor] = None        # sum of the row weights trained on (weighted steps only)
 
     def _conv_mode(self, rows: int):
         """MIOpen searches for convolution kernels the first time it sees a shape: 12 - 20 s for the nominal batch of this
@@ -80,18 +81,20 @@ class _Stepper:
                   f"size runs immediate mode", flush=True)
         return torch.backends.miopen.flags(immediate=True) if (imm and hasattr(torch.backends, "miopen")) else nullcontext()
 
-    def step(self, b_states, b_masks, b_policy, b_values, b_soft) -> bool:
+    def step(self, b_states, b_masks, b_policy, b_values, b_soft, b_weights=None) -> bool:
+        """`b_weights`: float32 [rows], already normalised (row_weights.normalise_row_weights); None: no weights."""
         with self._conv_mode(int(b_states.shape[0])):
-            return self._step(b_states, b_masks, b_policy, b_values, b_soft)
+            return self._step(b_states, b_masks, b_policy, b_values, b_soft, b_weights)
 
-    def _step(self, b_states, b_masks, b_policy, b_values, b_soft) -> bool:
+    def _step(self, b_states, b_masks, b_policy, b_values, b_soft, b_weights=None) -> bool:
         opt, scaler, dev = self.optimizer, self.scaler, self.dev
         opt.zero_grad(set_to_none=True)
         with (torch.amp.autocast("cuda", enabled=True) if self.amp else nullcontext()):
             lp1, lp2, lpm, vlogits = self.train_model(b_states)
         loss, parts = fused_policy_value_loss(lp1, lp2, lpm, vlogits, b_masks, b_policy, b_values, b_soft,
                                               soft_label_alpha=self.alpha, anti_draw_penalty=self.anti_draw,
-                                              policy_draw_weight=self.draw_w)
+                                              policy_draw_weight=self.draw_w,
+                                              **({} if b_weights is None else {"row_weights": b_weights}))
         # ONE host read per step for both finite checks of the reference (train_bridge.py:388-420 reads the loss flag and
         # then one flag per parameter tensor: ~130 device round trips per step).  The backward runs before the read; a
         # non-finite loss makes non-finite gradients, which are thrown away below exactly as if backward had not run
@@ -135,15 +138,20 @@ class _Stepper:
                                  b_soft.abs().mean()]).to(torch.float64)
         self.mix_abs_dev += mixed.abs().mean().to(torch.float64)        # summed on the device, read once per epoch
         self.batches += 1
+        if b_weights is not None:
+            rw = b_weights.sum().to(torch.float64)
+            self.rw_sum = rw if self.rw_sum is None else self.rw_sum + rw
         return True
 
     def epoch_stats(self, epoch: int, extra: Dict[str, Any], more_sums: Optional[List[float]] = None):
         red = torch.cat([self.acc, self.mix_abs_dev.view(1),
                          torch.tensor([float(self.batches), float(self.skip_loss), float(self.skip_grad)] + list(more_sums or []),
-                                      dtype=torch.float64, device=self.dev)])
+                                      dtype=torch.float64, device=self.dev)]
+                        + ([self.rw_sum.view(1)] if self.rw_sum is not None else []))
         if self.ddp:
             dist.all_reduce(red, op=dist.ReduceOp.SUM)
         r = red.tolist()
+        rw_sum = r.pop() if self.rw_sum is not None else None
         seen = int(round(r[5]))
         stats = {"epoch": epoch, "avg_loss": r[0] / max(1, seen), "avg_policy_loss": r[1] / max(1e-8, r[6]),
                  "avg_value_loss": r[2] / max(1, seen), "avg_value_bucket_loss": r[3] / max(1, seen),
@@ -153,6 +161,8 @@ class _Stepper:
                  "skipped_non_finite_loss_batches": int(round(r[11])), "skipped_non_finite_grad_batches": int(round(r[12])),
                  "miopen_nominal_rows": self._nominal_rows, "miopen_immediate_steps": int(self._conv_counts[1]),
                  "miopen_search_mode_steps": int(self._conv_counts[0])}
+        if rw_sum is not None:
+            stats["row_weight_sum"] = rw_sum
         stats.update(extra)
         return stats, r[13:]
 
@@ -228,6 +238,15 @@ def _wrap(model, strategy, dev):
     return model
 
 
+def _weighting_options(fn: str, given: Dict[str, Any], allowed: Dict[str, Any]) -> List[Any]:
+    """The row-weight keywords of a trainer arrive through its `**weighting`: the values of
+    `allowed` (name -> default) in order; any other name is the TypeError of an unknown keyword."""
+    for name in given:
+        if name not in allowed:
+            raise TypeError(f"{fn}() got an unexpected keyword argument {name!r}")
+    return [given.get(name, default) for name, default in allowed.items()]
+
+
 def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_size: int = 512, epochs: int = 1,
                                lr: float = 1e-3, weight_decay: float = 1e-4, soft_label_alpha: float = 0.0,
                                anti_draw_penalty: float = 0.0, policy_draw_weight: float = 1.0, device: str = "cuda:0",
@@ -236,14 +255,33 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                                ddp_pre_sharded: bool = False, optimizer_state_path: Optional[str] = None,
                                symmetry_augment: bool = False, symmetry_seed: int = 0,
                                symmetry_set: Sequence[int] = tuple(range(8)), dedup_positions: str = "off",
-                               dedup_max_copies: int = 1) -> Tuple[Any, Dict[str, Any]]:
+                               dedup_max_copies: int = 1, **weighting) -> Tuple[Any, Dict[str, Any]]:
+    """`**weighting` takes two keywords, `row_weights=None` and `dedup_weighting="copies"`.
+    `row_weights` ([num_samples], tensor or array; finite, >= 0, sum > 0) weighs every row in the loss; it is
+    normalised to mean one over the rows trained on (row_weights.normalise_row_weights).
+    `dedup_weighting="weight"`: a merged group leaves once with the weight min(count, dedup_max_copies) instead of that
+    many copies.  The metrics gain `row_weights`, the epoch stats `row_weight_sum`."""
+    dedup_weighting, row_weights = _weighting_options("train_network_from_tensors", weighting,
+                                                      {"dedup_weighting": "copies", "row_weights": None}) \
+        if weighting else ("copies", None)
     dedup = None
     if not (isinstance(dedup_positions, str) and dedup_positions == "off" and type(dedup_max_copies) is int
-            and dedup_max_copies == 1):                # the defaults reach nothing below, not even the module
-        from . import position_dedup as dedup_mod
+            and dedup_max_copies == 1 and isinstance(dedup_weighting, str) and dedup_weighting == "copies"):
+        from . import position_dedup as dedup_mod      # the defaults reach nothing here, not even the module
         dedup_mod.dedup_refusal(dedup_positions, dedup_max_copies, policy_draw_weight=policy_draw_weight,
                                 anti_draw_penalty=anti_draw_penalty)
         dedup = dedup_mod if dedup_mod.dedup_on(dedup_positions, dedup_max_copies) else None
+        dedup_mod.weighting_on(dedup_weighting, dedup_positions, dedup_max_copies)
+    weigh = weights = weights_info = None
+    if row_weights is not None:
+        if dedup is not None:
+            raise ValueError(f"row_weights cannot be combined with dedup_positions={dedup_positions!r}: there is no rule "
+                             "yet for the weight of a group merged from weighted rows")
+        from . import row_weights as weigh
+        weights = row_weights if isinstance(row_weights, torch.Tensor) else torch.as_tensor(row_weights)
+        if weights.dim() != 1 or int(weights.numel()) != int(samples.num_samples):
+            raise ValueError(f"row_weights must hold one weight per sample, [{int(samples.num_samples)}], got "
+                             f"{tuple(weights.shape)}")
     if samples.num_samples <= 0:
         return model, {"epoch_stats": [], "num_samples": 0}
     strategy, dev, rank, world = _resolve_strategy(parallel_strategy, device)
@@ -254,6 +292,8 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
     sl = slice(rank, None, world) if (strategy == "ddp" and world > 1 and not ddp_pre_sharded) else slice(None)
     src = [getattr(samples, k)[sl] for k in ("state_tensors", "legal_masks", "policy_targets", "value_targets",
                                              "soft_value_targets")]
+    if weights is not None:
+        weights = weights[sl].to(dev)
     shard_sec = time.perf_counter() - t0
     t0 = time.perf_counter()
     states = src[0].to(dev, non_blocking=True).to(torch.float32)
@@ -269,6 +309,8 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
     if filtered:
         keep = torch.nonzero(finite).view(-1)
         states, masks, policy, values, soft = (t.index_select(0, keep) for t in (states, masks, policy, values, soft))
+        if weights is not None:
+            weights = weights.index_select(0, keep)
     n = int(states.shape[0])
     if n <= 0:
         if strategy == "ddp":
@@ -278,9 +320,16 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
     dedup_stats = None
     if dedup is not None:                             # duplicate positions merged once, each rank its own share
         (states, masks, policy, values, soft), info = dedup.merge_duplicate_positions(
-            states, masks, policy, values, soft, mode=dedup_positions, max_copies=int(dedup_max_copies))
+            states, masks, policy, values, soft, mode=dedup_positions, max_copies=int(dedup_max_copies),
+            **({} if dedup_weighting == "copies" else {"weighting": dedup_weighting}))
         dedup_stats = dedup.stats_of(info)
         n = int(states.shape[0])
+        if "weights" in info:                             # one row per group, min(count, dedup_max_copies) its weight
+            from . import row_weights as weigh
+            weights = info["weights"]
+    if weights is not None:                               # mean one over the rows trained on; the one validating read
+        weights, weights_info = weigh.normalise_row_weights(
+            weights, source="row_weights" if dedup is None else "dedup_weighting", ddp=strategy == "ddp" and world > 1)
 
     optimizer, opt_loaded, opt_err = _make_optimizer(model, lr, weight_decay, optimizer_state_path, dev)
     amp = bool(use_amp)
@@ -320,7 +369,11 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                 b_states, b_masks, b_policy = transform_samples(states, masks, policy, sym_draw.draw(int(idx.numel())), idx)
             else:
                 b_states, b_masks, b_policy = states.index_select(0, idx), masks.index_select(0, idx), policy.index_select(0, idx)
-            stepper.step(b_states, b_masks, b_policy, values.index_select(0, idx), soft.index_select(0, idx))
+            if weights is None:
+                stepper.step(b_states, b_masks, b_policy, values.index_select(0, idx), soft.index_select(0, idx))
+            else:
+                stepper.step(b_states, b_masks, b_policy, values.index_select(0, idx), soft.index_select(0, idx),
+                             b_weights=weights.index_select(0, idx))
             if not first_done:
                 first_batch_sec, first_done = time.perf_counter() - tb, True
         st, _ = stepper.epoch_stats(epoch + 1, {"parallel_strategy": strategy, "ddp_world_size": world,
@@ -348,6 +401,8 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
         out["symmetry_augment"] = sym_draw.metrics()
     if dedup_stats is not None:
         out["position_dedup"] = dedup_stats
+    if weights_info is not None:
+        out["row_weights"] = weights_info
     return model, out
 
 
@@ -463,14 +518,23 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
                               ddp_pre_sharded: bool = False, optimizer_state_path: Optional[str] = None,
                               symmetry_augment: bool = False, symmetry_seed: int = 0,
                               symmetry_set: Sequence[int] = tuple(range(8)), replay_budget_per_generation: int = 0,
-                              replay_seed: int = 0) -> Tuple[Any, Dict[str, Any]]:
+                              replay_seed: int = 0, **weighting) -> Tuple[Any, Dict[str, Any]]:
     """One training pass over a `replay_window.ReplayWindow`: `train_network_from_tensors` with the rows left where they
     are, as 360-byte records in the window's ring.  `window.select(replay_budget_per_generation, replay_seed)` is made
     once per call (every row of the newest generation, then at most the budget of each older one; a budget <= 0 gives
     the older generations together the weight of the newest); every batch is decoded out of the ring by one kernel that
     also applies the board symmetries of `symmetry_augment`.  The shuffle, the symmetry draw, the optimiser and the
     metrics are those of `train_network_from_tensors`; the metrics gain `replay_window`.  Non-finite rows were dropped
-    when their generation entered the window.  One trainer rank: no DDP, no duplicate merging."""
+    when their generation entered the window.  One trainer rank: no DDP, no duplicate merging.
+    `**weighting` takes one keyword, `replay_age_decay=1.0`: d in (0, 1]; a selected row whose generation lies a generations behind the newest weighs d ** a in
+    the loss, normalised to mean one over the selection; the metrics gain `row_weights`."""
+    replay_age_decay, = _weighting_options("train_network_from_window", weighting, {"replay_age_decay": 1.0}) \
+        if weighting else (1.0,)
+    weigh = None
+    if not (type(replay_age_decay) is float and replay_age_decay == 1.0):      # 1.0 reaches nothing below
+        from . import row_weights as weigh
+        if weigh.check_age_decay(replay_age_decay) == 1.0:
+            weigh = None
     strategy = {"dp": "none", "data_parallel": "none", "none": "none", "single": "none", "ddp": "ddp"}.get(
         str(parallel_strategy).strip().lower())
     if strategy != "none":
@@ -484,7 +548,13 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
     sym_draw = _SymmetryDraw(symmetry_set, symmetry_seed, rank, dev) if symmetry_augment else None
     train_model = _wrap(model, strategy, dev)
     t0 = time.perf_counter()
-    slots = window.select(int(replay_budget_per_generation), int(replay_seed))
+    weights = weights_info = None
+    if weigh is None:
+        slots = window.select(int(replay_budget_per_generation), int(replay_seed))
+    else:
+        slots, ages = window.select(int(replay_budget_per_generation), int(replay_seed), return_ages=True)
+        weights, weights_info = weigh.normalise_row_weights(weigh.age_weights(ages, replay_age_decay),
+                                                            source="replay_age_decay")
     replay = window.metrics(int(replay_budget_per_generation))
     replay["select_sec"] = float(time.perf_counter() - t0)
     n = int(slots.numel())
@@ -516,7 +586,10 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
             tb = time.perf_counter()
             idx = perm[start:min(start + bsz, n)]
             sym = sym_draw.draw(int(idx.numel())) if sym_draw is not None else None
-            stepper.step(*window.gather(slots.index_select(0, idx), sym))     # unpack + gather + transform in one pass
+            if weights is None:
+                stepper.step(*window.gather(slots.index_select(0, idx), sym))     # unpack + gather + transform in one pass
+            else:
+                stepper.step(*window.gather(slots.index_select(0, idx), sym), b_weights=weights.index_select(0, idx))
             if not first_done:
                 first_batch_sec, first_done = time.perf_counter() - tb, True
         st, _ = stepper.epoch_stats(epoch + 1, {"parallel_strategy": strategy, "ddp_world_size": world,
@@ -543,4 +616,6 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
     if sym_draw is not None:
         out["symmetry_augment"] = sym_draw.metrics()
     out["replay_window"] = replay
+    if weights_info is not None:
+        out["row_weights"] = weights_info
     return model, out

@@ -8,7 +8,10 @@ fixed seed) once with `opening_random_moves` 0 and once with 6, and for the rows
   (b) device-event times of `merge_duplicate_positions` (after a warm-up call; median of --repeats) and of the keys kernel
       alone with its bytes/s (n x (1584 + 220 + 65) bytes) against the HBM peak, next to the wall time of one trainer
       epoch on the same rows in the same process (second of two runs of one epoch, MIOpen immediate mode), and the merge
-      as a fraction of the epoch.
+      as a fraction of the epoch;
+  (c) for --weighting-mode (default exact) with dedup_max_copies = --weighting-max-copies (default 4): the rows trained
+      per epoch and the wall time of one trainer epoch (second of two runs, the merge included) with
+      dedup_weighting="copies" and with "weight" -- the same groups as min(count, M) copies or once with that weight.
 Needs a GPU; there is no fallback.
 
   python scripts/bench_position_dedup.py --games 4096 --sims 64
@@ -73,7 +76,7 @@ def timed_ms(fn, repeats):
     return {"median": statistics.median(out), "min": min(out), "max": max(out)}
 
 
-def epoch_seconds(batch, batch_size):
+def epoch_seconds(batch, batch_size, **kw):
     import torch
     from liuzhou_amd.net import ChessNet, MODEL_CONFIGS, stable_resnet_init
     from liuzhou_amd.train_bridge import train_network_from_tensors
@@ -83,10 +86,10 @@ def epoch_seconds(batch, batch_size):
     for _ in range(2):                                            # the first run warms the allocator and the kernels up
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        model, _ = train_network_from_tensors(model, batch, batch_size=batch_size, epochs=1, device="cuda:0")
+        model, metrics = train_network_from_tensors(model, batch, batch_size=batch_size, epochs=1, device="cuda:0", **kw)
         torch.cuda.synchronize()
         secs.append(time.perf_counter() - t0)
-    return secs
+    return (secs, metrics) if kw else secs
 
 
 def main() -> int:
@@ -98,6 +101,8 @@ def main() -> int:
     ap.add_argument("--batch-size", type=int, default=4096)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seed", type=int, default=20261019)
+    ap.add_argument("--weighting-mode", default="exact", choices=("exact", "symmetric"))
+    ap.add_argument("--weighting-max-copies", type=int, default=4)
     args = ap.parse_args()
     os.environ.setdefault("LZ_TRAIN_MIOPEN", "immediate")
     import torch
@@ -135,6 +140,13 @@ def main() -> int:
         out["epoch_s"] = {"first": secs[0], "second": secs[1]}
         for mode in out["modes"]:
             out["modes"][mode]["merge_share_of_epoch"] = out["modes"][mode]["merge_ms"]["median"] * 1e-3 / secs[1]
+        out["weighting"] = {"mode": args.weighting_mode, "max_copies": args.weighting_max_copies}
+        for weighting in ("copies", "weight"):
+            secs, metrics = epoch_seconds(batch, args.batch_size, dedup_positions=args.weighting_mode,
+                                          dedup_max_copies=args.weighting_max_copies, dedup_weighting=weighting)
+            out["weighting"][weighting] = {"rows_trained_per_epoch": metrics["position_dedup"]["rows_out"],
+                                           "steps_per_epoch": metrics["total_train_steps"],
+                                           "epoch_s": {"first": secs[0], "second": secs[1]}}
         print(json.dumps(out), flush=True)
         del batch, five
         torch.cuda.empty_cache()

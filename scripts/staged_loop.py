@@ -72,12 +72,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dedup-positions", default="off", choices=("off", "exact", "symmetric"),
                     help="merge duplicate positions among the iteration's rows before training (see train_stage.py)")
     ap.add_argument("--dedup-max-copies", type=int, default=1)
+    ap.add_argument("--dedup-weighting", default="copies", choices=("copies", "weight"),
+                    help="weight: a merged position is trained on once with the row weight min(its count, "
+                         "--dedup-max-copies) instead of that many copies (see train_stage.py)")
     ap.add_argument("--replay-generations", type=int, default=1,
                     help="train on a window of this many past generations kept on the trainer's device as 360-byte records "
                          "(liuzhou_amd/replay_window.py); 1: every iteration trains on its own generation alone")
     ap.add_argument("--replay-budget", type=int, default=0,
                     help="rows each older generation of the window contributes to a pass; 0: the newest generation's "
                          "count divided by the number of older generations (train_stage.py --replay_budget_per_file)")
+    ap.add_argument("--replay-age-decay", type=float, default=1.0,
+                    help="D in (0, 1]: a row of the window whose generation lies a generations behind the newest weighs "
+                         "D ** a in the loss (normalised to mean one); 1: no weights")
     ap.add_argument("--replay-capacity-rows", type=int, default=0,
                     help="slots of the window's ring; 0: generations x players x games-per-gpu x min(max-game-plies, 144)")
     ap.add_argument("--overlap", type=int, default=0, choices=(0, 1),
@@ -104,18 +110,28 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = ap.parse_args(argv)
     if args.replay_generations > 1 and args.dedup_positions != "off":
         ap.error("--replay-generations > 1 does not merge duplicate positions: leave --dedup-positions off")
+    if args.dedup_weighting != "copies" and args.dedup_positions == "off":
+        ap.error("--dedup-weighting weight needs --dedup-positions exact or symmetric")
+    if not 0.0 < args.replay_age_decay <= 1.0:             # NaN fails both comparisons
+        ap.error(f"--replay-age-decay must be in (0, 1], got {args.replay_age_decay!r}")
+    if args.replay_age_decay != 1.0 and args.replay_generations <= 1:
+        ap.error("--replay-age-decay needs a window: --replay-generations > 1")
     if not args.validate and args.validate_evaluator is not None:
         ap.error("--validate-evaluator needs --validate 1")
     return args
 
 
-def iteration_entry(base: dict, *, replay=None, window_on: bool = False, validation=None, validate_on: bool = False) -> dict:
-    """An iteration's log entry: `replay` only with a window, `validation` only with --validate 1."""
+def iteration_entry(base: dict, *, replay=None, window_on: bool = False, validation=None, validate_on: bool = False,
+                    row_weights=None, weights_on: bool = False) -> dict:
+    """An iteration's log entry: `replay` only with a window, `validation` only with --validate 1, `row_weights` only
+    with --dedup-weighting weight or --replay-age-decay below 1."""
     entry = dict(base)
     if window_on:
         entry["replay"] = replay
     if validate_on:
         entry["validation"] = validation
+    if weights_on:
+        entry["row_weights"] = row_weights
     return entry
 
 
@@ -170,6 +186,7 @@ def main(argv=None) -> int:
         dist.all_gather(every, t)
         return [int(e.item()) for e in every]
 
+    weights_on = args.dedup_weighting != "copies" or args.replay_age_decay != 1.0
     window = None
     if trains and args.replay_generations > 1:
         from liuzhou_amd.replay_window import ReplayWindow
@@ -196,17 +213,22 @@ def main(argv=None) -> int:
         validation = validate(model, data, generation) if args.validate else None
         model, metrics = train_network_from_window(model, window, batch_size=args.batch_size, epochs=args.epochs,
                                                    lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),
-                                                   replay_budget_per_generation=args.replay_budget, replay_seed=0)
+                                                   replay_budget_per_generation=args.replay_budget, replay_seed=0,
+                                                   **({"replay_age_decay": args.replay_age_decay}
+                                                      if args.replay_age_decay != 1.0 else {}))
         model.eval()
         e = metrics["epoch_stats"][-1] if metrics and metrics.get("epoch_stats") else {}
         return model, int(metrics.get("num_samples", 0)), {"avg_loss": e.get("avg_loss"), "samples_stepped": int(e.get("samples", 0)),
-                                                           "replay": metrics.get("replay_window"), "validation": validation}
+                                                           "replay": metrics.get("replay_window"), "validation": validation,
+                                                           "row_weights": metrics.get("row_weights")}
 
     def train(model, data, generation=None):
         if window is not None:
             return train_window(model, data, generation)
         dedup = ({"dedup_positions": args.dedup_positions, "dedup_max_copies": args.dedup_max_copies}
                  if args.dedup_positions != "off" else {})
+        if args.dedup_weighting != "copies":
+            dedup["dedup_weighting"] = args.dedup_weighting
         validation = validate(model, data, generation) if args.validate else None
         model, metrics = train_network_from_tensors(model, data, batch_size=args.batch_size, epochs=args.epochs,
                                                     lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),
@@ -216,7 +238,7 @@ def main(argv=None) -> int:
         # rows handed to the trainer; `samples_stepped` (epoch_stats.samples) can be lower: the AMP scaler skips the
         # batches whose scaled gradients overflow, exactly as the reference's loop does (train_bridge.py:388-420)
         return model, int(metrics.get("num_samples", 0)), {"avg_loss": e.get("avg_loss"), "samples_stepped": int(e.get("samples", 0)),
-                                                           "validation": validation}
+                                                           "validation": validation, "row_weights": metrics.get("row_weights")}
 
     model = ChessNet(**MODEL_CONFIGS[args.model])
     stable_resnet_init(model, 20260314)                               # MODEL_INIT_SEED (big_train_v1.sh:24)
@@ -318,7 +340,8 @@ def main(argv=None) -> int:
                  "samples_stepped": (loss or {}).get("samples_stepped"), "weights_equal_on_all_ranks": same,
                  "weights_digest": digests_seen[-1] if digests_seen else None, "net_check": net_check},
                 replay=(loss or {}).get("replay"), window_on=window is not None,
-                validation=(loss or {}).get("validation"), validate_on=bool(args.validate)))
+                validation=(loss or {}).get("validation"), validate_on=bool(args.validate),
+                row_weights=(loss or {}).get("row_weights"), weights_on=weights_on))
     tail = None
     if trains and overlap and pending is not None:                     # the last generation, nothing left to overlap with
         t0 = time.perf_counter()
@@ -327,7 +350,8 @@ def main(argv=None) -> int:
         tail = {"train_samples": trained, "avg_loss": (loss or {}).get("avg_loss"),
                 "samples_stepped": (loss or {}).get("samples_stepped"), "train_sec": round(time.perf_counter() - t0, 3)}
         tail = iteration_entry(tail, replay=(loss or {}).get("replay"), window_on=window is not None,
-                               validation=(loss or {}).get("validation"), validate_on=bool(args.validate))
+                               validation=(loss or {}).get("validation"), validate_on=bool(args.validate),
+                               row_weights=(loss or {}).get("row_weights"), weights_on=weights_on)
     if trains:
         steady = log[1:] if len(log) > 1 else log
         out = {"workload": f"C5 staged loop: {max(1, world - 1)} self-play GPU(s) x {args.games_per_gpu} games, "

@@ -57,6 +57,10 @@ def parse(argv=None):
                          "(symmetric) and train on the averaged targets (default off)")
     ap.add_argument("--dedup_max_copies", "--dedup-max-copies", dest="dedup_max_copies", type=int, default=1,
                     help="a merged position is kept min(its count, M) times (default 1: each position once)")
+    ap.add_argument("--dedup_weighting", "--dedup-weighting", dest="dedup_weighting", default="copies",
+                    choices=["copies", "weight"],
+                    help="weight: a merged position is trained on once with the row weight min(its count, M) instead of "
+                         "that many copies (default copies)")
     args, ignored = ap.parse_known_args(argv)
     args.ignored = ignored
     return args
@@ -104,6 +108,11 @@ def main(argv=None) -> int:
                 raise SystemExit("--dedup_positions needs --streaming_load 0: the streaming trainer sees one batch at a "
                                  "time, duplicate positions can only be merged over the whole set of rows")
             common.update(dedup_positions=args.dedup_positions, dedup_max_copies=int(args.dedup_max_copies))
+    if args.dedup_weighting != "copies":
+        if args.dedup_positions == "off":
+            raise SystemExit("--dedup_weighting weight needs --dedup_positions exact or symmetric: without merged "
+                             "positions there is nothing to weigh")
+        common.update(dedup_weighting=args.dedup_weighting)
     t0 = time.perf_counter()
     if int(args.streaming_load):
         budget = int(args.replay_budget_per_file)
