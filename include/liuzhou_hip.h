@@ -1133,6 +1133,39 @@ LZ_API int lz_dedup_merge_groups(const float* planes, const uint8_t* masks, cons
                                  float* out_planes, uint8_t* out_masks, float* out_policy,
                                  float* out_value, float* out_soft, int32_t* out_count, void* stream);
 
+/* ---- duplicate positions across the replay window, record to record (csrc/lz_replay_merge.h) --
+ * The same pair over 360-byte records in a ring of `capacity` records, without the 2 692-byte rows in between.  `slot`
+ * int64[m] lists the selected records.  Both builds export both entry points; neither allocates or synchronises, both
+ * are capturable.  Nothing outside a record's 360 bytes is read.  m == 0 (or groups == 0): LZ_OK without a launch;
+ * negative sizes, `symmetric` not 0 or 1, or a NULL required pointer: LZ_ERR_ARG; records, out_records and the int64
+ * arrays 8-byte, the int32 arrays 4-byte aligned, else LZ_ERR_ALIGN. */
+
+/* Keys: keys[j] and sym[j] are byte for byte what lz_dedup_position_keys writes for the row that
+ * lz_unpack_trajectory_rows makes of record slot[j] -- for any 360 bytes: the phase is (w0 >> 36) & 7, the boards are
+ * masked to 36 bits, mask bits 220..223 and every bit the layout does not own are ignored.  A record is always
+ * representable; a slot[j] outside [0, capacity) gives {INT64_MIN | j, 0, ..., 0}, sym 0, and adds one to
+ * *not_representable (the caller zeroes it).  One wave per row; only the 88 header bytes of a record are read. */
+LZ_API int lz_replay_position_keys(const void* records, int64_t capacity, const int64_t* slot /*[m]*/, int64_t m,
+                                   int32_t symmetric, int64_t* keys /*[m,8]*/, int8_t* sym /*[m]*/,
+                                   int32_t* not_representable /*add-only*/, void* stream);
+
+/* Merge: `order` and `group_begin` index positions in `slot` as they index rows in lz_dedup_merge_groups, sym[m] is
+ * per position.  Output record g is byte for byte lz_pack_trajectory_rows of row g of lz_dedup_merge_groups run on the
+ * unpacked rows: the first member's header made canonical (boards masked, phase at bit 36 of word 0, unowned bits and
+ * the pad zero, mask bits >= 220 clear); policy slot r, the first member's r-th legal action b, = (float)(S / c_p) with
+ * S the sum over the members of (double) their policy at P_e^-1(b), e = sym[f]^-1 o sym[m] -- the member's slot at the
+ * rank of that action among its legal bits, 0 when the bit is clear or the rank >= 72; c_p the members with a non-zero
+ * entry among their first min(legal count, 72) slots (0 -> all zero); value and soft the mean over all c members; slots
+ * at or past the legal count zero; out_count[g] = c.  Sums in the association of lz_dedup_merge_groups.  A group of one
+ * carries its legal slots, value and soft as bit copies.  A first member with more than 72 legal bits gives the first
+ * 72 legal actions' slots and adds one to *not_representable.  An empty or impossible range, an `order` entry outside
+ * [0, m), a slot outside the ring or a sym outside 0..7 gives an all-zero record with count 0.  One wave per group. */
+LZ_API int lz_replay_merge_records(const void* records, int64_t capacity, const int64_t* slot /*[m]*/, int64_t m,
+                                   const int8_t* sym /*[m]*/, const int64_t* order /*[m]*/,
+                                   const int64_t* group_begin /*[groups+1]*/, int64_t groups,
+                                   void* out_records /*uint8[groups,360]*/, int32_t* out_count /*[groups]*/,
+                                   int32_t* not_representable /*add-only*/, void* stream);
+
 /* The packed forward on the slots of a batch that are LIVE: slot g of packed_states[num_slots] is evaluated iff
  * leaf_kind[g] == 1 (device int32[num_slots]; the tree search's "leaf to expand"), and its outputs go to row g of the
  * output arrays, bit-identical to lz_net_forward_packed_f16 of that slot; rows of other slots are not written.

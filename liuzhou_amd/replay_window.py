@@ -6,11 +6,17 @@ loop: one `uint8[capacity_rows, 360]` ring of `trajectory_codec` records (7.5x s
 generation = consecutive slots modulo the capacity, and training batches decoded straight out of the ring by one kernel
 (`lz_replay_gather_rows`: unpack + board symmetry in one pass; no expanded copy of the window ever exists).
 
+Duplicate positions across the window are merged record to record: `record_position_keys`
+and `merge_record_groups` read and write records only -- HIP tensors through the kernels of csrc/lz_replay_merge.hip,
+CPU tensors through the host build -- and `ReplayWindow.merge_selection` turns a selection into one record per position
+with a row weight.
+
 `GenerationTable` is the bookkeeping alone -- plain Python, no tensors -- and `select_slots` the selection rule on any
 device; `ReplayWindow` is HIP only, like the codec.
 """
 from __future__ import annotations
 
+import math
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
@@ -113,6 +119,129 @@ def select_slots(table: GenerationTable, budget_per_old_generation: int, seed: i
     return slots, torch.cat([torch.full((int(p.numel()),), a, dtype=torch.int64, device=dev) for p, a in zip(parts, ages)])
 
 
+def _records_and_slots(records: torch.Tensor, slots: torch.Tensor, op: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    if not isinstance(records, torch.Tensor) or not isinstance(slots, torch.Tensor):
+        raise TypeError(f"{op}: records and slots must be tensors")
+    if records.dtype != torch.uint8 or records.dim() != 2 or int(records.shape[1]) != RECORD_BYTES:
+        raise ValueError(f"{op}: expected uint8[capacity, {RECORD_BYTES}] records, got {records.dtype} {tuple(records.shape)}")
+    if slots.dtype != torch.int64 or slots.device != records.device:
+        raise ValueError(f"slots must be int64 on {records.device}, got {slots.dtype} on {slots.device}")
+    return records.contiguous(), slots.reshape(-1).contiguous()
+
+
+def gather_records(records: torch.Tensor, slots: torch.Tensor, sym: Optional[torch.Tensor] = None, *,
+                   op: str = "replay_window.gather_records"):
+    """`ReplayWindow.gather` over any uint8[capacity,360] buffer of records on a HIP device (the ring, or the merged
+    records of `merge_selection`): one launch of `lz_replay_gather_rows`."""
+    L.require_hip(slots, op)
+    records, slots = _records_and_slots(records, slots, op)
+    dev = records.device
+    m = int(slots.numel())
+    width = 1
+    if sym is not None:
+        if sym.dtype not in (torch.int8, torch.int32):
+            raise TypeError("sym must be an int8 / int32 tensor")
+        if sym.numel() != m or sym.device != dev:
+            raise ValueError(f"sym must hold {m} ids on {dev}")
+        sym = sym.reshape(-1).contiguous()
+        width = 1 if sym.dtype == torch.int8 else 4
+    planes = torch.empty((m, 11, 6, 6), dtype=torch.float32, device=dev)
+    masks = torch.empty((m, 220), dtype=torch.uint8, device=dev)
+    policy = torch.empty((m, 220), dtype=torch.float32, device=dev)
+    value = torch.empty((m,), dtype=torch.float32, device=dev)
+    soft = torch.empty((m,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().lz_replay_gather_rows(L.ptr(records), L.i64(int(records.shape[0])), L.ptr(slots),
+                                              L.ptr(sym), width, L.i64(m), L.ptr(planes), L.ptr(masks),
+                                              L.ptr(policy), L.ptr(value), L.ptr(soft), L.stream_ptr(dev)),
+                "replay_gather_rows")
+    return planes, masks.view(torch.bool), policy, value, soft
+
+
+def record_position_keys(records: torch.Tensor, slots: torch.Tensor, *, symmetric: bool):
+    """(keys int64[m,8], sym int8[m], not_representable int32[1]) of the records uint8[capacity,360] at `slots` int64[m]
+    (include/liuzhou_hip.h: lz_replay_position_keys): byte for byte the keys of the unpacked rows.  A slot outside
+    [0, capacity) gets a key of its own and is counted.  HIP tensors go to the kernel, CPU tensors to the host build;
+    the counter stays on the records' device, nothing is read back."""
+    records, slots = _records_and_slots(records, slots, "replay_window.record_position_keys")
+    dev = records.device
+    m = int(slots.numel())
+    keys = torch.empty((m, 8), dtype=torch.int64, device=dev)
+    sym = torch.empty((m,), dtype=torch.int8, device=dev)
+    bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+    with L.device_ctx(dev):
+        st = L.lib_for(records).lz_replay_position_keys(L.ptr(records), L.i64(int(records.shape[0])), L.ptr(slots), L.i64(m),
+                                                        1 if symmetric else 0, L.ptr(keys), L.ptr(sym), L.ptr(bad),
+                                                        L.stream_ptr(dev))
+    L.check(st, "replay_window.record_position_keys")
+    return keys, sym, bad
+
+
+def merge_record_groups(records: torch.Tensor, slots: torch.Tensor, sym: torch.Tensor, order: torch.Tensor,
+                        begin: torch.Tensor):
+    """(merged uint8[groups,360], count int32[groups], not_representable int32[1]): one record per group of positions
+    in `slots` (include/liuzhou_hip.h: lz_replay_merge_records; `sym` int8[m] from `record_position_keys`, `order`
+    int64[m] and `begin` int64[groups+1] from `position_dedup.group_rows`).  Byte for byte the packed rows of
+    `position_dedup.merge_duplicate_positions` on the unpacked records."""
+    records, slots = _records_and_slots(records, slots, "replay_window.merge_record_groups")
+    dev = records.device
+    m = int(slots.numel())
+    if sym.dtype != torch.int8 or int(sym.numel()) != m or sym.device != dev:
+        raise ValueError(f"sym must hold {m} int8 ids on {dev}")
+    if order.dtype != torch.int64 or begin.dtype != torch.int64 or order.device != dev or begin.device != dev:
+        raise ValueError(f"order and begin must be int64 on {dev}")
+    if int(order.numel()) != m or int(begin.numel()) < 1:
+        raise ValueError(f"order must hold {m} positions and begin at least one boundary")
+    sym, order, begin = sym.reshape(-1).contiguous(), order.reshape(-1).contiguous(), begin.reshape(-1).contiguous()
+    groups = int(begin.numel()) - 1
+    merged = torch.zeros((groups, RECORD_BYTES), dtype=torch.uint8, device=dev)
+    count = torch.zeros((groups,), dtype=torch.int32, device=dev)
+    over = torch.zeros((1,), dtype=torch.int32, device=dev)
+    with L.device_ctx(dev):
+        st = L.lib_for(records).lz_replay_merge_records(L.ptr(records), L.i64(int(records.shape[0])), L.ptr(slots), L.i64(m),
+                                                        L.ptr(sym), L.ptr(order), L.ptr(begin), L.i64(groups),
+                                                        L.ptr(merged), L.ptr(count), L.ptr(over), L.stream_ptr(dev))
+    L.check(st, "replay_window.merge_record_groups")
+    return merged, count, over
+
+
+def check_max_weight(max_weight) -> float:
+    """`max_weight` as a float: a finite number >= 1; bools, NaN and everything else: ValueError."""
+    if isinstance(max_weight, bool) or not isinstance(max_weight, (int, float)) or not math.isfinite(float(max_weight)) \
+            or float(max_weight) < 1.0:
+        raise ValueError(f"replay_merge_max_weight must be a finite number >= 1, got {max_weight!r}")
+    return float(max_weight)
+
+
+def merge_weights(group_of_row: torch.Tensor, count: torch.Tensor, ages: Optional[torch.Tensor], age_decay: float,
+                  max_weight, span: Optional[int] = None) -> torch.Tensor:
+    """float64[groups]: w_g = min(sum over the members of age_decay ** age, max_weight), before normalisation.  No
+    floating-point scatter: the members are counted per (group, age) with an integer bincount, then count[g, a] *
+    age_weights(a) is added in ascending age.  Without ages, or with a decay of 1, this is min(count, max_weight);
+    with no duplicates it is `row_weights.age_weights` bit for bit.  `span`: the ages are known to lie in [0, span)
+    (the caller has checked, ages outside are clamped); without it the largest age is read from the device."""
+    cap = check_max_weight(max_weight)
+    groups = int(count.numel())
+    if ages is None or groups == 0:
+        return count.to(torch.float64).clamp(max=cap)
+    from .row_weights import age_weights, check_age_decay
+    decay = check_age_decay(age_decay)
+    if decay == 1.0:
+        return count.to(torch.float64).clamp(max=cap)
+    if span is None:
+        lo, hi = (int(v) for v in torch.stack([ages.min(), ages.max()]).tolist())
+        if lo < 0:
+            raise ValueError("ages must not be negative")
+        span = hi + 1
+    span = max(1, int(span))
+    per = torch.bincount(group_of_row * span + ages.clamp(0, span - 1), minlength=groups * span).view(groups, span)
+    scale = age_weights(torch.arange(span, dtype=torch.int64, device=count.device), decay)
+    total = torch.zeros((groups,), dtype=torch.float64, device=count.device)
+    for a in range(span):
+        total = total + per[:, a].to(torch.float64) * scale[a]
+    return total.clamp(max=cap)
+
+
 class ReplayWindow:
     """The last `max_generations` generations of training rows as records in one device ring of `capacity_rows` slots."""
 
@@ -210,30 +339,51 @@ class ReplayWindow:
         `slots`, each under the board symmetry `sym[j]` (int8 / int32 ids; None: as stored).  A slot outside the ring or
         an id outside 0..7 gives an all-zero row."""
         L.require_hip(slots, "ReplayWindow.gather")
-        dev = self.device
-        if slots.dtype != torch.int64 or slots.device != dev:
-            raise ValueError(f"slots must be int64 on {dev}, got {slots.dtype} on {slots.device}")
+        return gather_records(self.ring, slots, sym, op="ReplayWindow.gather")
+
+    # ---- duplicate positions (DESIGN.md section 30) --------------------------------------------------------------------
+    def position_keys(self, slots: torch.Tensor, *, symmetric: bool):
+        """(keys int64[m,8], sym int8[m], not_representable int32[1]) of the records at `slots`: what
+        `position_dedup.position_keys` gives for their unpacked rows, from the 88 header bytes of each record."""
+        return record_position_keys(self.ring, slots, symmetric=symmetric)
+
+    def merge_selection(self, slots: torch.Tensor, *, mode: str, ages: Optional[torch.Tensor] = None,
+                        age_decay: float = 1.0, max_weight=1):
+        """(merged uint8[groups,360], weights float64[groups], info): the selection with duplicate positions merged
+        record to record -- keys, `position_dedup.group_rows` (exact, groups by ascending first member), merge.  A
+        selection lists the newest generation first, so a group keeps its newest member's frame.  A group's targets are
+        the plain mean over its members whatever their age; its weight is min(sum of age_decay ** age over the members,
+        max_weight) (`merge_weights`; every member counts 1 without `ages`).  `info`: `position_dedup.STAT_KEYS`, mode,
+        max_weight, group_of_row int64[m] and count int32[groups]; one host read."""
+        from . import position_dedup as dedup
+        if not isinstance(mode, str) or mode not in dedup.MODES[1:]:
+            raise ValueError(f"merge_selection needs mode 'exact' or 'symmetric', got {mode!r}")
+        cap = check_max_weight(max_weight)
+        keys, sym, bad = self.position_keys(slots, symmetric=mode == "symmetric")
         slots = slots.reshape(-1).contiguous()
         m = int(slots.numel())
-        width = 1
-        if sym is not None:
-            if sym.dtype not in (torch.int8, torch.int32):
-                raise TypeError("sym must be an int8 / int32 tensor")
-            if sym.numel() != m or sym.device != dev:
-                raise ValueError(f"sym must hold {m} ids on {dev}")
-            sym = sym.reshape(-1).contiguous()
-            width = 1 if sym.dtype == torch.int8 else 4
-        planes = torch.empty((m, 11, 6, 6), dtype=torch.float32, device=dev)
-        masks = torch.empty((m, 220), dtype=torch.uint8, device=dev)
-        policy = torch.empty((m, 220), dtype=torch.float32, device=dev)
-        value = torch.empty((m,), dtype=torch.float32, device=dev)
-        soft = torch.empty((m,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            L.check(L.lib().lz_replay_gather_rows(L.ptr(self.ring), L.i64(self.table.capacity_rows), L.ptr(slots),
-                                                  L.ptr(sym), width, L.i64(m), L.ptr(planes), L.ptr(masks),
-                                                  L.ptr(policy), L.ptr(value), L.ptr(soft), L.stream_ptr(dev)),
-                    "replay_gather_rows")
-        return planes, masks.view(torch.bool), policy, value, soft
+        if ages is not None and (ages.dtype != torch.int64 or int(ages.numel()) != m or ages.device != slots.device):
+            raise ValueError(f"ages must hold {m} int64 ages on {slots.device}")
+        group_of_row, order, begin, count64 = dedup.group_rows(keys)
+        merged, count, over = merge_record_groups(self.ring, slots, sym, order, begin)
+        groups = int(count64.numel())
+        span = max(1, len(self.table.entries))              # an age is a number of generations behind the newest
+        zero = torch.zeros((), dtype=torch.int64, device=slots.device)
+        off = zero
+        if ages is not None:
+            ages = ages.reshape(-1)
+            off = ((ages < 0) | (ages >= span)).sum()
+        weights = merge_weights(group_of_row, count64, ages, age_decay, cap, span=span)
+        big = count64 > 1
+        stats = torch.stack([big.sum(), (count64 * big).sum(), count64.max() if groups else zero,
+                             bad[0].to(torch.int64) + over[0].to(torch.int64), off]).tolist()     # the one host read
+        if stats[4]:
+            raise ValueError(f"{int(stats[4])} ages lie outside [0, {span}): the window holds {span} generations")
+        info: Dict[str, Any] = {"rows_in": m, "rows_out": groups, "groups": groups, "merged_groups": int(stats[0]),
+                                "merged_rows": int(stats[1]), "largest_group": int(stats[2]),
+                                "not_representable": int(stats[3]), "mode": mode, "max_weight": cap,
+                                "group_of_row": group_of_row, "count": count}
+        return merged, weights, info
 
     # ---- restart -----------------------------------------------------------------------------------------------------
     def state_dict(self) -> Dict[str, Any]:

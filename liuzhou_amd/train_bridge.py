@@ -525,16 +525,40 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
     the older generations together the weight of the newest); every batch is decoded out of the ring by one kernel that
     also applies the board symmetries of `symmetry_augment`.  The shuffle, the symmetry draw, the optimiser and the
     metrics are those of `train_network_from_tensors`; the metrics gain `replay_window`.  Non-finite rows were dropped
-    when their generation entered the window.  One trainer rank: no DDP, no duplicate merging.
-    `**weighting` takes one keyword, `replay_age_decay=1.0`: d in (0, 1]; a selected row whose generation lies a generations behind the newest weighs d ** a in
-    the loss, normalised to mean one over the selection; the metrics gain `row_weights`."""
-    replay_age_decay, = _weighting_options("train_network_from_window", weighting, {"replay_age_decay": 1.0}) \
-        if weighting else (1.0,)
+    when their generation entered the window.  One trainer rank: no DDP.
+    `**weighting` takes three keywords.  `replay_age_decay=1.0`: d in (0, 1]; a selected row whose generation lies a generations behind the newest weighs d ** a in
+    the loss, normalised to mean one over the selection; the metrics gain `row_weights`.
+    `replay_merge_positions="off" | "exact" | "symmetric"` and `replay_merge_max_weight=1` (a finite number >= 1):
+    duplicate positions of the selection are merged once per call, record to record (`ReplayWindow.merge_selection`,
+    DESIGN.md section 30); a group leaves as one record with the mean targets of its members and the row weight
+    min(sum of d ** a over its members, replay_merge_max_weight), the batches are decoded from the merged records, and
+    the row count, the shuffle and the steps are those of the groups.  The metrics gain `replay_window["merge"]` and
+    `row_weights`.  Refused with `policy_draw_weight != 1` and an anti-draw penalty, like `dedup_positions`."""
+    replay_age_decay, merge_mode, merge_max_weight = _weighting_options(
+        "train_network_from_window", weighting,
+        {"replay_age_decay": 1.0, "replay_merge_positions": "off", "replay_merge_max_weight": 1}) \
+        if weighting else (1.0, "off", 1)
     weigh = None
     if not (type(replay_age_decay) is float and replay_age_decay == 1.0):      # 1.0 reaches nothing below
         from . import row_weights as weigh
         if weigh.check_age_decay(replay_age_decay) == 1.0:
             weigh = None
+    merge_on = False
+    if not (isinstance(merge_mode, str) and merge_mode == "off" and type(merge_max_weight) is int
+            and merge_max_weight == 1):                                        # the defaults reach nothing below
+        from . import position_dedup as dedup_mod
+        from .replay_window import check_max_weight
+        if not isinstance(merge_mode, str) or merge_mode not in dedup_mod.MODES:
+            raise ValueError(f"replay_merge_positions must be one of {dedup_mod.MODES}, got {merge_mode!r}")
+        merge_max_weight = check_max_weight(merge_max_weight)
+        merge_on = merge_mode != "off"
+        if merge_on:
+            try:
+                dedup_mod.dedup_refusal(merge_mode, 1, policy_draw_weight=policy_draw_weight,
+                                        anti_draw_penalty=anti_draw_penalty)
+            except ValueError as exc:
+                raise ValueError(str(exc).replace("dedup_positions", "replay_merge_positions")) from None
+            from . import row_weights as weigh_mod
     strategy = {"dp": "none", "data_parallel": "none", "none": "none", "single": "none", "ddp": "ddp"}.get(
         str(parallel_strategy).strip().lower())
     if strategy != "none":
@@ -548,8 +572,19 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
     sym_draw = _SymmetryDraw(symmetry_set, symmetry_seed, rank, dev) if symmetry_augment else None
     train_model = _wrap(model, strategy, dev)
     t0 = time.perf_counter()
-    weights = weights_info = None
-    if weigh is None:
+    weights = weights_info = merged = merge_stats = None
+    if merge_on:                                       # one record per position, its weight the members' (capped) sum
+        slots, ages = window.select(int(replay_budget_per_generation), int(replay_seed), return_ages=True)
+        t1 = time.perf_counter()
+        merged, group_w, info = window.merge_selection(
+            slots, mode=merge_mode, ages=None if weigh is None else ages,
+            age_decay=1.0 if weigh is None else float(replay_age_decay), max_weight=merge_max_weight)
+        weights, weights_info = weigh_mod.normalise_row_weights(group_w, source="replay_merge")
+        merge_stats = {k: info[k] for k in dedup_mod.STAT_KEYS + ("mode", "max_weight")}
+        slots = torch.arange(int(merged.shape[0]), dtype=torch.int64, device=dev)
+        merge_stats["merge_sec"] = float(time.perf_counter() - t1)
+        del info, group_w, ages
+    elif weigh is None:
         slots = window.select(int(replay_budget_per_generation), int(replay_seed))
     else:
         slots, ages = window.select(int(replay_budget_per_generation), int(replay_seed), return_ages=True)
@@ -557,8 +592,17 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
                                                             source="replay_age_decay")
     replay = window.metrics(int(replay_budget_per_generation))
     replay["select_sec"] = float(time.perf_counter() - t0)
+    if merge_stats is not None:
+        replay["merge"] = merge_stats
     n = int(slots.numel())
     filtered = int(replay["filtered_non_finite_rows"])
+    if merged is None:
+        gather = window.gather
+    else:
+        from .replay_window import gather_records
+
+        def gather(rows, sym):                            # the same kernel, its ring the merged records
+            return gather_records(merged, rows, sym)
 
     optimizer, opt_loaded, opt_err = _make_optimizer(model, lr, weight_decay, optimizer_state_path, dev)
     amp = bool(use_amp)
@@ -587,9 +631,9 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
             idx = perm[start:min(start + bsz, n)]
             sym = sym_draw.draw(int(idx.numel())) if sym_draw is not None else None
             if weights is None:
-                stepper.step(*window.gather(slots.index_select(0, idx), sym))     # unpack + gather + transform in one pass
+                stepper.step(*gather(slots.index_select(0, idx), sym))     # unpack + gather + transform in one pass
             else:
-                stepper.step(*window.gather(slots.index_select(0, idx), sym), b_weights=weights.index_select(0, idx))
+                stepper.step(*gather(slots.index_select(0, idx), sym), b_weights=weights.index_select(0, idx))
             if not first_done:
                 first_batch_sec, first_done = time.perf_counter() - tb, True
         st, _ = stepper.epoch_stats(epoch + 1, {"parallel_strategy": strategy, "ddp_world_size": world,
@@ -597,6 +641,7 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
                                                 "dropped_samples_for_sync": 0,
                                                 "filtered_non_finite_samples": filtered})
         epoch_stats.append(st)
+    merged = gather = None                             # the merged records go with the call
     lr_final = float(optimizer.param_groups[0]["lr"])
     if optimizer_state_path:
         try:

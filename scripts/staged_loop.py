@@ -37,6 +37,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -84,6 +85,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--replay-age-decay", type=float, default=1.0,
                     help="D in (0, 1]: a row of the window whose generation lies a generations behind the newest weighs "
                          "D ** a in the loss (normalised to mean one); 1: no weights")
+    ap.add_argument("--replay-merge-positions", default="off", choices=("off", "exact", "symmetric"),
+                    help="merge duplicate positions across the window's selection, record to record, before every "
+                         "training pass: a position leaves once with the mean targets of its copies and a row weight "
+                         "(liuzhou_amd/replay_window.py: merge_selection); needs --replay-generations > 1")
+    ap.add_argument("--replay-merge-max-weight", type=float, default=1.0,
+                    help="cap of a merged position's row weight (the sum of its copies' age weights); a number >= 1")
     ap.add_argument("--replay-capacity-rows", type=int, default=0,
                     help="slots of the window's ring; 0: generations x players x games-per-gpu x min(max-game-plies, 144)")
     ap.add_argument("--overlap", type=int, default=0, choices=(0, 1),
@@ -109,13 +116,18 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.replay_generations > 1 and args.dedup_positions != "off":
-        ap.error("--replay-generations > 1 does not merge duplicate positions: leave --dedup-positions off")
+        ap.error("--replay-generations > 1 does not merge duplicate positions with --dedup-positions: leave it off and "
+                 "use --replay-merge-positions, which merges the window's records")
     if args.dedup_weighting != "copies" and args.dedup_positions == "off":
         ap.error("--dedup-weighting weight needs --dedup-positions exact or symmetric")
     if not 0.0 < args.replay_age_decay <= 1.0:             # NaN fails both comparisons
         ap.error(f"--replay-age-decay must be in (0, 1], got {args.replay_age_decay!r}")
     if args.replay_age_decay != 1.0 and args.replay_generations <= 1:
         ap.error("--replay-age-decay needs a window: --replay-generations > 1")
+    if not (math.isfinite(args.replay_merge_max_weight) and args.replay_merge_max_weight >= 1.0):
+        ap.error(f"--replay-merge-max-weight must be a finite number >= 1, got {args.replay_merge_max_weight!r}")
+    if (args.replay_merge_positions != "off" or args.replay_merge_max_weight != 1.0) and args.replay_generations <= 1:
+        ap.error("--replay-merge-positions / --replay-merge-max-weight need a window: --replay-generations > 1")
     if not args.validate and args.validate_evaluator is not None:
         ap.error("--validate-evaluator needs --validate 1")
     return args
@@ -124,7 +136,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 def iteration_entry(base: dict, *, replay=None, window_on: bool = False, validation=None, validate_on: bool = False,
                     row_weights=None, weights_on: bool = False) -> dict:
     """An iteration's log entry: `replay` only with a window, `validation` only with --validate 1, `row_weights` only
-    with --dedup-weighting weight or --replay-age-decay below 1."""
+    with --dedup-weighting weight, --replay-age-decay below 1 or --replay-merge-positions on."""
     entry = dict(base)
     if window_on:
         entry["replay"] = replay
@@ -186,7 +198,7 @@ def main(argv=None) -> int:
         dist.all_gather(every, t)
         return [int(e.item()) for e in every]
 
-    weights_on = args.dedup_weighting != "copies" or args.replay_age_decay != 1.0
+    weights_on = args.dedup_weighting != "copies" or args.replay_age_decay != 1.0 or args.replay_merge_positions != "off"
     window = None
     if trains and args.replay_generations > 1:
         from liuzhou_amd.replay_window import ReplayWindow
@@ -211,11 +223,14 @@ def main(argv=None) -> int:
         if n_new > 0:
             window.add_generation(data, generation=generation)
         validation = validate(model, data, generation) if args.validate else None
+        weighting = {"replay_age_decay": args.replay_age_decay} if args.replay_age_decay != 1.0 else {}
+        if args.replay_merge_positions != "off":
+            weighting.update(replay_merge_positions=args.replay_merge_positions,
+                             replay_merge_max_weight=args.replay_merge_max_weight)
         model, metrics = train_network_from_window(model, window, batch_size=args.batch_size, epochs=args.epochs,
                                                    lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),
                                                    replay_budget_per_generation=args.replay_budget, replay_seed=0,
-                                                   **({"replay_age_decay": args.replay_age_decay}
-                                                      if args.replay_age_decay != 1.0 else {}))
+                                                   **weighting)
         model.eval()
         e = metrics["epoch_stats"][-1] if metrics and metrics.get("epoch_stats") else {}
         return model, int(metrics.get("num_samples", 0)), {"avg_loss": e.get("avg_loss"), "samples_stepped": int(e.get("samples", 0)),
