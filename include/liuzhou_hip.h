@@ -1039,6 +1039,26 @@ LZ_API int lz_policy_value_loss_weighted_fwd_bwd(const float* log_p1, const floa
                                                  float* grad_log_p2, float* grad_log_pmc, float* grad_value_logits,
                                                  void* stream);
 
+/* The same loss with a distributional value target for some rows: two more instantiations of the
+ * same kernel.  The arguments of the weighted entry, then dist_row int32 [B], value_dist float32 [D,101] (the table of
+ * lz_merge_value_distributions) and D.  row_weight may be NULL: the unweighted arithmetic.  A row b with
+ * 0 <= dist_row[b] < D takes row dist_row[b] of the table as its value target in place of the two-hot of its value and
+ * soft value: terms[b][2] is the cross entropy against that row, grad_value_logits (softmax - row) * scale.  Any other
+ * dist_row[b] takes the scalar two-hot path: every byte of the row's outputs is that of the entry without a table.
+ * Policy, the weight column, the WDL term and every scale are untouched; the table was built for anti_draw_penalty 0,
+ * which the callers pass.  Nothing outside the table and the row's own data is read.  NULL dist_row, D < 0 or a NULL
+ * value_dist with D > 0: LZ_ERR_ARG; otherwise the checks of the entries above. */
+LZ_API int lz_policy_value_loss_dist_fwd_bwd(const float* log_p1, const float* log_p2, const float* log_pmc,
+                                             const float* value_logits, const uint8_t* legal_mask,
+                                             const float* policy_target, const float* value_target,
+                                             const float* soft_value_target, const float* row_weight,
+                                             int64_t batch, float soft_label_alpha, float anti_draw_penalty,
+                                             float policy_draw_weight, const float* policy_weight_sum,
+                                             float grad_scale, float* terms, float* grad_log_p1,
+                                             float* grad_log_p2, float* grad_log_pmc, float* grad_value_logits,
+                                             void* stream, const int32_t* dist_row, const float* value_dist,
+                                             int64_t D);
+
 /* ---- compact trajectory records: wire format of the per-iteration gather ---- */
 
 /* A row of the 5-tensor trajectory contract (v1/python/trajectory_buffer.py:11-33; 2 692 B) as an exact 360-byte
@@ -1165,6 +1185,32 @@ LZ_API int lz_replay_merge_records(const void* records, int64_t capacity, const 
                                    const int64_t* group_begin /*[groups+1]*/, int64_t groups,
                                    void* out_records /*uint8[groups,360]*/, int32_t* out_count /*[groups]*/,
                                    int32_t* not_representable /*add-only*/, void* stream);
+
+/* ---- the value target of a merged group as a distribution (csrc/lz_value_dist.h) -------------
+ * Both merges above leave the MEAN value and soft value of a group; the bucket cross entropy of the loss is linear in
+ * its target distribution, not in the value, so the lossless value target of a group is the mean of its members'
+ * two-hot distributions.  Row dist_row[g] of `dist` (float32 [D,101]) receives, for group g = members
+ * order[group_begin[g] .. group_begin[g+1]):
+ *   dist[b] = (float)(S[b] / c),  S[b] = sum over the members, sequentially from 0.0 in member order, in double, of
+ *   (double)((b == lo ? 1.0f - frac : 0) + (b == hi ? frac : 0)),
+ * (lo, hi, frac) the bin assignment of lz_policy_value_loss_fwd_bwd with anti_draw_penalty 0 for the member's value and
+ * soft value: mixed = fminf(fmaxf((1-alpha)*v + alpha*soft, -1), 1) uncontracted in float32 (a NaN lands on bin 0),
+ * u = (mixed + 1) / (2/100), lo = floor(u) in 0..100, hi = min(lo + 1, 100), frac = clamp(u - lo, 0, 1), 0 when hi == lo.
+ * A group whose members share their (value, soft) bits gets exactly that member's two-hot.
+ * Member p's element is e = index[p] (index NULL: e = p); its value is the float at value_base + e * stride_bytes, its
+ * soft value the float at soft_base + e * stride_bytes.  One entry serves both merges: tensors (value_base = values,
+ * soft_base = soft, stride_bytes 4, index NULL, n rows) and the replay ring (value_base = ring + 348, soft_base =
+ * ring + 352, stride_bytes 360, index = slot, n = capacity).
+ * A group with dist_row[g] outside [0, D) writes nothing.  An `order` entry outside [0, m), an element outside [0, n)
+ * or an empty or impossible range gives an all-zero row.  groups == 0 or D == 0: LZ_OK without a launch; a negative
+ * size, stride_bytes < 4 or a NULL required pointer (index is optional; order only with m > 0, the bases only with
+ * n > 0): LZ_ERR_ARG; the int64 arrays 8-byte, the bases, stride_bytes, dist_row and dist 4-byte aligned, else
+ * LZ_ERR_ALIGN.  Both builds export it; it neither allocates nor synchronises.  One wave per group. */
+LZ_API int lz_merge_value_distributions(const void* value_base, const void* soft_base, int64_t stride_bytes, int64_t n,
+                                        const int64_t* index /*[m] or NULL*/, int64_t m, const int64_t* order /*[m]*/,
+                                        const int64_t* group_begin /*[groups+1]*/, int64_t groups,
+                                        const int32_t* dist_row /*[groups]*/, float alpha, float* dist /*[D,101]*/,
+                                        int64_t D, void* stream);
 
 /* The packed forward on the slots of a batch that are LIVE: slot g of packed_states[num_slots] is evaluated iff
  * leaf_kind[g] == 1 (device int32[num_slots]; the tree search's "leaf to expand"), and its outputs go to row g of the

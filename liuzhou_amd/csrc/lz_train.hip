@@ -36,14 +36,18 @@ __device__ __forceinline__ int move_dest_cell(int from, int dir) {      // DIREC
 // WEIGHTED: a per-row weight rw = row_weight[s] multiplies the row's policy weight and its value gradient (absolute
 // multipliers: weight_sum and B stay the denominators the caller chose).  The unweighted instantiation never reads the
 // pointer, which is the last argument so that the kernel arguments in front of it keep their offsets.
-template <bool WEIGHTED>
+// DIST: a row whose d = dist_row[s] lies in [0, D) takes row d of value_dist [D,101] as its value target (the mean of the
+// two-hot distributions of the rows it was merged from, lz_value_dist.h); any other d takes the
+// scalar two-hot.  The three arguments come after row_weight and are never read by the other instantiations.
+template <bool WEIGHTED, bool DIST>
 __global__ __launch_bounds__(kWave * kWavesPerBlock) void policy_value_loss_kernel(
     const float* __restrict__ lp1, const float* __restrict__ lp2, const float* __restrict__ lpm,
     const float* __restrict__ vlogits, const uint8_t* __restrict__ legal, const float* __restrict__ target,
     const float* __restrict__ value, const float* __restrict__ soft, int64_t B, float alpha, float anti_draw,
     float draw_weight, const float* __restrict__ weight_sum, float grad_scale,
     float* __restrict__ terms /*[B,4]: kl, weight, bucket CE, wdl aux*/, float* __restrict__ g1, float* __restrict__ g2,
-    float* __restrict__ gm, float* __restrict__ gv, const float* __restrict__ row_weight) {
+    float* __restrict__ gm, float* __restrict__ gv, const float* __restrict__ row_weight,
+    const int32_t* __restrict__ dist_row, const float* __restrict__ value_dist, int64_t D) {
     __shared__ float s_dc[kWavesPerBlock][256];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -150,8 +154,15 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void policy_value_loss_kern
     const float e0 = expf(v0 - vm), e1 = has1 ? expf(v1 - vm) : 0.f;
     const float vs = lzw::wave_sum(e0 + e1);
     const float vlse = vm + logf(vs);
-    const float tg0 = (lane == lo ? 1.0f - frac : 0.f) + (lane == hi ? frac : 0.f);
-    const float tg1 = (lane + 64 == lo ? 1.0f - frac : 0.f) + (lane + 64 == hi ? frac : 0.f);
+    float tg0 = (lane == lo ? 1.0f - frac : 0.f) + (lane == hi ? frac : 0.f);
+    float tg1 = (lane + 64 == lo ? 1.0f - frac : 0.f) + (lane + 64 == hi ? frac : 0.f);
+    if constexpr (DIST) {
+        const int d = __builtin_amdgcn_readfirstlane(dist_row[s]);      // wave-uniform, like value[s]
+        if (d >= 0 && (int64_t)d < D) {
+            tg0 = value_dist[(int64_t)d * kBins + lane];
+            tg1 = has1 ? value_dist[(int64_t)d * kBins + lane + 64] : 0.f;       // never past the row
+        }
+    }
     float cev = -(tg0 * (v0 - vlse)) - (has1 ? tg1 * (v1 - vlse) : 0.f);
     cev = lzw::wave_sum(cev);
     const float sm0 = e0 / vs, sm1 = e1 / vs;
@@ -180,25 +191,26 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void policy_value_loss_kern
 
 namespace {
 
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool DIST = false>
 int launch_policy_value_loss(const float* log_p1, const float* log_p2, const float* log_pmc, const float* value_logits,
                              const uint8_t* legal_mask, const float* policy_target, const float* value_target,
                              const float* soft_value_target, const float* row_weight, int64_t batch,
                              float soft_label_alpha, float anti_draw_penalty, float policy_draw_weight,
                              const float* policy_weight_sum, float grad_scale, float* terms, float* grad_log_p1,
-                             float* grad_log_p2, float* grad_log_pmc, float* grad_value_logits, void* stream) {
-    if (batch < 0) return LZ_ERR_ARG;
+                             float* grad_log_p2, float* grad_log_pmc, float* grad_value_logits, void* stream,
+                             const int32_t* dist_row = nullptr, const float* value_dist = nullptr, int64_t D = 0) {
+    if (batch < 0 || D < 0) return LZ_ERR_ARG;
     if (batch == 0) return LZ_OK;
     if (!log_p1 || !log_p2 || !log_pmc || !value_logits || !legal_mask || !policy_target || !value_target ||
         !soft_value_target || !policy_weight_sum || !terms || !grad_log_p1 || !grad_log_p2 || !grad_log_pmc ||
-        !grad_value_logits || (WEIGHTED && !row_weight))
+        !grad_value_logits || (WEIGHTED && !row_weight) || (DIST && (!dist_row || (D > 0 && !value_dist))))
         return LZ_ERR_ARG;
     const unsigned grid = (unsigned)((batch + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL(policy_value_loss_kernel<WEIGHTED>, dim3(grid), dim3(kWave * kWavesPerBlock), 0,
+    hipLaunchKernelGGL((policy_value_loss_kernel<WEIGHTED, DIST>), dim3(grid), dim3(kWave * kWavesPerBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), log_p1, log_p2, log_pmc, value_logits, legal_mask,
                        policy_target, value_target, soft_value_target, batch, soft_label_alpha, anti_draw_penalty,
                        policy_draw_weight, policy_weight_sum, grad_scale, terms, grad_log_p1, grad_log_p2, grad_log_pmc,
-                       grad_value_logits, row_weight);
+                       grad_value_logits, row_weight, dist_row, value_dist, D);
     return hipGetLastError() == hipSuccess ? LZ_OK : LZ_ERR_LAUNCH;
 }
 
@@ -231,6 +243,29 @@ extern "C" int lz_policy_value_loss_weighted_fwd_bwd(const float* log_p1, const 
                                           soft_value_target, row_weight, batch, soft_label_alpha, anti_draw_penalty,
                                           policy_draw_weight, policy_weight_sum, grad_scale, terms, grad_log_p1,
                                           grad_log_p2, grad_log_pmc, grad_value_logits, stream);
+}
+
+extern "C" int lz_policy_value_loss_dist_fwd_bwd(const float* log_p1, const float* log_p2, const float* log_pmc,
+                                                 const float* value_logits, const uint8_t* legal_mask,
+                                                 const float* policy_target, const float* value_target,
+                                                 const float* soft_value_target, const float* row_weight,
+                                                 int64_t batch, float soft_label_alpha, float anti_draw_penalty,
+                                                 float policy_draw_weight, const float* policy_weight_sum,
+                                                 float grad_scale, float* terms, float* grad_log_p1,
+                                                 float* grad_log_p2, float* grad_log_pmc, float* grad_value_logits,
+                                                 void* stream, const int32_t* dist_row, const float* value_dist,
+                                                 int64_t D) {
+    if (row_weight != nullptr)
+        return launch_policy_value_loss<true, true>(log_p1, log_p2, log_pmc, value_logits, legal_mask, policy_target,
+                                                    value_target, soft_value_target, row_weight, batch, soft_label_alpha,
+                                                    anti_draw_penalty, policy_draw_weight, policy_weight_sum, grad_scale,
+                                                    terms, grad_log_p1, grad_log_p2, grad_log_pmc, grad_value_logits,
+                                                    stream, dist_row, value_dist, D);
+    return launch_policy_value_loss<false, true>(log_p1, log_p2, log_pmc, value_logits, legal_mask, policy_target,
+                                                 value_target, soft_value_target, nullptr, batch, soft_label_alpha,
+                                                 anti_draw_penalty, policy_draw_weight, policy_weight_sum, grad_scale,
+                                                 terms, grad_log_p1, grad_log_p2, grad_log_pmc, grad_value_logits, stream,
+                                                 dist_row, value_dist, D);
 }
 
 // ---- compact trajectory records (wire format of the per-iteration gather) ----------------

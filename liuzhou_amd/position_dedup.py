@@ -22,6 +22,8 @@ from . import _lib as L
 
 MODES = ("off", "exact", "symmetric")
 WEIGHTINGS = ("copies", "weight")
+VALUE_TARGETS = ("mean", "distribution")
+VALUE_BINS = 101
 NUM_ACTIONS = 220
 STAT_KEYS = ("rows_in", "rows_out", "groups", "merged_groups", "merged_rows", "largest_group", "not_representable")
 
@@ -49,6 +51,44 @@ def weighting_on(weighting, mode="off", max_copies=1) -> bool:
         raise ValueError("dedup_weighting='weight' needs dedup_positions 'exact' or 'symmetric': with dedup_positions="
                          f"{mode!r} there are no groups to weigh")
     return weighting == "weight"
+
+
+def value_target_on(value_target, mode="off", max_copies=1, *, name: str = "dedup_value_target",
+                    needs: str = "dedup_positions") -> bool:
+    """Validate a value-target keyword (merge on or off alike) and say whether merged groups are trained on the
+    distribution of their members' value targets."""
+    if not isinstance(value_target, str) or value_target not in VALUE_TARGETS:
+        raise ValueError(f"{name} must be one of {VALUE_TARGETS}, got {value_target!r}")
+    if value_target == "distribution" and not dedup_on(mode, max_copies):
+        raise ValueError(f"{name}='distribution' needs {needs} 'exact' or 'symmetric': with {needs}={mode!r} there are "
+                         "no groups to describe")
+    return value_target == "distribution"
+
+
+def table_rows(count64: torch.Tensor) -> torch.Tensor:
+    """int32[groups]: the row of the value-distribution table of every group -- groups of more than one member are
+    numbered in order, a group of one gets -1 (its two-hot is what the loss computes from its value).  No host read."""
+    merged = count64 > 1
+    return torch.where(merged, torch.cumsum(merged, 0) - 1, torch.full_like(count64, -1)).to(torch.int32)
+
+
+def merge_value_distributions(value_base: torch.Tensor, soft_base: torch.Tensor, stride_bytes: int, n: int, index,
+                              order: torch.Tensor, begin: torch.Tensor, dist_row: torch.Tensor, alpha: float,
+                              rows: int) -> torch.Tensor:
+    """float32[rows,101]: the table of include/liuzhou_hip.h: lz_merge_value_distributions.  `value_base` / `soft_base`
+    are tensors whose first byte is element 0's value / soft value (float32 [n] with stride 4, or views into a ring of
+    records with stride 360 and `index` = the selection's slots).  HIP tensors go to the kernel, CPU tensors to the host
+    build.  Rows no group points at stay zero."""
+    dev = order.device
+    dist = torch.zeros((int(rows), VALUE_BINS), dtype=torch.float32, device=dev)
+    groups = int(begin.numel()) - 1
+    with L.device_ctx(dev):
+        st = L.lib_for(order).lz_merge_value_distributions(
+            L.ptr(value_base), L.ptr(soft_base), L.i64(stride_bytes), L.i64(n), L.ptr(index), L.i64(int(order.numel())),
+            L.ptr(order), L.ptr(begin), L.i64(groups), L.ptr(dist_row), float(alpha), L.ptr(dist), L.i64(int(rows)),
+            L.stream_ptr(dev))
+    L.check(st, "position_dedup.merge_value_distributions")
+    return dist
 
 
 def group_weights(count: torch.Tensor, max_copies: int = 1) -> torch.Tensor:
@@ -130,17 +170,23 @@ def group_rows(keys: torch.Tensor):
 
 
 def merge_duplicate_positions(planes: torch.Tensor, masks: torch.Tensor, policy: torch.Tensor, values: torch.Tensor,
-                              soft: torch.Tensor, *, mode: str, max_copies: int = 1, weighting: str = "copies"):
+                              soft: torch.Tensor, *, mode: str, max_copies: int = 1, weighting: str = "copies",
+                              value_target: str = "mean", soft_label_alpha: float = 0.0):
     """((planes, masks, policy, values, soft), info): the rows with duplicate positions merged.
 
     planes float32[n,11,6,6] (or [n,11,36]); masks bool / uint8 [n,220]; policy float32[n,220]; values and soft
     float32[n].  mode "exact" or "symmetric".  Groups leave in the order of their first members, each min(count,
     max_copies) times.  `info` holds the stats (`STAT_KEYS`, "mode", "max_copies"; one host read), `group_of_row`
     int64[n] and `count` int32[groups].  weighting "weight": each group leaves once, and `info` gains "weighting" and
-    "weights" = `group_weights(count, max_copies)`, one per row that leaves."""
+    "weights" = `group_weights(count, max_copies)`, one per row that leaves.  value_target "distribution" (DESIGN.md
+    section 31): `info` gains "value_target", "value_dist" float32[merged_groups,101] -- per group of more than one member
+    the mean of its members' two-hot value distributions at `soft_label_alpha` (clamped to [0, 1] as the trainers clamp it)
+    -- and "value_dist_row" int32, one per row that leaves: its row of the table, -1 for a group of one.  The rows keep
+    their mean value and soft value."""
     if not dedup_on(mode, max_copies):
         raise ValueError("merge_duplicate_positions needs mode 'exact' or 'symmetric'")
     weighted = weighting_on(weighting, mode, max_copies)
+    distribution = value_target_on(value_target, mode, max_copies, name="value_target", needs="mode")
     copies = int(max_copies)
     pl, mk, n = _rows(planes, masks)
     dev = pl.device
@@ -173,9 +219,16 @@ def merge_duplicate_positions(planes: torch.Tensor, masks: torch.Tensor, policy:
     stats = torch.stack([reps.sum(), merged.sum(), (count64 * merged).sum(), count64.max() if groups else zero,
                          bad[0].to(torch.int64)]).tolist()             # the one host read of the stats
     outs = (out_planes, out_masks, out_policy, out_values, out_soft)
+    dist = dist_row = None
+    if distribution:                                                  # D = merged_groups came with the one read above
+        dist_row = table_rows(count64)
+        dist = merge_value_distributions(val, sof, 4, n, None, order, begin, dist_row,
+                                         max(0.0, min(1.0, float(soft_label_alpha))), int(stats[1]))
     if stats[0] != groups:                                            # some group leaves more than once
         take = torch.repeat_interleave(torch.arange(groups, dtype=torch.int64, device=dev), reps, output_size=int(stats[0]))
         outs = tuple(t.index_select(0, take) for t in outs)
+        if distribution:
+            dist_row = dist_row.index_select(0, take)                 # every copy of a group points at the group's row
     info: Dict[str, Any] = {"rows_in": n, "rows_out": int(stats[0]), "groups": groups, "merged_groups": int(stats[1]),
                             "merged_rows": int(stats[2]), "largest_group": int(stats[3]),
                             "not_representable": int(stats[4]), "mode": mode, "max_copies": copies,
@@ -183,9 +236,13 @@ def merge_duplicate_positions(planes: torch.Tensor, masks: torch.Tensor, policy:
     if weighted:
         info["weighting"] = "weight"
         info["weights"] = group_weights(count, copies)
+    if distribution:
+        info["value_target"] = "distribution"
+        info["value_dist"], info["value_dist_row"] = dist, dist_row
     return outs, info
 
 
 def stats_of(info: Dict[str, Any]) -> Dict[str, Any]:
     """The plain-number part of `info` (what the trainer's metrics carry)."""
-    return {k: info[k] for k in STAT_KEYS + ("mode", "max_copies") + (("weighting",) if "weighting" in info else ())}
+    return {k: info[k] for k in STAT_KEYS + ("mode", "max_copies") + (("weighting",) if "weighting" in info else ())
+            + (("value_target",) if "value_target" in info else ())}

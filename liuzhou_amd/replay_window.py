@@ -348,16 +348,20 @@ class ReplayWindow:
         return record_position_keys(self.ring, slots, symmetric=symmetric)
 
     def merge_selection(self, slots: torch.Tensor, *, mode: str, ages: Optional[torch.Tensor] = None,
-                        age_decay: float = 1.0, max_weight=1):
+                        age_decay: float = 1.0, max_weight=1, value_target: str = "mean", soft_label_alpha: float = 0.0):
         """(merged uint8[groups,360], weights float64[groups], info): the selection with duplicate positions merged
         record to record -- keys, `position_dedup.group_rows` (exact, groups by ascending first member), merge.  A
         selection lists the newest generation first, so a group keeps its newest member's frame.  A group's targets are
         the plain mean over its members whatever their age; its weight is min(sum of age_decay ** age over the members,
         max_weight) (`merge_weights`; every member counts 1 without `ages`).  `info`: `position_dedup.STAT_KEYS`, mode,
-        max_weight, group_of_row int64[m] and count int32[groups]; one host read."""
+        max_weight, group_of_row int64[m] and count int32[groups]; one host read.  value_target "distribution"
+        (DESIGN.md section 31): `info` gains "value_target", "value_dist" float32[merged_groups,101] -- the mean of the
+        members' two-hot value distributions at `soft_label_alpha`, computed straight from the ring through `slots` -- and
+        "value_dist_row" int32[groups], -1 for a group of one.  The merged records keep the mean value and soft value."""
         from . import position_dedup as dedup
         if not isinstance(mode, str) or mode not in dedup.MODES[1:]:
             raise ValueError(f"merge_selection needs mode 'exact' or 'symmetric', got {mode!r}")
+        distribution = dedup.value_target_on(value_target, mode, name="value_target", needs="mode")
         cap = check_max_weight(max_weight)
         keys, sym, bad = self.position_keys(slots, symmetric=mode == "symmetric")
         slots = slots.reshape(-1).contiguous()
@@ -383,6 +387,13 @@ class ReplayWindow:
                                 "merged_rows": int(stats[1]), "largest_group": int(stats[2]),
                                 "not_representable": int(stats[3]), "mode": mode, "max_weight": cap,
                                 "group_of_row": group_of_row, "count": count}
+        if distribution:                                    # D = merged_groups came with the one read above
+            flat = self.ring.view(-1)
+            info["value_target"] = "distribution"
+            info["value_dist_row"] = dedup.table_rows(count64)
+            info["value_dist"] = dedup.merge_value_distributions(
+                flat[348:], flat[352:], RECORD_BYTES, int(self.ring.shape[0]), slots, order, begin, info["value_dist_row"],
+                max(0.0, min(1.0, float(soft_label_alpha))), int(stats[0]))
         return merged, weights, info
 
     # ---- restart -----------------------------------------------------------------------------------------------------

@@ -45,7 +45,13 @@ class _Stepper:
         self._row_hist: Dict[int, int] = {}               # batch sizes seen so far
         self._conv_counts = [0, 0]                        # steps in [search-once, immediate] mode (reported per epoch)
         self._conv_logged = False
+        self.value_dist: Optional[torch.Tensor] = None     # the table `b_dist_row` points into (set_value_dist)
         self.reset()
+
+    def set_value_dist(self, table: Optional[torch.Tensor]) -> None:
+        """The value-distribution table of the merged groups (float32 [D,101]), given once; the
+        steps that come with `b_dist_row` (`step_dist`) read it."""
+        self.value_dist = table
 
     def reset(self) -> None:
         # loss, policy*w, value, bucket, aux, seen, wsum, valid, |soft|
@@ -86,7 +92,13 @@ class _Stepper:
         with self._conv_mode(int(b_states.shape[0])):
             return self._step(b_states, b_masks, b_policy, b_values, b_soft, b_weights)
 
-    def _step(self, b_states, b_masks, b_policy, b_values, b_soft, b_weights=None) -> bool:
+    def step_dist(self, b_states, b_masks, b_policy, b_values, b_soft, b_weights=None, b_dist_row=None) -> bool:
+        """`step` for a batch of merged rows with a distributional value target: `b_dist_row` int32 [rows], every row's
+        row of the table of `set_value_dist` (-1: none); None: `step`."""
+        with self._conv_mode(int(b_states.shape[0])):
+            return self._step(b_states, b_masks, b_policy, b_values, b_soft, b_weights, b_dist_row)
+
+    def _step(self, b_states, b_masks, b_policy, b_values, b_soft, b_weights=None, b_dist_row=None) -> bool:
         opt, scaler, dev = self.optimizer, self.scaler, self.dev
         opt.zero_grad(set_to_none=True)
         with (torch.amp.autocast("cuda", enabled=True) if self.amp else nullcontext()):
@@ -94,7 +106,9 @@ class _Stepper:
         loss, parts = fused_policy_value_loss(lp1, lp2, lpm, vlogits, b_masks, b_policy, b_values, b_soft,
                                               soft_label_alpha=self.alpha, anti_draw_penalty=self.anti_draw,
                                               policy_draw_weight=self.draw_w,
-                                              **({} if b_weights is None else {"row_weights": b_weights}))
+                                              **({} if b_weights is None else {"row_weights": b_weights}),
+                                              **({} if b_dist_row is None else {"value_dist": self.value_dist,
+                                                                                "value_dist_row": b_dist_row}))
         # ONE host read per step for both finite checks of the reference (train_bridge.py:388-420 reads the loss flag and
         # then one flag per parameter tensor: ~130 device round trips per step).  The backward runs before the read; a
         # non-finite loss makes non-finite gradients, which are thrown away below exactly as if backward had not run
@@ -256,22 +270,29 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                                symmetry_augment: bool = False, symmetry_seed: int = 0,
                                symmetry_set: Sequence[int] = tuple(range(8)), dedup_positions: str = "off",
                                dedup_max_copies: int = 1, **weighting) -> Tuple[Any, Dict[str, Any]]:
-    """`**weighting` takes two keywords, `row_weights=None` and `dedup_weighting="copies"`.
+    """`**weighting` takes three keywords, `row_weights=None`, `dedup_weighting="copies"` and `dedup_value_target="mean"`.
     `row_weights` ([num_samples], tensor or array; finite, >= 0, sum > 0) weighs every row in the loss; it is
     normalised to mean one over the rows trained on (row_weights.normalise_row_weights).
     `dedup_weighting="weight"`: a merged group leaves once with the weight min(count, dedup_max_copies) instead of that
-    many copies.  The metrics gain `row_weights`, the epoch stats `row_weight_sum`."""
-    dedup_weighting, row_weights = _weighting_options("train_network_from_tensors", weighting,
-                                                      {"dedup_weighting": "copies", "row_weights": None}) \
-        if weighting else ("copies", None)
+    many copies.  The metrics gain `row_weights`, the epoch stats `row_weight_sum`.
+    `dedup_value_target="distribution"`: a merged group is trained on the mean of its members'
+    two-hot value distributions in place of the two-hot of their mean value; refused without `dedup_positions`.  The
+    metrics' `position_dedup` gains `value_target`."""
+    dedup_weighting, row_weights, dedup_value_target = _weighting_options(
+        "train_network_from_tensors", weighting,
+        {"dedup_weighting": "copies", "row_weights": None, "dedup_value_target": "mean"}) \
+        if weighting else ("copies", None, "mean")
     dedup = None
+    dist_rows = dist_table = None
     if not (isinstance(dedup_positions, str) and dedup_positions == "off" and type(dedup_max_copies) is int
-            and dedup_max_copies == 1 and isinstance(dedup_weighting, str) and dedup_weighting == "copies"):
+            and dedup_max_copies == 1 and isinstance(dedup_weighting, str) and dedup_weighting == "copies"
+            and isinstance(dedup_value_target, str) and dedup_value_target == "mean"):
         from . import position_dedup as dedup_mod      # the defaults reach nothing here, not even the module
         dedup_mod.dedup_refusal(dedup_positions, dedup_max_copies, policy_draw_weight=policy_draw_weight,
                                 anti_draw_penalty=anti_draw_penalty)
         dedup = dedup_mod if dedup_mod.dedup_on(dedup_positions, dedup_max_copies) else None
         dedup_mod.weighting_on(dedup_weighting, dedup_positions, dedup_max_copies)
+        dedup_mod.value_target_on(dedup_value_target, dedup_positions, dedup_max_copies)
     weigh = weights = weights_info = None
     if row_weights is not None:
         if dedup is not None:
@@ -321,9 +342,13 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
     if dedup is not None:                             # duplicate positions merged once, each rank its own share
         (states, masks, policy, values, soft), info = dedup.merge_duplicate_positions(
             states, masks, policy, values, soft, mode=dedup_positions, max_copies=int(dedup_max_copies),
-            **({} if dedup_weighting == "copies" else {"weighting": dedup_weighting}))
+            **({} if dedup_weighting == "copies" else {"weighting": dedup_weighting}),
+            **({} if dedup_value_target == "mean" else {"value_target": dedup_value_target,
+                                                        "soft_label_alpha": soft_label_alpha}))
         dedup_stats = dedup.stats_of(info)
         n = int(states.shape[0])
+        if "value_dist" in info:                          # the table stays whole, every batch gathers its rows' rows
+            dist_table, dist_rows = info["value_dist"], info["value_dist_row"]
         if "weights" in info:                             # one row per group, min(count, dedup_max_copies) its weight
             from . import row_weights as weigh
             weights = info["weights"]
@@ -356,6 +381,8 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                        anti_draw=float(anti_draw_penalty), draw_w=draw_w, grad_clip_norm=grad_clip_norm,
                        ddp=strategy == "ddp", dev=dev)
     stepper._nominal_rows = bsz                       # the one batch size worth a MIOpen kernel search (see _conv_mode)
+    if dist_rows is not None:
+        stepper.set_value_dist(dist_table)
     for epoch in range(n_epochs):
         perm = torch.randperm(n, device=dev)
         stepper.reset()
@@ -369,7 +396,11 @@ def train_network_from_tensors(model, samples: TensorSelfPlayBatch, *, batch_siz
                 b_states, b_masks, b_policy = transform_samples(states, masks, policy, sym_draw.draw(int(idx.numel())), idx)
             else:
                 b_states, b_masks, b_policy = states.index_select(0, idx), masks.index_select(0, idx), policy.index_select(0, idx)
-            if weights is None:
+            if dist_rows is not None:
+                stepper.step_dist(b_states, b_masks, b_policy, values.index_select(0, idx), soft.index_select(0, idx),
+                                  **({} if weights is None else {"b_weights": weights.index_select(0, idx)}),
+                                  b_dist_row=dist_rows.index_select(0, idx))
+            elif weights is None:
                 stepper.step(b_states, b_masks, b_policy, values.index_select(0, idx), soft.index_select(0, idx))
             else:
                 stepper.step(b_states, b_masks, b_policy, values.index_select(0, idx), soft.index_select(0, idx),
@@ -533,11 +564,15 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
     DESIGN.md section 30); a group leaves as one record with the mean targets of its members and the row weight
     min(sum of d ** a over its members, replay_merge_max_weight), the batches are decoded from the merged records, and
     the row count, the shuffle and the steps are those of the groups.  The metrics gain `replay_window["merge"]` and
-    `row_weights`.  Refused with `policy_draw_weight != 1` and an anti-draw penalty, like `dedup_positions`."""
-    replay_age_decay, merge_mode, merge_max_weight = _weighting_options(
+    `row_weights`.  Refused with `policy_draw_weight != 1` and an anti-draw penalty, like `dedup_positions`.
+    `replay_merge_value_target="mean" | "distribution"`: with "distribution" a merged group is
+    trained on the mean of its members' two-hot value distributions, computed straight from the ring; refused without
+    `replay_merge_positions`.  `replay_window["merge"]` gains `value_target`."""
+    replay_age_decay, merge_mode, merge_max_weight, merge_value_target = _weighting_options(
         "train_network_from_window", weighting,
-        {"replay_age_decay": 1.0, "replay_merge_positions": "off", "replay_merge_max_weight": 1}) \
-        if weighting else (1.0, "off", 1)
+        {"replay_age_decay": 1.0, "replay_merge_positions": "off", "replay_merge_max_weight": 1,
+         "replay_merge_value_target": "mean"}) \
+        if weighting else (1.0, "off", 1, "mean")
     weigh = None
     if not (type(replay_age_decay) is float and replay_age_decay == 1.0):      # 1.0 reaches nothing below
         from . import row_weights as weigh
@@ -545,13 +580,16 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
             weigh = None
     merge_on = False
     if not (isinstance(merge_mode, str) and merge_mode == "off" and type(merge_max_weight) is int
-            and merge_max_weight == 1):                                        # the defaults reach nothing below
+            and merge_max_weight == 1 and isinstance(merge_value_target, str)
+            and merge_value_target == "mean"):                                 # the defaults reach nothing below
         from . import position_dedup as dedup_mod
         from .replay_window import check_max_weight
         if not isinstance(merge_mode, str) or merge_mode not in dedup_mod.MODES:
             raise ValueError(f"replay_merge_positions must be one of {dedup_mod.MODES}, got {merge_mode!r}")
         merge_max_weight = check_max_weight(merge_max_weight)
         merge_on = merge_mode != "off"
+        dedup_mod.value_target_on(merge_value_target, merge_mode, name="replay_merge_value_target",
+                                  needs="replay_merge_positions")
         if merge_on:
             try:
                 dedup_mod.dedup_refusal(merge_mode, 1, policy_draw_weight=policy_draw_weight,
@@ -572,15 +610,20 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
     sym_draw = _SymmetryDraw(symmetry_set, symmetry_seed, rank, dev) if symmetry_augment else None
     train_model = _wrap(model, strategy, dev)
     t0 = time.perf_counter()
-    weights = weights_info = merged = merge_stats = None
+    weights = weights_info = merged = merge_stats = dist_rows = dist_table = None
     if merge_on:                                       # one record per position, its weight the members' (capped) sum
         slots, ages = window.select(int(replay_budget_per_generation), int(replay_seed), return_ages=True)
         t1 = time.perf_counter()
         merged, group_w, info = window.merge_selection(
             slots, mode=merge_mode, ages=None if weigh is None else ages,
-            age_decay=1.0 if weigh is None else float(replay_age_decay), max_weight=merge_max_weight)
+            age_decay=1.0 if weigh is None else float(replay_age_decay), max_weight=merge_max_weight,
+            **({} if merge_value_target == "mean" else {"value_target": merge_value_target,
+                                                        "soft_label_alpha": soft_label_alpha}))
         weights, weights_info = weigh_mod.normalise_row_weights(group_w, source="replay_merge")
-        merge_stats = {k: info[k] for k in dedup_mod.STAT_KEYS + ("mode", "max_weight")}
+        merge_stats = {k: info[k] for k in dedup_mod.STAT_KEYS + ("mode", "max_weight")
+                       + (("value_target",) if "value_target" in info else ())}
+        if "value_dist" in info:                          # the table stays whole, every batch gathers its rows' rows
+            dist_table, dist_rows = info["value_dist"], info["value_dist_row"]
         slots = torch.arange(int(merged.shape[0]), dtype=torch.int64, device=dev)
         merge_stats["merge_sec"] = float(time.perf_counter() - t1)
         del info, group_w, ages
@@ -622,6 +665,8 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
     stepper = _Stepper(model, train_model, optimizer, scheduler, scaler, amp=amp, alpha=alpha,
                        anti_draw=float(anti_draw_penalty), draw_w=draw_w, grad_clip_norm=grad_clip_norm, ddp=False, dev=dev)
     stepper._nominal_rows = bsz                       # the one batch size worth a MIOpen kernel search (see _conv_mode)
+    if dist_rows is not None:
+        stepper.set_value_dist(dist_table)
     for epoch in range(n_epochs):
         perm = torch.randperm(n, device=dev)
         stepper.reset()
@@ -630,7 +675,10 @@ def train_network_from_window(model, window, *, batch_size: int = 512, epochs: i
             tb = time.perf_counter()
             idx = perm[start:min(start + bsz, n)]
             sym = sym_draw.draw(int(idx.numel())) if sym_draw is not None else None
-            if weights is None:
+            if dist_rows is not None:                     # a merge: the weights are there too
+                stepper.step_dist(*gather(slots.index_select(0, idx), sym), b_weights=weights.index_select(0, idx),
+                                  b_dist_row=dist_rows.index_select(0, idx))
+            elif weights is None:
                 stepper.step(*gather(slots.index_select(0, idx), sym))     # unpack + gather + transform in one pass
             else:
                 stepper.step(*gather(slots.index_select(0, idx), sym), b_weights=weights.index_select(0, idx))

@@ -76,6 +76,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dedup-weighting", default="copies", choices=("copies", "weight"),
                     help="weight: a merged position is trained on once with the row weight min(its count, "
                          "--dedup-max-copies) instead of that many copies (see train_stage.py)")
+    ap.add_argument("--dedup-value-target", default="mean", choices=("mean", "distribution"),
+                    help="distribution: a merged position's value target is the mean of its copies' two-hot value "
+                         "distributions instead of the two-hot of their mean value (see train_stage.py)")
     ap.add_argument("--replay-generations", type=int, default=1,
                     help="train on a window of this many past generations kept on the trainer's device as 360-byte records "
                          "(liuzhou_amd/replay_window.py); 1: every iteration trains on its own generation alone")
@@ -91,6 +94,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "(liuzhou_amd/replay_window.py: merge_selection); needs --replay-generations > 1")
     ap.add_argument("--replay-merge-max-weight", type=float, default=1.0,
                     help="cap of a merged position's row weight (the sum of its copies' age weights); a number >= 1")
+    ap.add_argument("--replay-merge-value-target", default="mean", choices=("mean", "distribution"),
+                    help="distribution: a position merged across the window is trained on the mean of its copies' two-hot "
+                         "value distributions, computed from the ring; needs --replay-merge-positions exact or symmetric")
     ap.add_argument("--replay-capacity-rows", type=int, default=0,
                     help="slots of the window's ring; 0: generations x players x games-per-gpu x min(max-game-plies, 144)")
     ap.add_argument("--overlap", type=int, default=0, choices=(0, 1),
@@ -120,6 +126,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                  "use --replay-merge-positions, which merges the window's records")
     if args.dedup_weighting != "copies" and args.dedup_positions == "off":
         ap.error("--dedup-weighting weight needs --dedup-positions exact or symmetric")
+    if args.dedup_value_target != "mean" and args.dedup_positions == "off":
+        ap.error("--dedup-value-target distribution needs --dedup-positions exact or symmetric")
     if not 0.0 < args.replay_age_decay <= 1.0:             # NaN fails both comparisons
         ap.error(f"--replay-age-decay must be in (0, 1], got {args.replay_age_decay!r}")
     if args.replay_age_decay != 1.0 and args.replay_generations <= 1:
@@ -128,6 +136,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error(f"--replay-merge-max-weight must be a finite number >= 1, got {args.replay_merge_max_weight!r}")
     if (args.replay_merge_positions != "off" or args.replay_merge_max_weight != 1.0) and args.replay_generations <= 1:
         ap.error("--replay-merge-positions / --replay-merge-max-weight need a window: --replay-generations > 1")
+    if args.replay_merge_value_target != "mean" and args.replay_merge_positions == "off":
+        ap.error("--replay-merge-value-target distribution needs --replay-merge-positions exact or symmetric")
     if not args.validate and args.validate_evaluator is not None:
         ap.error("--validate-evaluator needs --validate 1")
     return args
@@ -227,6 +237,8 @@ def main(argv=None) -> int:
         if args.replay_merge_positions != "off":
             weighting.update(replay_merge_positions=args.replay_merge_positions,
                              replay_merge_max_weight=args.replay_merge_max_weight)
+            if args.replay_merge_value_target != "mean":
+                weighting["replay_merge_value_target"] = args.replay_merge_value_target
         model, metrics = train_network_from_window(model, window, batch_size=args.batch_size, epochs=args.epochs,
                                                    lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),
                                                    replay_budget_per_generation=args.replay_budget, replay_seed=0,
@@ -244,6 +256,8 @@ def main(argv=None) -> int:
                  if args.dedup_positions != "off" else {})
         if args.dedup_weighting != "copies":
             dedup["dedup_weighting"] = args.dedup_weighting
+        if args.dedup_value_target != "mean":
+            dedup["dedup_value_target"] = args.dedup_value_target
         validation = validate(model, data, generation) if args.validate else None
         model, metrics = train_network_from_tensors(model, data, batch_size=args.batch_size, epochs=args.epochs,
                                                     lr=args.lr, soft_label_alpha=args.soft_label_alpha, device=str(dev),

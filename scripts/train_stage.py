@@ -61,6 +61,10 @@ def parse(argv=None):
                     choices=["copies", "weight"],
                     help="weight: a merged position is trained on once with the row weight min(its count, M) instead of "
                          "that many copies (default copies)")
+    ap.add_argument("--dedup_value_target", "--dedup-value-target", dest="dedup_value_target", default="mean",
+                    choices=["mean", "distribution"],
+                    help="distribution: a merged position's value target is the mean of its copies' two-hot value "
+                         "distributions instead of the two-hot of their mean value (default mean)")
     args, ignored = ap.parse_known_args(argv)
     args.ignored = ignored
     return args
@@ -113,6 +117,11 @@ def main(argv=None) -> int:
             raise SystemExit("--dedup_weighting weight needs --dedup_positions exact or symmetric: without merged "
                              "positions there is nothing to weigh")
         common.update(dedup_weighting=args.dedup_weighting)
+    if args.dedup_value_target != "mean":
+        if args.dedup_positions == "off":
+            raise SystemExit("--dedup_value_target distribution needs --dedup_positions exact or symmetric: without "
+                             "merged positions there is no distribution to form")
+        common.update(dedup_value_target=args.dedup_value_target)
     t0 = time.perf_counter()
     if int(args.streaming_load):
         budget = int(args.replay_budget_per_file)
