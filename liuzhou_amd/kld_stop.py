@@ -1,4 +1,4 @@
-"""KLD-gain early stopping of the tree backend's searches: parameter validation and the refusals.
+"""KLD-gain early stopping of the tree backend's searches: parameter validation.
 
 The rule (Leela Chess Zero's, per game at the root): every `kld_stop_interval` simulations the root's visit distribution
 is compared with the one `kld_stop_interval` simulations earlier.  With o_k the visits of child k in the game's snapshot,
@@ -15,7 +15,7 @@ puct_shape.py.
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, Mapping, NamedTuple, Optional
+from typing import Any, Dict, Mapping, NamedTuple
 
 INTERVAL_DEFAULT = 100
 PARAM_KEYS = ("kld_stop_threshold", "kld_stop_interval", "kld_stop_min_simulations")
@@ -89,25 +89,3 @@ def kld_stop_kwargs(kld_stop_threshold=0.0, kld_stop_interval=INTERVAL_DEFAULT, 
 def kld_stop_meta(kwargs: Mapping[str, Any]) -> Dict[str, Any]:
     """metadata["kld_stop"] from the keyword arguments of an `on` configuration."""
     return parse_kld_stop(**{k: kwargs[k] for k in PARAM_KEYS}).meta()
-
-
-def kld_stop_refusal(*, batch_k=1, several_networks=False, fused=True, gumbel_considered=0,
-                     persistent: Optional[bool] = None) -> Optional[str]:
-    """Why a configuration cannot run the rule (None: it can).  What the playout cap refuses -- the check kernel sits
-    between the launches of the fused launch-pair search and lowers the budget its CAP kernels read -- plus the Gumbel
-    root search, whose Sequential Halving schedule is a function of a fixed budget."""
-    if persistent is None:
-        from .tree_engine import _persistent_default
-        persistent = _persistent_default()
-    return ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
-            "several networks in one search" if several_networks else
-            "an external evaluator (split-phase path)" if not fused else
-            "the persistent search kernel (LZ_TREE_PERSISTENT)" if persistent else
-            "the Gumbel root search (its Sequential Halving schedule is a function of a fixed budget)"
-            if int(gumbel_considered) > 0 else None)
-
-
-def refuse_backend(on: bool, search_backend: Optional[str]) -> None:
-    if on and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"KLD-gain early stopping needs the tree backend, not the root-PUCT search ({search_backend!r}): "
-                         "the rule lowers the per-game budget of the tree search")

@@ -15,26 +15,16 @@ kld_stop.py.
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, List, Mapping, Optional
+from typing import Any, Dict, List, Mapping
 
 import numpy as np
+
+from .kld_stop import _number
 
 # the int64[4] block of lz_tree_move_pick, in its order; all of them add up over parts, chunks, workers and ranks
 COUNTER_KEYS = ("move_pick_applied", "move_pick_cut_visits", "move_pick_cut_value", "move_pick_changed")
 PARAM_KEYS = ("move_visit_offset", "move_value_cutoff", "temperature_halflife")
 VALUE_CUTOFF_MAX = 2.0          # values live in [-1, 1]: a cutoff of 2 cuts nothing
-
-
-def _number(name: str, value, what: str) -> float:
-    if isinstance(value, bool):
-        raise ValueError(f"{name} must be {what}, got {value!r}")
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be {what}, got {value!r}") from None
-    if not math.isfinite(v):
-        raise ValueError(f"{name} must be {what} (finite), got {v}")
-    return v
 
 
 def move_pick_on(move_visit_offset=0.0, move_value_cutoff=0.0) -> bool:
@@ -73,22 +63,6 @@ def move_pick_meta(kwargs: Mapping[str, Any]) -> Dict[str, Any]:
     return {"visit_offset": float(kwargs.get("move_visit_offset", 0.0)),
             "value_cutoff": float(kwargs.get("move_value_cutoff", 0.0)),
             "temperature_halflife": float(kwargs.get("temperature_halflife", 0.0))}
-
-
-def move_pick_refusal(*, sample_moves: bool = True, gumbel_considered: int = 0) -> Optional[str]:
-    """Why the re-pick cannot run with these settings (None: it can)."""
-    if int(gumbel_considered) > 0:
-        return "the Gumbel root search (its pick is the Sequential Halving winner and ignores temperatures by definition)"
-    if not bool(sample_moves):
-        return "sample_moves=False (the most visited move is played already; there is no sampled move to re-pick)"
-    return None
-
-
-def refuse_backend(on: bool, search_backend: Optional[str]) -> None:
-    if on and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"move_visit_offset / move_value_cutoff / temperature_halflife need the tree backend, not the "
-                         f"root-PUCT search ({search_backend!r}): they act on the tree search's root children and its "
-                         "per-ply move temperature")
 
 
 def temperature_table(temperature_init: float, temperature_final: float, temperature_threshold: int,

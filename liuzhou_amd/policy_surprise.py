@@ -1,5 +1,5 @@
 """Policy surprise weighting of training rows in the tree backend's self-play (KataGo's policySurpriseDataWeight; Wu,
-"Accelerating Self-Play Learning in Go", and the later methods notes): parameter validation, refusals, the root-prior
+"Accelerating Self-Play Learning in Go", and the later methods notes): parameter validation, the root-prior
 helper and the counters.
 
 The rule (tests/policy_surprise.py restates it in numpy):
@@ -33,7 +33,7 @@ arithmetic in csrc/lz_surprise.h; wave_tail.WaveTail launches them).  What lives
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, Optional, Sequence
+from typing import Any, Dict, Sequence
 
 # the int64[3] block of lz_wave_surprise_resample, in its order, then the sum of the surprises in micro-nats; all of them
 # add up over chunks, workers and ranks
@@ -55,27 +55,6 @@ def policy_surprise_on(alpha) -> bool:
     if math.isnan(v) or v < 0.0 or v > 1.0:
         raise ValueError(f"policy_surprise_weight must be a number in [0, 1] (0 = off; KataGo uses 0.5), got {v}")
     return v > 0.0
-
-
-def policy_surprise_refusal(*, device_tail: bool = True, reseat: bool = False, prior_evaluator: bool = False,
-                            batch_k: int = 1) -> Optional[str]:
-    """Why policy surprise weighting cannot run in this configuration, or None.  `batch_k` > 1 is allowed: the legacy
-    waves return the same `model_input` / `legal_mask` / `policy_dense` per slot, and the feature reads nothing else."""
-    if not device_tail:
-        return "the host loop (device_tail=False): the surprises and the resampling live in the per-ply device tail"
-    if reseat:
-        return ("the in-kernel re-seat (reseat=True): it clears step_counts inside the step kernel, before the rows of "
-                "the game are weighed")
-    if prior_evaluator:
-        return ("a PriorEvaluator: it returns priors of its own making, there is no plain network to evaluate the root "
-                "with")
-    return None
-
-
-def refuse_backend(on: bool, search_backend: Optional[str]) -> None:
-    if on and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"policy surprise weighting needs the tree backend, not the root-PUCT search "
-                         f"({search_backend!r}): it compares the tree search's policy target with the network prior")
 
 
 def root_prior(net, search, fused: bool):

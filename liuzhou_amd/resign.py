@@ -15,8 +15,9 @@ launches them).  What lives here is pure Python and needs no GPU, next to value_
 """
 from __future__ import annotations
 
-import math
-from typing import Any, Dict, Mapping, Optional, Sequence
+from typing import Any, Dict, Mapping, Sequence
+
+from .kld_stop import _integer, _number
 
 STREAKS = ("side", "ply")
 # the int64[8] block of lz_wave_resign_book, in its order; all of them add up over chunks, workers and ranks
@@ -25,25 +26,6 @@ COUNTER_KEYS = ("resigned_games", "resigned_black", "resigned_white", "playthrou
 # derived from the sums above (they do NOT add up: derive_counters() recomputes them after every merge)
 DERIVED_KEYS = ("resign_avg_ply", "resign_plies_saved_estimate")
 PARAM_KEYS = ("resign_threshold", "resign_min_moves", "resign_consecutive", "resign_playthrough_fraction", "resign_streak")
-
-
-def _number(name: str, value, what: str) -> float:
-    if isinstance(value, bool):
-        raise ValueError(f"{name} must be {what}, got {value!r}")
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be {what}, got {value!r}") from None
-    if not math.isfinite(v):
-        raise ValueError(f"{name} must be {what} (finite), got {v}")
-    return v
-
-
-def _integer(name: str, value, lo: int, what: str) -> int:
-    v = _number(name, value, what)
-    if v != int(v) or int(v) < lo:
-        raise ValueError(f"{name} must be {what}, got {value!r}")
-    return int(v)
 
 
 def resign_on(resign_threshold=0.0, resign_min_moves=10, resign_consecutive=3, resign_playthrough_fraction=0.1,
@@ -100,9 +82,3 @@ def derive_counters(counters: Dict[str, Any]) -> Dict[str, Any]:
 def counters_from_block(block: Sequence[int]) -> Dict[str, int]:
     """The device's int64[8] block -> mcts_counters entries (sums and derived)."""
     return derive_counters({k: int(v) for k, v in zip(COUNTER_KEYS, block)})
-
-
-def refuse_backend(on: bool, search_backend: Optional[str]) -> None:
-    if on and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"resignation needs the tree backend, not the root-PUCT search ({search_backend!r}): it reads "
-                         "the tree search's root values in the per-ply device tail")

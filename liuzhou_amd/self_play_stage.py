@@ -31,6 +31,7 @@ from typing import Any, Callable, Dict, Iterator, List, Optional, Sequence, Tupl
 import torch
 
 from .distributed import split_games, worker_seed
+from .search_rules import SearchRules, merged_meta, persistent_default, read_meta
 from .self_play_storage import estimate_bytes_per_sample, plan_sample_ranges, save_self_play_payload, slice_batch_cpu
 from .self_play_types import SelfPlayV1Stats
 from .self_play_worker import merge_self_play_stats, merge_target_summaries, summarize_scalar_targets
@@ -78,16 +79,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     summaries: Dict[str, List[Dict[str, Any]]] = {"value_target_summary": [], "soft_value_target_summary": [],
                                                   "mixed_value_target_summary": []}
     bps_num = bps_den = 0
-    cap_meta: Optional[Dict[str, Any]] = None
-    forced_meta: Optional[Dict[str, Any]] = None
-    gumbel_meta: Optional[Dict[str, Any]] = None
-    td_meta: Optional[Dict[str, Any]] = None
-    solver_meta = False
-    shape_meta: Optional[Dict[str, Any]] = None
-    resign_meta: Optional[Dict[str, Any]] = None
-    kld_meta: Optional[Dict[str, Any]] = None
-    pick_meta: Optional[Dict[str, Any]] = None
-    surprise_weight: Optional[float] = None
+    rule_meta: Dict[str, Any] = {}          # search_rules.RULE_SPECS: the first worker's settings of every rule that ran
     for path in worker_manifest_paths:
         wm = _load(path)
         if not isinstance(wm, dict) or str(wm.get("payload_format", "")).strip().lower() != "v1_worker_chunk_manifest":
@@ -102,35 +94,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
                 files.append(name)
                 sizes.append(int(ws[i]) if i < len(ws) else 0)
         stats.append(stats_from_payload(wm.get("stats", {})))
-        wcap = (wm.get("metadata") or {}).get("playout_cap")
-        if isinstance(wcap, dict) and cap_meta is None:
-            cap_meta = {"fast_simulations": int(wcap.get("fast_simulations", 0)), "full_prob": float(wcap.get("full_prob", 1.0))}
-        wforced = (wm.get("metadata") or {}).get("forced_playouts")
-        if isinstance(wforced, dict) and forced_meta is None:
-            forced_meta = {"k": float(wforced.get("k", 0.0))}
-        wgumbel = (wm.get("metadata") or {}).get("gumbel")
-        if isinstance(wgumbel, dict) and gumbel_meta is None:
-            gumbel_meta = {"considered": int(wgumbel.get("considered", 0)), "c_visit": float(wgumbel.get("c_visit", 50.0)),
-                           "c_scale": float(wgumbel.get("c_scale", 1.0))}
-        wtd = (wm.get("metadata") or {}).get("value_target")
-        if isinstance(wtd, dict) and td_meta is None:
-            td_meta = {"td_lambda": float(wtd.get("td_lambda", 1.0))}
-        solver_meta = solver_meta or bool((wm.get("metadata") or {}).get("mcts_solver"))
-        wsh = (wm.get("metadata") or {}).get("puct_shape")
-        if isinstance(wsh, dict) and shape_meta is None:
-            shape_meta = {k: wsh.get(k) for k in ("fpu_reduction", "fpu_root_reduction", "cpuct_log", "cpuct_base")}
-        wrs = (wm.get("metadata") or {}).get("resign")
-        if isinstance(wrs, dict) and resign_meta is None:
-            resign_meta = {k: wrs.get(k) for k in ("threshold", "min_moves", "consecutive", "playthrough_fraction", "streak")}
-        wkl = (wm.get("metadata") or {}).get("kld_stop")
-        if isinstance(wkl, dict) and kld_meta is None:
-            kld_meta = {k: wkl.get(k) for k in ("threshold", "interval", "min_simulations")}
-        wmp = (wm.get("metadata") or {}).get("move_pick")
-        if isinstance(wmp, dict) and pick_meta is None:
-            pick_meta = {k: wmp.get(k) for k in ("visit_offset", "value_cutoff", "temperature_halflife")}
-        wps = (wm.get("metadata") or {}).get("policy_surprise")
-        if isinstance(wps, dict) and surprise_weight is None:
-            surprise_weight = float(wps.get("weight", 0.0))
+        read_meta(rule_meta, wm.get("metadata") or {})
         for key, bucket in summaries.items():
             if isinstance(wm.get(key), dict):
                 bucket.append(wm[key])
@@ -145,33 +109,7 @@ def merge_worker_manifests(worker_manifest_paths: Sequence[str], *, output_path:
     meta.update({"self_play_target_samples_per_shard": int(target_samples_per_shard),
                  "self_play_chunk_target_bytes": int(chunk_target_bytes)})
     meta.update({k: merge_target_summaries(v) for k, v in summaries.items()})
-    if cap_meta is not None:            # playout cap: its settings and the searches of every kind over all workers
-        meta["playout_cap"] = {**cap_meta, **{k: int(merged.mcts_counters.get(k, 0))
-                                              for k in ("full_searches", "fast_searches")}}
-    if forced_meta is not None:         # forced playouts: k, forced descents and pruned visits over all workers
-        meta["forced_playouts"] = {**forced_meta, **{k: int(merged.mcts_counters.get(k, 0))
-                                                     for k in ("forced_playouts", "pruned_visits")}}
-    if gumbel_meta is not None:         # Gumbel root search: its settings and the searches that ran the rule, all workers
-        meta["gumbel"] = {**gumbel_meta, "gumbel_searches": int(merged.mcts_counters.get("gumbel_searches", 0))}
-    if td_meta is not None:             # TD(lambda) value targets: the lambda the rows' value_targets were blended with
-        meta["value_target"] = td_meta
-    if solver_meta:                     # MCTS-Solver: on (its counters travel in the merged mcts_counters)
-        meta["mcts_solver"] = True
-    if shape_meta is not None:          # first-play urgency / visit-scaled cpuct: the four values the searches ran with
-        meta["puct_shape"] = shape_meta
-    if resign_meta is not None:         # resignation: its settings, the resigned and the play-through games of all workers
-        from .resign import COUNTER_KEYS, DERIVED_KEYS
-        meta["resign"] = {**resign_meta, **{k: int(merged.mcts_counters.get(k, 0)) for k in COUNTER_KEYS + DERIVED_KEYS}}
-    if kld_meta is not None:            # KLD-gain early stopping: its settings, the stopped searches of all workers
-        from .kld_stop import COUNTER_KEYS as KLD_COUNTER_KEYS
-        meta["kld_stop"] = {**kld_meta, **{k: int(merged.mcts_counters.get(k, 0)) for k in KLD_COUNTER_KEYS}}
-    if pick_meta is not None:           # move selection: its settings, and the re-pick's counters where the re-pick ran
-        from .move_pick import COUNTER_KEYS as PICK_COUNTER_KEYS
-        meta["move_pick"] = {**pick_meta, **{k: int(merged.mcts_counters[k]) for k in PICK_COUNTER_KEYS
-                                             if k in merged.mcts_counters}}
-    if surprise_weight is not None:     # policy surprise weighting: its weight, what the resampling did over all workers
-        from .policy_surprise import surprise_meta
-        meta["policy_surprise"] = surprise_meta(surprise_weight, merged.mcts_counters)
+    meta.update(merged_meta(rule_meta, merged.mcts_counters))      # settings + the rules' counters over all workers
     manifest = {"payload_format": "v1_sharded_manifest", "version": 1, "num_samples": int(sum(sizes)),
                 "num_shards": len(files), "shard_files": files, "shard_sizes": sizes,
                 "chunk_target_bytes": int(chunk_target_bytes), "avg_bytes_per_sample": int(bps_num // max(1, bps_den)),
@@ -192,87 +130,19 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
                         search_backend: str = "cuda_root", portable_mcts_backend: str = "python",
                         portable_cpp_threads: int = 1, policy_target_temperature: Optional[float] = None,
                         policy_target_prior_pseudocount: float = 0.0, sample_moves: bool = True,
-                        eval_symmetry: Any = "none", worker_fn: Optional[Callable[..., Dict[str, Any]]] = None,
-                        in_process: bool = False, playout_cap_fast_simulations: int = 0,
-                        playout_cap_full_prob: float = 1.0, forced_playouts_k: float = 0.0,
-                        gumbel_considered: int = 0, gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0,
-                        value_target_lambda: float = 1.0,
-                        mcts_solver: bool = False, fpu_reduction: Optional[float] = None,
-                        fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
-                        cpuct_base: float = 19652.0, resign_threshold: float = 0.0, resign_min_moves: int = 10,
-                        resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
-                        resign_streak: str = "side", kld_stop_threshold: float = 0.0, kld_stop_interval: int = 100,
-                        kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
-                        move_value_cutoff: float = 0.0,
-                        temperature_halflife: float = 0.0,
-                        policy_surprise_weight: float = 0.0) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
+                        worker_fn: Optional[Callable[..., Dict[str, Any]]] = None,
+                        in_process: bool = False, **search_options) -> Tuple[SelfPlayV1Stats, Dict[str, Any]]:
     """Play `num_games` split over `devices` (one spawned process per device, each owning its GPU) and write
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
-    `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `eval_symmetry` (tree backend: "none",
-    "random" or a fixed id 0..7) reaches the workers only when it is not "none"; so do `playout_cap_fast_simulations` /
-    `playout_cap_full_prob` (tree backend, playout cap randomization) only when the cap is on, and `forced_playouts_k`
-    (tree backend, forced playouts and policy target pruning) only when it is > 0, and `gumbel_considered` /
-    `gumbel_c_visit` / `gumbel_c_scale` (tree backend, Gumbel root search with Sequential Halving; a Gumbel search never
-    mixes Dirichlet noise into the root priors, whatever `add_dirichlet_noise` says) only when gumbel_considered > 0, and
-    `value_target_lambda` (tree backend, TD(lambda) value targets from the searches' root values; 1 = off) only when < 1,
-    and `mcts_solver` (tree backend, the MCTS-Solver) only when it is on, and `fpu_reduction` / `fpu_root_reduction` /
-    `cpuct_log` / `cpuct_base` (tree backend, first-play urgency and the visit-scaled exploration constant) only when one
-    of the two halves is on, and `resign_threshold` / `resign_min_moves` / `resign_consecutive` /
-    `resign_playthrough_fraction` / `resign_streak` (tree backend, resignation with play-through calibration) only when
-    resign_threshold < 0, and `kld_stop_threshold` / `kld_stop_interval` / `kld_stop_min_simulations` (tree backend, KLD-gain
-    early stopping of the searches) only when kld_stop_threshold > 0, and `move_visit_offset` / `move_value_cutoff` (tree
-    backend, visit-offset / value-cutoff move selection) only when one of the two is above 0, `temperature_halflife` (tree
-    backend, decaying move temperature) only when it is, and `policy_surprise_weight` (tree backend, policy surprise
-    weighting of training rows; 0 = off) only when it is > 0."""
-    from .policy_surprise import policy_surprise_on, refuse_backend as surprise_refuse_backend
-    surprise = policy_surprise_on(policy_surprise_weight)
-    surprise_refuse_backend(surprise, search_backend)
-    from .move_pick import move_pick_kwargs, move_pick_refusal, refuse_backend as pick_refuse_backend
-    pick = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
-    pick_refuse_backend(bool(pick), search_backend)
-    from .kld_stop import kld_stop_refusal, parse_kld_stop, refuse_backend as kld_refuse_backend
-    kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
-    kld_refuse_backend(kld.on, search_backend)
-    from .resign import refuse_backend, resign_kwargs
-    resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
-                           resign_streak)
-    refuse_backend(bool(resign), search_backend)
-    from .tree_engine import puct_shape_refusal
-    shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
-                               cpuct_base=cpuct_base, gumbel_considered=gumbel_considered, search_backend=search_backend)
-    solver = bool(mcts_solver)
-    if solver and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"the MCTS-Solver needs the tree backend, not the root-PUCT search ({search_backend!r}): it marks "
-                         "proven results in the search tree")
-    from .gumbel import gumbel_on
-    from .tree_engine import forced_playouts_on, gumbel_refusal, playout_cap_on
-    from .value_target import td_lambda_on
-    td = td_lambda_on(value_target_lambda)
-    if td and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"TD(lambda) value targets need the tree backend, not the root-PUCT search ({search_backend!r}): "
-                         "they blend the tree search's root values")
-    gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
-    if "move_visit_offset" in pick:
-        why = move_pick_refusal(sample_moves=sample_moves, gumbel_considered=gumbel_considered if gumbel else 0)
-        if why is not None:
-            raise ValueError(f"visit-offset / value-cutoff move selection is not supported with {why}")
-    if kld.on:
-        why = kld_stop_refusal(gumbel_considered=gumbel_considered if gumbel else 0)
-        if why is not None:
-            raise ValueError(f"KLD-gain early stopping is not supported with {why}")
-    if gumbel:
-        if str(search_backend).strip().lower() not in ("portable", "tree"):
-            raise ValueError(f"the Gumbel root search needs the tree backend, not the root-PUCT search ({search_backend!r})")
-        why = gumbel_refusal(forced_playouts_k=forced_playouts_k, policy_target_temperature=policy_target_temperature,
-                             policy_target_prior_pseudocount=policy_target_prior_pseudocount)
-        if why is not None:
-            raise ValueError(f"the Gumbel root search is not supported with {why}")
-    forced = forced_playouts_on(forced_playouts_k)
-    if forced and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"forced playouts need the tree backend, not the root-PUCT search ({search_backend!r})")
-    cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
-    if cap and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"playout cap randomization needs the tree backend, not the root-PUCT search ({search_backend!r})")
+    `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `search_options`: the optional rules
+    of the tree backend's search (symmetric evaluation, playout cap, forced playouts, Gumbel root search, TD(lambda)
+    targets, MCTS-Solver, PUCT shape, resignation, KLD-gain stop, move re-pick, temperature half-life, policy surprise),
+    under the names and defaults of `search_rules.SearchRules.parse`; described there.  They are validated and refused
+    here, and reach the workers only when they are on."""
+    rules = SearchRules.parse(mcts_simulations, **search_options)
+    rules.refuse(search_backend=search_backend, sample_moves=sample_moves, persistent=persistent_default(),
+                 policy_target_temperature=policy_target_temperature,
+                 policy_target_prior_pseudocount=policy_target_prior_pseudocount)
     if worker_fn is None:
         from .self_play_worker import run_self_play_worker as worker_fn
     shards = split_games(int(num_games), len(devices))
@@ -306,15 +176,7 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
             policy_target_prior_pseudocount=float(policy_target_prior_pseudocount), sample_moves=bool(sample_moves),
             target_samples_per_shard=int(target_samples_per_shard), chunk_target_bytes=int(chunk_target_bytes),
             chunk_output_dir=out_dir, chunk_file_prefix=f"{stem}.w{idx:02d}", chunk_file_ext=ext,
-            **({} if eval_symmetry == "none" else {"eval_symmetry": eval_symmetry}),
-            **({"playout_cap_fast_simulations": int(playout_cap_fast_simulations),
-                "playout_cap_full_prob": float(playout_cap_full_prob)} if cap else {}),
-            **({"forced_playouts_k": float(forced_playouts_k)} if forced else {}),
-            **({"gumbel_considered": int(gumbel_considered), "gumbel_c_visit": float(gumbel_c_visit),
-                "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
-            **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-            **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign, **kld.kwargs(), **pick,
-            **({"policy_surprise_weight": float(policy_surprise_weight)} if surprise else {}))
+            **rules.kwargs())
 
     started = time.perf_counter()
     rows: List[Dict[str, Any]] = []

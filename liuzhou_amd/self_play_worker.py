@@ -588,104 +588,17 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                          chunk_file_ext: str = ".pt", sparse_ply: int = 1, sparse_top_k: int = 8,
                          search_backend: str = "cuda_root", portable_mcts_backend: str = "python",
                          portable_cpp_threads: int = 1, policy_target_temperature: Optional[float] = None,
-                         policy_target_prior_pseudocount: float = 0.0, eval_symmetry="none",
-                         playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
-                         forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
-                         gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0,
-                         mcts_solver: bool = False, fpu_reduction: Optional[float] = None,
-                         fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
-                         cpuct_base: float = 19652.0, resign_threshold: float = 0.0, resign_min_moves: int = 10,
-                         resign_consecutive: int = 3, resign_playthrough_fraction: float = 0.1,
-                         resign_streak: str = "side", kld_stop_threshold: float = 0.0, kld_stop_interval: int = 100,
-                         kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
-                         move_value_cutoff: float = 0.0, temperature_halflife: float = 0.0,
-                         policy_surprise_weight: float = 0.0) -> Dict[str, Any]:
-    """`eval_symmetry` (tree backend only): "none", "random" or an id 0..7, see tree_engine.PortableTreeMCTS.
-    `playout_cap_fast_simulations` / `playout_cap_full_prob` (tree backend only): playout cap randomization, see
-    tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["playout_cap"] when on.
-    `forced_playouts_k` (tree backend only; 0 = off): forced playouts and policy target pruning, see
-    tree_engine.self_play_tree_gpu; recorded in the manifests' metadata["forced_playouts"] when on.
-    `gumbel_considered` m (tree backend only; 0 = off), `gumbel_c_visit`, `gumbel_c_scale`: Gumbel root search with
-    Sequential Halving, see tree_engine.self_play_tree_gpu; a Gumbel search never mixes Dirichlet noise into the root
-    priors, whatever `add_dirichlet_noise` says.  Recorded in the manifests' metadata["gumbel"] when on.
-    `value_target_lambda` (tree backend only; 1 = off): TD(lambda) value targets from the searches' root values, see
-    tree_engine.self_play_tree_gpu; they travel in `value_targets`.  Recorded in the manifests'
-    metadata["value_target"] when on.
-    `mcts_solver` (tree backend only): the MCTS-Solver, see tree_engine.self_play_tree_gpu.  Recorded in the manifests'
-    metadata["mcts_solver"] when on.
-    `fpu_reduction` (None = off), `fpu_root_reduction`, `cpuct_log` (0 = off), `cpuct_base` (tree backend only): first-play
-    urgency and the visit-scaled exploration constant, see tree_engine.self_play_tree_gpu.  The four values are recorded in
-    the manifests' metadata["puct_shape"] when either half is on.
-    `resign_threshold` (tree backend only; 0 = off), `resign_min_moves`, `resign_consecutive`,
-    `resign_playthrough_fraction`, `resign_streak`: resignation with play-through calibration, see
-    tree_engine.self_play_tree_gpu.  The five values are recorded in the manifests' metadata["resign"] when on.
-    `kld_stop_threshold` (tree backend only; 0 = off), `kld_stop_interval`, `kld_stop_min_simulations` (None = the
-    interval): KLD-gain early stopping of the searches, see tree_engine.self_play_tree_gpu.  The three values are recorded
-    in the manifests' metadata["kld_stop"] when on.
-    `move_visit_offset` / `move_value_cutoff` (tree backend only; 0 = off): visit-offset / value-cutoff move selection;
-    `temperature_halflife` (tree backend only; 0 = off): the move temperature decays with this half-life below
-    `temperature_threshold`; see tree_engine.self_play_tree_gpu.  The three values are recorded in the manifests'
-    metadata["move_pick"] when any of them is on.
-    `policy_surprise_weight` (tree backend only; 0 = off, in [0, 1]): policy surprise weighting of training rows, see
-    tree_engine.self_play_tree_gpu.  The weight and what the resampling did (games, rows, rows_replaced, mean_surprise) are
-    recorded in the manifests' metadata["policy_surprise"] when on."""
-    from .move_pick import move_pick_kwargs, move_pick_meta, move_pick_refusal, refuse_backend as pick_refuse_backend
-    pick = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
-    pick_refuse_backend(bool(pick), search_backend)
-    if "move_visit_offset" in pick:
-        from .gumbel import gumbel_on as _gumbel_on
-        why = move_pick_refusal(sample_moves=sample_moves, gumbel_considered=gumbel_considered
-                                if _gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale) else 0)
-        if why is not None:
-            raise ValueError(f"visit-offset / value-cutoff move selection is not supported with {why}")
-    from .kld_stop import kld_stop_refusal, parse_kld_stop, refuse_backend as kld_refuse_backend
-    kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
-    kld_refuse_backend(kld.on, search_backend)
-    if kld.on:
-        from .gumbel import gumbel_on as _gumbel_on
-        why = kld_stop_refusal(gumbel_considered=gumbel_considered
-                               if _gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale) else 0)
-        if why is not None:
-            raise ValueError(f"KLD-gain early stopping is not supported with {why}")
-    from .policy_surprise import policy_surprise_on, refuse_backend as refuse_surprise_backend
-    surprise = policy_surprise_on(policy_surprise_weight)
-    refuse_surprise_backend(surprise, search_backend)
-    from .resign import refuse_backend, resign_kwargs, resign_meta
-    resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
-                           resign_streak)
-    refuse_backend(bool(resign), search_backend)
-    from .tree_engine import puct_shape_refusal
-    shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
-                               cpuct_base=cpuct_base, gumbel_considered=gumbel_considered, search_backend=search_backend)
-    solver = bool(mcts_solver)
-    if solver and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"the MCTS-Solver needs the tree backend, not the root-PUCT search ({search_backend!r}): it marks "
-                         "proven results in the search tree")
-    from .gumbel import gumbel_on
-    from .tree_engine import forced_playouts_on, gumbel_refusal, parse_eval_symmetry, playout_cap_on
-    from .value_target import td_lambda_on
-    td = td_lambda_on(value_target_lambda)
-    if td and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"TD(lambda) value targets need the tree backend, not the root-PUCT search ({search_backend!r}): "
-                         "they blend the tree search's root values")
-    gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
-    if gumbel:
-        if str(search_backend).strip().lower() not in ("portable", "tree"):
-            raise ValueError(f"the Gumbel root search needs the tree backend, not the root-PUCT search ({search_backend!r})")
-        why = gumbel_refusal(forced_playouts_k=forced_playouts_k, policy_target_temperature=policy_target_temperature,
-                             policy_target_prior_pseudocount=policy_target_prior_pseudocount)
-        if why is not None:
-            raise ValueError(f"the Gumbel root search is not supported with {why}")
-    forced = forced_playouts_on(forced_playouts_k)
-    if forced and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"forced playouts need the tree backend, not the root-PUCT search ({search_backend!r})")
-    eval_symmetry = parse_eval_symmetry(eval_symmetry)
-    cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
-    if cap and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"playout cap randomization needs the tree backend, not the root-PUCT search ({search_backend!r})")
-    if eval_symmetry != "none" and str(search_backend).strip().lower() not in ("portable", "tree"):
-        raise ValueError(f"eval_symmetry={eval_symmetry!r} needs the tree backend: the root-PUCT search "
-                         f"({search_backend!r}) evaluates children without the symmetry hook")
+                         policy_target_prior_pseudocount: float = 0.0, **search_options) -> Dict[str, Any]:
+    """`search_options`: the optional rules of the tree backend's search, under the names and defaults of
+    `search_rules.SearchRules.parse` and described there (symmetric evaluation, playout cap, forced playouts, Gumbel root
+    search, TD(lambda) targets, MCTS-Solver, PUCT shape, resignation, KLD-gain stop, move re-pick, temperature half-life,
+    policy surprise).  They are validated and refused before a device is touched; the rules that are on are recorded in
+    the manifests' metadata (`SearchRules.meta`)."""
+    from .search_rules import SearchRules, persistent_default
+    rules = SearchRules.parse(mcts_simulations, **search_options)
+    rules.refuse(search_backend=search_backend, sample_moves=sample_moves, persistent=persistent_default(),
+                 policy_target_temperature=policy_target_temperature,
+                 policy_target_prior_pseudocount=policy_target_prior_pseudocount)
     try:
         t_worker = time.perf_counter()
         torch.manual_seed(int(seed))
@@ -749,18 +662,7 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                                           policy_target_temperature=policy_target_temperature,
                                           policy_target_prior_pseudocount=float(policy_target_prior_pseudocount),
                                           seed=rng_seed, collect_timing=os.environ.get("LZ_WORKER_TIMING", "1") != "0", row_log=row_log,
-                                          eval_symmetry=eval_symmetry,
-                                          playout_cap_fast_simulations=int(playout_cap_fast_simulations) if cap else 0,
-                                          playout_cap_full_prob=float(playout_cap_full_prob) if cap else 1.0,
-                                          **({"forced_playouts_k": float(forced_playouts_k)} if forced else {}),
-                                          **({"gumbel_considered": int(gumbel_considered),
-                                              "gumbel_c_visit": float(gumbel_c_visit),
-                                              "gumbel_c_scale": float(gumbel_c_scale)} if gumbel else {}),
-                                          **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-                                          **({"mcts_solver": True} if solver else {}), **shape.kwargs(), **resign,
-                                          **kld.kwargs(), **pick,
-                                          **({"policy_surprise_weight": float(policy_surprise_weight)} if surprise else {}),
-                                          **common)
+                                          **rules.kwargs(), **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
                                     sparse_top_k=int(sparse_top_k), row_log=row_log, **common)
@@ -776,19 +678,7 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                        # PyTorch (a shape the kernel is not built for; `evaluator_reason` says which)
                        "evaluator": evaluator_name, **({"evaluator_reason": evaluator_why} if evaluator_why else {}),
                        "streamed": bool(stream), **({"stream_fallback": stream_fallback} if stream_fallback else {}),
-                       **({"eval_symmetry": eval_symmetry} if eval_symmetry != "none" else {}),
-                       **({"playout_cap": {"fast_simulations": int(playout_cap_fast_simulations),
-                                           "full_prob": float(playout_cap_full_prob)}} if cap else {}),
-                       **({"forced_playouts": {"k": float(forced_playouts_k)}} if forced else {}),
-                       **({"gumbel": {"considered": int(gumbel_considered), "c_visit": float(gumbel_c_visit),
-                                      "c_scale": float(gumbel_c_scale)}} if gumbel else {}),
-                       **({"value_target": {"td_lambda": float(value_target_lambda)}} if td else {}),
-                       **({"mcts_solver": True} if solver else {}),
-                       **({"puct_shape": shape.meta()} if shape.on else {}),
-                       **({"resign": resign_meta(resign)} if resign else {}),
-                       **({"kld_stop": kld.meta()} if kld.on else {}),
-                       **({"move_pick": move_pick_meta(pick)} if pick else {}),
-                       **({"policy_surprise": {"weight": float(policy_surprise_weight)}} if surprise else {})}
+                       **rules.meta()}
         if stream:
             os.makedirs(chunk_dir, exist_ok=True)
             return stream_worker_shard(lambda log: run_once(games, row_log=log)[1], device=dev, worker_idx=int(worker_idx),

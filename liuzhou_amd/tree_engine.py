@@ -12,7 +12,6 @@ prepare roots -> evaluate -> complete, then sims x (select -> evaluate -> comple
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 import sys
 import time
@@ -29,17 +28,16 @@ from .gumbel import considered_table, gumbel_on
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput, TOTAL_ACTION_DIM, states_to_model_input, \
     encode_actions_fast
 from .net_hip import DescArray, FusedNet, LzNetDesc, MAX_MULTI_NETS, multi_compatible
-from .puct_shape import CPUCT_BASE_DEFAULT, CPUCT_TABLE_LEN, PuctShape, cpuct_table, parse_puct_shape
+from .puct_shape import CPUCT_BASE_DEFAULT, CPUCT_TABLE_LEN, cpuct_table, parse_puct_shape
 from .self_play_types import SelfPlayV1Stats
 from .streams import CAPTURE_MODE
 from .trajectory_buffer import TensorSelfPlayBatch, TensorTrajectoryBuffer
-from .kld_stop import INTERVAL_DEFAULT as KLD_INTERVAL_DEFAULT, KldStop, kld_stop_refusal, parse_kld_stop
-from .move_pick import (counters_from_block as move_pick_counters, move_pick_kwargs, move_pick_on, move_pick_refusal,
-                        temperature_table)
-from .policy_surprise import counters_from_block as surprise_counters_from_block
-from .policy_surprise import policy_surprise_on, policy_surprise_refusal, root_prior
-from .resign import counters_from_block, resign_kwargs
-from .value_target import td_lambda_on
+from .kld_stop import KldStop, parse_kld_stop
+from .move_pick import temperature_table
+from .policy_surprise import counters_from_block as surprise_counters_from_block, root_prior
+from .resign import counters_from_block
+from .search_rules import (SearchRules, engine_counters, forced_playouts_on, parse_eval_symmetry,
+                           persistent_default as _persistent_default, playout_cap_on, search_simulations)
 
 MAX_CHILDREN = 72
 OUT_CAP = 80
@@ -72,38 +70,6 @@ class LzTreeDesc(C.Structure):
                [(n, C.c_void_p) for n in ("kld_snapshot", "kld_budget", "kld_stops", "kld_saved", "kld_trace")] + \
                [("puct_shape", C.c_int32), ("cpuct_table_len", C.c_int32), ("fpu_reduction", C.c_double),
                 ("fpu_root_reduction", C.c_double), ("cpuct_table", C.c_void_p)]
-
-
-def playout_cap_on(fast_simulations: int, full_prob: float, sims: int) -> bool:
-    """Validate the playout cap's parameters against the search's `sims`: on when 0 < fast_simulations < sims, off for
-    fast_simulations == 0; anything else (and full_prob outside [0, 1]) is a ValueError."""
-    F, p = int(fast_simulations), float(full_prob)
-    if not 0.0 <= p <= 1.0:
-        raise ValueError(f"playout_cap_full_prob must lie in [0, 1], got {full_prob}")
-    if F == 0:
-        return False
-    if not 0 < F < int(sims):
-        raise ValueError(f"playout_cap_fast_simulations must be 0 (off) or in (0, mcts_simulations={int(sims)}), got {F}")
-    return True
-
-
-def parse_eval_symmetry(value) -> "str | int":
-    """`eval_symmetry` of the tree search: "none", "random" or a fixed element id 0..7 (liuzhou_amd/symmetry.py).  Env
-    LZ_EVAL_SYMMETRY=random / none / 0..7 overrides the argument (A/B runs)."""
-    env = os.environ.get("LZ_EVAL_SYMMETRY", "").strip().lower()
-    if env:
-        value = env
-    if isinstance(value, str):
-        v = value.strip().lower()
-        if v in ("none", "random"):
-            return v
-        if v.isdigit():
-            value = int(v)
-        else:
-            raise ValueError(f"eval_symmetry must be 'none', 'random' or an id 0..7, got {value!r}")
-    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 8:
-        raise ValueError(f"eval_symmetry must be 'none', 'random' or an id 0..7, got {value!r}")
-    return int(value)
 
 
 class LzTreeWaveDesc(C.Structure):
@@ -191,72 +157,6 @@ def samples_per_launch_pass(net) -> int:
     ch, flags = int(net.desc.channels), int(net.desc.flags)
     groups = int(net.desc.max_blocks) if int(net.desc.max_blocks) > 0 else (512 if (ch == 64 and flags & 1) else 256)
     return groups * (16 if (ch == 64 and not flags & 1) else 8)
-
-
-def gumbel_refusal(*, batch_k=1, several_networks=False, fused=True, forced_playouts_k=0.0,
-                   policy_target_temperature=None, policy_target_prior_pseudocount=0.0) -> Optional[str]:
-    """Why a configuration cannot run the Gumbel root search (None: it can).  What the cap and the forced playouts refuse,
-    plus the forced playouts themselves (two rules for the same root level) and the visit-count target options (the
-    target is not made of visits any more)."""
-    return ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
-            "several networks in one search" if several_networks else
-            "an external evaluator (split-phase path)" if not fused else
-            "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else
-            "forced playouts (two rules for the same root level)" if float(forced_playouts_k) > 0.0 else
-            "policy_target_temperature (the training target is not made of visit counts)"
-            if policy_target_temperature is not None else
-            "policy_target_prior_pseudocount > 0 (the training target is not made of visit counts)"
-            if float(policy_target_prior_pseudocount) > 0.0 else None)
-
-
-def solver_refusal(*, batch_k=1, several_networks=False, fused=True) -> Optional[str]:
-    """Why a configuration cannot run the MCTS-Solver (None: it can): the marks are made by the expand step of the fused
-    launch-pair search, which the legacy waves, the multi-network search, the host-side split protocol and the persistent
-    kernel do not run."""
-    return ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
-            "several networks in one search" if several_networks else
-            "an external evaluator (split-phase path)" if not fused else
-            "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else None)
-
-
-def puct_shape_refusal(*, fpu_reduction=None, fpu_root_reduction=None, cpuct_log=0.0, cpuct_base=CPUCT_BASE_DEFAULT,
-                       batch_k=1, fused=True, gumbel_considered=0, search_backend="tree",
-                       persistent: Optional[bool] = None) -> PuctShape:
-    """Validate the PUCT shape parameters (first-play urgency, visit-scaled cpuct) and the configuration they are asked
-    for; returns the parsed PuctShape.  ValueError for a non-finite or negative value, cpuct_base <= 0, fpu_root_reduction
-    without fpu_reduction, and -- only when the shape is on -- for the Gumbel root search, batch_k > 1, the persistent kernel,
-    an external evaluator and the root-PUCT backend: the shaped score lives in the select step of the fused launch-pair
-    tree search, which none of them runs."""
-    shape = parse_puct_shape(fpu_reduction, fpu_root_reduction, cpuct_log, cpuct_base)
-    if not shape.on:
-        return shape
-    persistent = _persistent_default() if persistent is None else bool(persistent)
-    why = ("the root-PUCT search (it needs the tree backend)"
-           if str(search_backend).strip().lower() not in ("portable", "tree") else
-           "the Gumbel root search (its root level has a rule of its own)" if int(gumbel_considered) > 0 else
-           "batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
-           "an external evaluator (split-phase path)" if not fused else
-           "the persistent search kernel (LZ_TREE_PERSISTENT)" if persistent else None)
-    if why is not None:
-        raise ValueError(f"first-play urgency / the visit-scaled cpuct are not supported with {why}")
-    return shape
-
-
-def search_simulations(num_simulations) -> int:
-    """Validate the simulations of a search: an integer >= 1.  A root expanded and never searched has no visited child, and
-    the read-out (lz_tree_finish) has no policy for it at a temperature above 1e-6 -- the reference raises "no policy mass"
-    there; every smaller budget the searches can end with (playout cap, KLD-gain early stopping) is >= 1 too."""
-    if isinstance(num_simulations, bool) or int(num_simulations) != num_simulations or int(num_simulations) < 1:
-        raise ValueError(f"num_simulations must be an integer >= 1 (a root without a visit has no policy), got {num_simulations!r}")
-    return int(num_simulations)
-
-
-def forced_playouts_on(k) -> bool:
-    """Validate `forced_playouts_k`: 0 = off, a positive finite number = on; negative or non-finite is a ValueError."""
-    k = float(k)
-    if not math.isfinite(k) or k < 0.0:
-        raise ValueError(f"forced_playouts_k must be a finite number >= 0 (0 = off), got {k}")
-    return k > 0.0
 
 
 class TreeEngine:
@@ -910,10 +810,6 @@ class TreeEngine:
         return self.phase_ticks
 
 
-def _persistent_default() -> bool:
-    return os.environ.get("LZ_TREE_PERSISTENT", "0").strip().lower() in ("1", "on", "true")
-
-
 def persistent_search_available(net, batch_k: int = 1) -> bool:
     """Does the search of `net` run as the one-launch-per-move kernel (csrc/lz_search.hip; opt-in)?  Then one engine over
     all games already puts two workgroups on every CU, and the two-stream split (DualStreamTreeMCTS) has nothing to add."""
@@ -952,23 +848,16 @@ class PortableTreeMCTS:
                  reuse_factor: float = -1.0, policy_target_temperature: Optional[float] = None,
                  policy_target_prior_pseudocount: float = 0.0, batch_k: int = 1, seed: int = 12345,
                  game_offset: int = 0, game_stride: Optional[int] = None, trace: bool = False,
-                 collect_timing: bool = False, compact_evals: Optional[bool] = None, eval_symmetry="none",
-                 segment_games: Optional[int] = None, multi_launch: bool = True, fast_simulations: int = 0,
-                 full_prob: float = 1.0, forced_playouts_k: float = 0.0, gumbel_considered: int = 0,
-                 gumbel_c_visit: float = 50.0, gumbel_c_scale: float = 1.0, solver: bool = False,
-                 fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
-                 cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT,
-                 cpuct_table_len: int = CPUCT_TABLE_LEN, kld_stop: Optional[KldStop] = None,
-                 move_visit_offset: float = 0.0, move_value_cutoff: float = 0.0) -> None:
+                 collect_timing: bool = False, compact_evals: Optional[bool] = None,
+                 segment_games: Optional[int] = None, multi_launch: bool = True,
+                 cpuct_table_len: int = CPUCT_TABLE_LEN, rules: Optional[SearchRules] = None, **rule_options) -> None:
         """`net` a list of K networks with `segment_games` (a multiple of 16, num_games = K * segment_games): slot g is
         searched with network g // segment_games, every segment in the same simulation steps (compact lists always on).
         FusedNets of one layout share one network launch per simulation (lz_tree_search_multi); any other mix runs the
         split-phase protocol, each segment's rows through its own evaluator.  Not with batch_k > 1, eval_symmetry or the
         persistent kernel.  `multi_launch=False` takes the split-phase path for FusedNets too (parity tests).  A single
         network behaves as below.
-        `eval_symmetry`: "none" (default), "random" or a fixed element id 0..7 -- every leaf is evaluated as
-        sigma_k(leaf) and the heads are mapped back (parse_eval_symmetry, TreeEngine.set_eval_symmetry); not with
-        batch_k > 1 (ValueError).  `compact_evals` (fused network only): per simulation only the leaves that need the network are evaluated
+        `compact_evals` (fused network only): per simulation only the leaves that need the network are evaluated
         (`TreeEngine(compact_evals=True)`); True = in every search; None = the engine is built for both forms when a launch
         of all slots is at least two network passes per CU (C3: eight) and uses the lists for the searches that say so
         (`search_batch(compact=True)`, the runner's hint that the wave is draining) -- env LZ_TREE_COMPACT=0 / 1 overrides.
@@ -983,127 +872,43 @@ class PortableTreeMCTS:
         `reuse_tree`: keep the played child's subtree between consecutive search_batch calls on the same games
         (the reference's portable self-play does, v1/python/portable_self_play.py:191); the arenas then hold
         (1 + reuse_factor) * sims nodes per game (reuse_factor < 0: as much as a third of the free memory allows).  `policy_target_*`: portable_mcts.py:690-700.
-        `fast_simulations` / `full_prob`: playout cap randomization (on when 0 < fast_simulations < num_simulations): each
-        search of game g at ply t is full (num_simulations, root noise) when uniform(seed, g, t, purpose 3) < full_prob,
-        else fast (fast_simulations, no root noise).  The mask of the last search is `full_search` (uint8[B]); parity
-        runs inject one through `injected_full_search`.  Searches then always use the compact lists; not with batch_k > 1,
-        several networks, an external evaluator or the persistent kernel (ValueError).
-        `forced_playouts_k` k (0 = off): forced playouts and policy target pruning (Wu 2019, section 3.2) in the searches
-        whose root-noise switch is on (every search without the cap, the full ones with it): a root child with N > 0 and
-        N^2 < k P n is visited before PUCT is asked, and the training target (policy_dense) is formed from the pruned
-        visits; the move pick and the kept subtree use the raw visits.  `forced_counts` (int64[2]): forced descents and
-        pruned visits so far.  Refused where the cap is refused (ValueError).
-        `gumbel_considered` m (0 = off; the paper uses 16), `gumbel_c_visit`, `gumbel_c_scale`: Gumbel root search with
-        Sequential Halving (Danihelka et al., ICLR 2022; gumbel.py) in the searches whose root-noise
-        switch is on (every search without the cap, the full ones with it).  The root samples m children without
-        replacement by g + log P (Gumbel-top-k), spends the simulations on them by Sequential Halving with
-        g + log P + sigma(completed Q), plays the winner and trains on softmax(log P + sigma(completed Q)); below the
-        root nothing changes.  A Gumbel search never mixes Dirichlet noise into the root priors, whatever
-        `add_dirichlet_noise` says: the Gumbel variates are its exploration; temperatures, `sample_moves` and the pick
-        uniform do not apply to it either (opening random moves keep precedence).  The variates come from the per-game
-        RNG (GameRng.gumbel_into); parity runs inject their own through `injected_gumbel` ([B, <= OUT_CAP]).
-        `gumbel_searches` counts the searches that ran the rule.  Refused where the cap is refused, and with
-        forced playouts, `policy_target_temperature` and `policy_target_prior_pseudocount` > 0 (ValueError).
-        `solver`: MCTS-Solver (TreeEngine.set_solver).  Exact results -- eliminations, draws by the
-        move or no-capture limit -- are marked on the edges and carried up as far as they decide the parent; decided children
-        stop being searched, and the played move never throws a proven win away (nor picks a proven loss next to another
-        move).  The outputs gain `root_proven`; `solver_counts` sums proofs, decided roots and changed picks.  Composes with
-        the cap, forced playouts, Gumbel, symmetric evaluation, shared leaves and tree reuse; refused where the cap is.
-        `fpu_reduction` (None = off, 0.0 = on without a reduction), `fpu_root_reduction` (None = fpu_reduction), `cpuct_log`
-        (0 = off), `cpuct_base`: first-play urgency and the visit-scaled exploration constant (TreeEngine.set_puct_shape,
-        DESIGN.md section 16) on every level that PUCT decides.  Either half works without the other.  Composes with the cap,
-        forced playouts (the pruning rule then uses c(root visits)), the solver, several networks in one launch, symmetric
-        evaluation, shared leaves and tree reuse; refused with the Gumbel root search, batch_k > 1, an external evaluator
-        and the persistent kernel (ValueError).  Such a search runs the one-wave tree step at every launch size.
-        `kld_stop` (kld_stop.parse_kld_stop(threshold, interval, min_simulations); None or threshold 0 = off): KLD-gain early
-        stopping.  Every `interval` simulations a game's root visit distribution is compared with the
-        one `interval` simulations earlier, and from `min_simulations` on the game's search ends once the gain per
-        simulation is below the threshold: its budget becomes the check's simulation + 1, and its tree is bit for bit the
-        one a search of that many simulations builds.  `sim_budget` (int32[B]) is refilled before every search -- with
-        `num_simulations`, or by the playout cap's draw, which the rule may only lower -- and `last_sim_budget` is what the
-        search left in it; `kld_counts` (int64[2]) sums the stopped searches and the simulations they did not run; parity
-        runs hand every game its budget through `injected_sim_budget` (int32[B], honoured by any search that owns a budget
-        array, after the cap's draw).  Searches then always use the compact lists.  Refused where the cap is refused and
-        with the Gumbel root search (ValueError).
-        `move_visit_offset` o (>= 0), `move_value_cutoff` c (in [0, 2]; both 0 = off): visit-offset / value-cutoff move
-        selection (move_pick.py).  Where the finish sampled a game's move from the visits, one kernel
-        behind it (TreeEngine.move_pick) draws the move again with the same uniform from the children that keep more than o
-        visits and whose mean value is within c of the most visited child's; the solver pick, if on, still has the last
-        word.  Training targets and every other output stay as the finish wrote them.  `move_pick_counts` (int64[4]):
-        games re-picked, children cut by the offset, children cut by the value test, picks changed.  Composes with
-        everything but the Gumbel root search and `sample_moves=False` (ValueError)."""
+        `rules` (a search_rules.SearchRules), or the same options under the constructor's own names in `rule_options`
+        (`eval_symmetry`, `fast_simulations` / `full_prob`, `forced_playouts_k`, `gumbel_considered` / `gumbel_c_visit` /
+        `gumbel_c_scale`, `solver`, `fpu_reduction` / `fpu_root_reduction` / `cpuct_log` / `cpuct_base`, `kld_stop` (a
+        KldStop), `move_visit_offset` / `move_value_cutoff`): the optional rules of the search, described in
+        search_rules; a configuration one of them cannot run in is a ValueError before anything is allocated.  What they
+        leave on the engine: `full_search` (uint8[B], the playout cap's mask of the last search) and `cap_counts`,
+        `sim_budget` / `last_sim_budget` (int32[B], refilled before every search by the cap's draw or with
+        `num_simulations`, lowered by the KLD-gain rule), `forced_counts`, `gumbel_searches`, `solver_counts`,
+        `kld_counts`, `move_pick_counts`; parity runs inject their own draws through `injected_full_search`,
+        `injected_sim_budget` (honoured after the cap's draw) and `injected_gumbel` ([B, <= OUT_CAP])."""
         search_simulations(num_simulations)
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.multi = segment_games is not None
-        self.solver = bool(solver)
-        if self.solver:
-            why = solver_refusal(batch_k=batch_k, several_networks=self.multi or len(self.nets) != 1,
-                                 fused=isinstance(self.nets[0], FusedNet))
-            if why is not None:
-                raise ValueError(f"the MCTS-Solver is not supported with {why}")
-        self.gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
-        self.gumbel_considered = int(gumbel_considered)
-        self.gumbel_c_visit, self.gumbel_c_scale = float(gumbel_c_visit), float(gumbel_c_scale)
-        if self.gumbel:
-            why = gumbel_refusal(batch_k=batch_k, several_networks=self.multi or len(self.nets) != 1,
-                                 fused=isinstance(self.nets[0], FusedNet), forced_playouts_k=forced_playouts_k,
-                                 policy_target_temperature=policy_target_temperature,
-                                 policy_target_prior_pseudocount=policy_target_prior_pseudocount)
-            if why is not None:
-                raise ValueError(f"the Gumbel root search is not supported with {why}")
-        self.forced = forced_playouts_on(forced_playouts_k)
-        self.forced_playouts_k = float(forced_playouts_k)
-        if self.forced:
-            why = ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
-                   "several networks in one search" if self.multi or len(self.nets) != 1 else
-                   "an external evaluator (split-phase path)" if not isinstance(self.nets[0], FusedNet) else
-                   "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else None)
-            if why is not None:
-                raise ValueError(f"forced playouts are not supported with {why}")
-        self.kld_stop = parse_kld_stop() if kld_stop is None else parse_kld_stop(*kld_stop)
-        self.kld = self.kld_stop.on
-        if self.kld:
-            why = kld_stop_refusal(batch_k=batch_k, several_networks=self.multi or len(self.nets) != 1,
-                                   fused=isinstance(self.nets[0], FusedNet),
-                                   gumbel_considered=gumbel_considered if self.gumbel else 0)
-            if why is not None:
-                raise ValueError(f"KLD-gain early stopping is not supported with {why}")
-        self.move_pick = move_pick_on(move_visit_offset, move_value_cutoff)
-        self.move_visit_offset, self.move_value_cutoff = float(move_visit_offset), float(move_value_cutoff)
-        if self.move_pick:
-            why = move_pick_refusal(sample_moves=sample_moves, gumbel_considered=gumbel_considered if self.gumbel else 0)
-            if why is not None:
-                raise ValueError(f"visit-offset / value-cutoff move selection is not supported with {why}")
-        self.cap = playout_cap_on(fast_simulations, full_prob, num_simulations)
-        self.fast_simulations, self.full_prob = int(fast_simulations), float(full_prob)
-        if self.cap:
-            why = ("batch_k > 1 (legacy waves)" if int(batch_k) > 1 else
-                   "several networks in one search" if self.multi or len(self.nets) != 1 else
-                   "an external evaluator (split-phase path)" if not isinstance(self.nets[0], FusedNet) else
-                   "the persistent search kernel (LZ_TREE_PERSISTENT)" if _persistent_default() else None)
-            if why is not None:
-                raise ValueError(f"playout cap randomization is not supported with {why}")
-            compact_evals = True           # a dense launch would evaluate every slot at every simulation: nothing saved
-        if self.kld:
-            compact_evals = True           # likewise: a stopped game must leave the network launches
+        if rules is not None and rule_options:
+            raise TypeError(f"pass `rules` or the options by name, not both: {sorted(rule_options)}")
+        self.rules = r = SearchRules.parse_engine(num_simulations, **rule_options) if rules is None else rules
+        self.fused_multi = self.multi and bool(multi_launch) and multi_compatible(self.nets)
+        self.fused = isinstance(self.nets[0], FusedNet) and (not self.multi or self.fused_multi)
+        r.refuse(batch_k=batch_k, several_networks=self.multi or len(self.nets) != 1, fused=self.fused,
+                 persistent=_persistent_default(), sample_moves=sample_moves,
+                 policy_target_temperature=policy_target_temperature,
+                 policy_target_prior_pseudocount=policy_target_prior_pseudocount)
+        self.cap, self.forced, self.gumbel, self.solver = r.cap, r.forced, r.gumbel, r.solver
+        self.kld_stop, self.kld, self.move_pick, self.puct_shape = r.kld, r.kld_on, r.repick, r.shape
         if not self.multi and len(self.nets) != 1:
             raise ValueError("several networks need segment_games")
         if self.multi:
             if len(self.nets) * int(segment_games) != int(num_games):
                 raise ValueError(f"{len(self.nets)} networks x segment_games={segment_games} != num_games={num_games}")
-            if int(batch_k) > 1 or parse_eval_symmetry(eval_symmetry) != "none":
+            if int(batch_k) > 1 or r.symmetric:
                 raise ValueError("several networks in one search: batch_k = 1 and eval_symmetry='none' only")
             if sum(isinstance(n, PriorEvaluator) for n in self.nets) not in (0, len(self.nets)):
                 raise ValueError("PriorEvaluators and networks cannot share one search")
             compact_evals = True
         net = self.nets[0]
         self.net, self.sims = net, int(num_simulations)
-        self.fused_multi = self.multi and bool(multi_launch) and multi_compatible(self.nets)
-        self.fused = isinstance(net, FusedNet) and (not self.multi or self.fused_multi)
         self._desc_array = DescArray(self.nets) if self.fused_multi else None
-        self.puct_shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction,
-                                             cpuct_log=cpuct_log, cpuct_base=cpuct_base, batch_k=batch_k,
-                                             fused=self.fused, gumbel_considered=gumbel_considered if self.gumbel else 0)
         self.reuse_tree = bool(reuse_tree)
         self.batch_k = max(1, int(batch_k))
         env_c = os.environ.get("LZ_TREE_COMPACT", "").strip()
@@ -1117,7 +922,7 @@ class PortableTreeMCTS:
         if compact_evals is None:
             compact_evals = self.fused and int(num_games) >= 2 * samples_per_launch_pass(net)
             self.compact_default = compact_evals and self.batch_k == 1 and shares_leaves(num_games)
-        if self.cap or self.kld:
+        if self.cap or self.kld:     # a dense launch would evaluate every slot at every simulation, stopped games included
             compact_evals = self.compact_default = True
         self.engine = TreeEngine(num_games, num_simulations, device, exploration_weight,
                                  reuse_factor=float(reuse_factor) if self.reuse_tree else 0.0, batch_k=self.batch_k,
@@ -1126,11 +931,11 @@ class PortableTreeMCTS:
         if trace:
             self.engine.enable_trace()
         if self.forced:
-            self.engine.set_forced_playouts(self.forced_playouts_k)
+            self.engine.set_forced_playouts(r.forced_k)
         self._pruned_total = torch.zeros((1,), dtype=torch.int64, device=self.engine.device)   # sum of pruned_visits
         self.injected_gumbel: Optional[torch.Tensor] = None      # parity runs: [B, <= OUT_CAP] instead of the RNG's draws
         if self.gumbel:
-            self.engine.set_gumbel(self.gumbel_considered, self.gumbel_c_visit, self.gumbel_c_scale, int(num_simulations))
+            self.engine.set_gumbel(r.gumbel_considered, r.gumbel_c_visit, r.gumbel_c_scale, int(num_simulations))
         self._roots_decided = torch.zeros((1,), dtype=torch.int64, device=self.engine.device)
         if self.solver:
             self.engine.set_solver(True)
@@ -1146,7 +951,7 @@ class PortableTreeMCTS:
                                   (n.device if isinstance(n, FusedNet) else next(n.parameters()).device) for n in self.nets]
             self._eval_device = self._eval_devices[0]
         self.rng = GameRng(num_games, device, seed=seed, game_offset=game_offset, game_stride=game_stride)
-        self.eval_symmetry = parse_eval_symmetry(eval_symmetry)
+        self.eval_symmetry = r.eval_symmetry
         self.engine.set_eval_symmetry(self.eval_symmetry, seed, self.rng.game, self.rng.ply)
         self._game0 = self.rng.game.clone()
         self._uniforms = torch.zeros((self.engine.B,), dtype=torch.float32, device=self.engine.device)
@@ -1280,9 +1085,9 @@ class PortableTreeMCTS:
             full = self.injected_full_search.to(device=self.engine.device, dtype=torch.bool)
         else:
             self.rng.uniform_into(self._cap_u, PURPOSE_PLAYOUT_CAP)
-            full = self._cap_u.double() < self.full_prob
+            full = self._cap_u.double() < self.rules.cap_full_prob
         self.full_search.copy_(full)
-        self.sim_budget.copy_(torch.where(full, self.sims, self.fast_simulations))
+        self.sim_budget.copy_(torch.where(full, self.sims, self.rules.cap_fast_simulations))
         if self.injected_sim_budget is not None:
             self.sim_budget.copy_(self.injected_sim_budget.to(device=self.engine.device, dtype=torch.int32))
         live = torch.ones_like(full) if active is None else active.to(device=full.device, dtype=torch.bool)
@@ -1647,7 +1452,7 @@ class PortableTreeMCTS:
             if self.forced:
                 self._pruned_total.add_(e.pruned_visits.sum(dtype=torch.int64))
             if self.move_pick:            # re-pick of the sampled moves; in front of the solver, which keeps the last word
-                e.move_pick(temps, uniforms, self.move_visit_offset, self.move_value_cutoff, force_uniform_random_mask,
+                e.move_pick(temps, uniforms, self.rules.move_visit_offset, self.rules.move_value_cutoff, force_uniform_random_mask,
                             self.sample_moves, self._move_pick_counts)
             if self.solver:               # a proven win is played, a proven loss is not while another move exists
                 e.solver_pick(force_uniform_random_mask)
@@ -1669,6 +1474,9 @@ class DualStreamTreeMCTS:
     engine, hipGraph and stream, one half's tree kernel overlaps the other half's network kernel.  The network runs
     4-wave workgroups of 8 samples (two per CU, `FusedNet(half_workgroups=True)`), so that a half batch alone still
     covers every CU.  Results are identical to one engine over all games (games are independent)."""
+
+    SUMMED = ("leaf_evals", "consumed_evals", "cap_counts", "gumbel_searches", "forced_counts", "solver_counts",
+              "kld_counts", "move_pick_counts")
 
     def __init__(self, model, num_games: int, num_simulations: int, device, num_parts: Optional[int] = None, **kw) -> None:
         search_simulations(num_simulations)
@@ -1701,21 +1509,16 @@ class DualStreamTreeMCTS:
             self.parts.append(PortableTreeMCTS(base.variant(half_workgroups=half), n, num_simulations, dev,
                                                game_offset=a, game_stride=self.B, **kw))
         self.sims = int(num_simulations)
+        first = self.parts[0]
+        self.rules, self.cap, self.forced, self.gumbel, self.solver = first.rules, first.cap, first.forced, first.gumbel, first.solver
+        self.kld, self.kld_stop, self.move_pick, self.puct_shape = first.kld, first.kld_stop, first.move_pick, first.puct_shape
         # playout cap: one full / fast mask over all games, each part writing its slice (the wave tail reads the whole)
-        self.cap = self.parts[0].cap
-        self.forced = self.parts[0].forced
-        self.gumbel = self.parts[0].gumbel
-        self.solver = self.parts[0].solver
-        self.puct_shape = self.parts[0].puct_shape
-        self.move_pick = self.parts[0].move_pick
         self.full_search = None
         if self.cap:
             self.full_search = torch.zeros((self.B,), dtype=torch.uint8, device=dev)
             for (a, b), part in zip(self.bounds, self.parts):
                 part.bind_full_search(self.full_search[a:b])
         # KLD-gain early stopping: likewise one budget array over all games, each part refilling and lowering its slice
-        self.kld = self.parts[0].kld
-        self.kld_stop = self.parts[0].kld_stop
         self.sim_budget = None
         self.injected_sim_budget: Optional[torch.Tensor] = None    # parity runs: int32[B], cut for the parts at every search
         if self.kld:
@@ -1743,34 +1546,6 @@ class DualStreamTreeMCTS:
         self.overlap_ratio: Optional[float] = None          # union / _t_serial of the last watched search (statistics)
 
     @property
-    def leaf_evals(self) -> int:
-        return sum(p.leaf_evals for p in self.parts)
-
-    @property
-    def cap_counts(self) -> torch.Tensor:
-        return sum(p.cap_counts for p in self.parts)
-
-    @property
-    def gumbel_searches(self) -> torch.Tensor:
-        return sum(p.gumbel_searches for p in self.parts)
-
-    @property
-    def forced_counts(self) -> torch.Tensor:
-        return sum(p.forced_counts for p in self.parts)
-
-    @property
-    def solver_counts(self) -> torch.Tensor:
-        return sum(p.solver_counts for p in self.parts)
-
-    @property
-    def kld_counts(self) -> torch.Tensor:
-        return sum(p.kld_counts for p in self.parts)
-
-    @property
-    def move_pick_counts(self) -> torch.Tensor:
-        return sum(p.move_pick_counts for p in self.parts)
-
-    @property
     def last_sim_budget(self) -> Optional[torch.Tensor]:
         if self.kld:
             return self.sim_budget
@@ -1779,10 +1554,6 @@ class DualStreamTreeMCTS:
     @property
     def last_full_search(self) -> Optional[torch.Tensor]:
         return self.full_search.bool() if self.cap else None
-
-    @property
-    def consumed_evals(self) -> int:
-        return sum(p.consumed_evals for p in self.parts)
 
     def prepare(self, state: GpuStateBatch) -> None:
         for (a, b), part in zip(self.bounds, self.parts):
@@ -1931,6 +1702,10 @@ class DualStreamTreeMCTS:
                                      **({"root_proven": torch.cat([o.root_proven for o in outs], dim=0)} if self.solver else {}))
 
 
+for _name in DualStreamTreeMCTS.SUMMED:                  # counters of the whole batch: the parts' sums
+    setattr(DualStreamTreeMCTS, _name, property(lambda self, n=_name: sum(getattr(p, n) for p in self.parts)))
+
+
 class SteadyStateTreeSelfPlay:
     """B games, always full (finished games are re-seated); one step = one searched move for every game."""
 
@@ -2027,18 +1802,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        policy_target_prior_pseudocount: float = 0.0, reuse_tree: bool = True,
                        reuse_factor: float = -1.0, dual_stream: Optional[bool] = None, continuous_waves: bool = True,
                        device_tail: bool = True, batch_k: int = 1, evaluator: str = "auto", seed: int = 12345,
-                       collect_timing: bool = False, row_log=None, eval_symmetry="none",
-                       playout_cap_fast_simulations: int = 0, playout_cap_full_prob: float = 1.0,
-                       forced_playouts_k: float = 0.0, gumbel_considered: int = 0, gumbel_c_visit: float = 50.0,
-                       gumbel_c_scale: float = 1.0, value_target_lambda: float = 1.0, mcts_solver: bool = False,
-                       fpu_reduction: Optional[float] = None, fpu_root_reduction: Optional[float] = None,
-                       cpuct_log: float = 0.0, cpuct_base: float = CPUCT_BASE_DEFAULT, resign_threshold: float = 0.0,
-                       resign_min_moves: int = 10, resign_consecutive: int = 3,
-                       resign_playthrough_fraction: float = 0.1, resign_streak: str = "side",
-                       kld_stop_threshold: float = 0.0, kld_stop_interval: int = KLD_INTERVAL_DEFAULT,
-                       kld_stop_min_simulations: Optional[int] = None, move_visit_offset: float = 0.0,
-                       move_value_cutoff: float = 0.0, temperature_halflife: float = 0.0,
-                       policy_surprise_weight: float = 0.0) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
+                       collect_timing: bool = False, row_log=None,
+                       **search_options) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
     `model` may also be a `PriorEvaluator` (states -> priors over the 220 actions + values, the reference's own
@@ -2048,146 +1813,33 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     kernel.  `seed`: key of the per-game counter RNG (noise, sampled moves); game ids are the runner's game numbers.
     `row_log` (finished_log.FinishedRowLog, the streaming worker): the rows of every game leave through the log when the
     game ends and the returned batch is empty; needs `device_tail` and `continuous_waves`.
-    `eval_symmetry`: "none" (default), "random" or an id 0..7 -- each leaf evaluated under a board symmetry
-    (PortableTreeMCTS); not with batch_k > 1.
-    `playout_cap_fast_simulations` F / `playout_cap_full_prob` p: playout cap randomization (on when 0 < F <
-    mcts_simulations): a move's search is full with probability p (drawn per game and ply) and records a training row,
-    otherwise it is a fast search of F simulations without root noise that only advances the game.  `num_positions`
-    counts recorded rows, `avg_game_length` plies; mcts_counters gain full_searches / fast_searches /
-    recorded_positions.  Fused network and batch_k = 1 only (ValueError otherwise).
-    `forced_playouts_k` k (0 = off): forced playouts and policy target pruning (PortableTreeMCTS) in every search that
-    records a row; mcts_counters gain forced_playouts / pruned_visits.  Fused network and batch_k = 1 only (ValueError
-    otherwise).
-    `gumbel_considered` m (0 = off; the paper uses 16), `gumbel_c_visit`, `gumbel_c_scale`: Gumbel root search with
-    Sequential Halving (PortableTreeMCTS) in every search that records a row: the move is the Sequential Halving winner
-    and the row's policy is softmax(log P + sigma(completed Q)).  Such a search never mixes Dirichlet noise into the root
-    priors, whatever `add_dirichlet_noise` says: the Gumbel variates are its exploration.  mcts_counters gain
-    gumbel_searches.  Fused network and batch_k = 1 only; not with forced playouts, `policy_target_temperature` or
-    `policy_target_prior_pseudocount` > 0 (ValueError).
-    `value_target_lambda` (1 = off): TD(lambda) value targets (value_target.py).  With Q_t = the root value of the game's
-    t-th search from Black's frame (every search counts, the playout cap's fast ones and a terminal root's too), y_L = the
-    result and y_t = (1 - lambda) Q_t + lambda y_{t+1}, the row recorded at ply t gets value_target = sign * y_t instead of
-    sign * result; `soft_value_targets` stay as they are.  Needs `device_tail` (ValueError otherwise: the host loop keeps
-    the reference's finalisation); composes with everything else.
-    `mcts_solver`: MCTS-Solver (PortableTreeMCTS `solver`) in every search: proven wins, draws and losses are marked in the
-    tree, decided children stop being searched and the played move never throws a proven win away.  mcts_counters gain
-    solver_proofs / solver_roots_decided / solver_pick_overrides.  Fused network and batch_k = 1 only (ValueError
-    otherwise); composes with everything else.
-    `fpu_reduction` (None = off), `fpu_root_reduction` (None = fpu_reduction), `cpuct_log` (0 = off), `cpuct_base`: first-play
-    urgency and the visit-scaled exploration constant (PortableTreeMCTS) in every search.  Fused
-    network and batch_k = 1 only, not with the Gumbel root search or the persistent kernel (ValueError); composes with
-    everything else.  Off, nothing is allocated and every output is byte-identical.
-    `resign_threshold` (0 = off; on in [-1, 0)), `resign_min_moves`, `resign_consecutive`, `resign_playthrough_fraction`,
-    `resign_streak` ("side" / "ply"): resignation with play-through calibration (resign.py).  A game
-    whose searches' root values have been <= the threshold `resign_consecutive` times in a row (the mover's own searches
-    with "side") in the movement phases, from ply `resign_min_moves` on, ends as a loss of the side to move; the row of
-    that ply stays recorded.  A seeded share `resign_playthrough_fraction` of the games (a pure function of `seed` and the
-    game number) never resigns and measures the false positives.  mcts_counters gain resigned_games / resigned_black /
-    resigned_white / playthrough_games / playthrough_would_resign / playthrough_false_positive / resign_avg_ply /
-    resign_plies_saved_estimate (and the two sums the last two derive from).  Needs `device_tail` (ValueError otherwise);
-    composes with everything else.  Off, nothing is allocated or launched and every output is byte-identical.
-    `kld_stop_threshold` (0 = off), `kld_stop_interval` (100), `kld_stop_min_simulations` (None = the interval): KLD-gain
-    early stopping (kld_stop.py, PortableTreeMCTS `kld_stop`): a game's search ends once its root
-    visit distribution gains less than the threshold per simulation between two checks `kld_stop_interval` simulations
-    apart.  mcts_counters gain kld_stopped_searches / kld_simulations_saved.  Fused network and batch_k = 1 only, not with
-    the Gumbel root search or the persistent kernel (ValueError); composes with everything else -- with the playout cap the
-    cap's draw sets the budget and the rule may only lower it.  Off, nothing is allocated or launched and every output is
-    byte-identical.
-    `move_visit_offset` o (0 = off), `move_value_cutoff` c (0 = off; at most 2): visit-offset / value-cutoff move selection
-    (move_pick.py, PortableTreeMCTS).  On the plies whose move is sampled from the visits, the move
-    is drawn again, with the same uniform, from the root children that keep more than o visits and whose mean value is
-    within c of the most visited child's; rows, targets and the RNG streams are untouched, so only the game paths change.
-    mcts_counters gain move_pick_applied / move_pick_cut_visits / move_pick_cut_value / move_pick_changed.  Not with the
-    Gumbel root search or `sample_moves=False` (ValueError); composes with everything else.
-    `temperature_halflife` h (0 = off): the move temperature of ply p below `temperature_threshold` is temperature_final
-    + (temperature_init - temperature_final) * 0.5^(p / h) instead of temperature_init, from a float32 table built once
-    on the host (move_pick.temperature_table).  Where the policy target follows the move temperature
-    (`policy_target_temperature` None) it follows the half-life too, exactly as it follows the step.  Off, nothing is
-    allocated or launched and every output is byte-identical.
-    `policy_surprise_weight` alpha (0 = off; in [0, 1]; KataGo uses 0.5): policy surprise weighting of training rows
-    (policy_surprise.py).  A share alpha of a finished game's total row weight is handed out in
-    proportion to KL(the row's policy target || the network's noise-free root prior), and systematic resampling with one
-    seeded uniform per game turns the weights into copy counts inside the game's own row slots: game paths, RNG streams
-    and the rows per game stay as they are, only which of a game's rows fill its slots changes.  The root prior costs one
-    extra network launch of the wave per ply.  With the playout cap only recorded rows take part.  mcts_counters gain
-    surprise_games / surprise_rows / surprise_rows_replaced / surprise_mean (micro-nats per row; and the sum it derives
-    from).  Needs `device_tail`, not with a `PriorEvaluator` (ValueError); composes with everything else.  Off, nothing is
-    allocated or launched and every output is byte-identical."""
+    `search_options`: the optional rules of the search and of the per-ply tail -- symmetric evaluation, playout cap,
+    forced playouts, Gumbel root search, TD(lambda) value targets, MCTS-Solver, first-play urgency / visit-scaled cpuct,
+    resignation, KLD-gain early stopping, move re-pick, temperature half-life, policy surprise weighting -- under the names
+    and defaults of `search_rules.SearchRules.parse`; what each does, the mcts_counters it adds and what it cannot run
+    with are described in search_rules.  A refusal is a ValueError before anything is allocated."""
     dev = torch.device(device)
-    surprise = policy_surprise_on(policy_surprise_weight)
-    if surprise:
-        why = policy_surprise_refusal(device_tail=bool(device_tail), prior_evaluator=isinstance(model, PriorEvaluator),
-                                      batch_k=batch_k)
-        if why is not None:
-            raise ValueError(f"policy surprise weighting is not supported with {why}")
-    pick_kw = move_pick_kwargs(move_visit_offset, move_value_cutoff, temperature_halflife)
-    repick = "move_visit_offset" in pick_kw
-    halflife = float(pick_kw.get("temperature_halflife", 0.0))
-    solver = bool(mcts_solver)
-    kld = parse_kld_stop(kld_stop_threshold, kld_stop_interval, kld_stop_min_simulations)
-    resign = resign_kwargs(resign_threshold, resign_min_moves, resign_consecutive, resign_playthrough_fraction,
-                           resign_streak)
-    if resign and not device_tail:
-        raise ValueError("resignation needs device_tail: the rule runs in the per-ply device tail, the host loop has none")
-    td = td_lambda_on(value_target_lambda)
-    if td and not device_tail:
-        raise ValueError("value_target_lambda < 1 needs device_tail: the host loop keeps the reference's finalisation "
-                         "(every row gets the final result)")
-    cap = playout_cap_on(playout_cap_fast_simulations, playout_cap_full_prob, mcts_simulations)
-    forced = forced_playouts_on(forced_playouts_k)
-    gumbel = gumbel_on(gumbel_considered, gumbel_c_visit, gumbel_c_scale)
-    eval_symmetry = parse_eval_symmetry(eval_symmetry)
-    if eval_symmetry != "none" and int(batch_k) > 1:
-        raise ValueError("eval_symmetry is not supported by the legacy waves (batch_k > 1): their wave kernels evaluate "
-                         "leaves without the symmetry hook")
+    rules = SearchRules.parse(mcts_simulations, **search_options)
+    cap, resign, surprise = rules.cap, rules.resign_kwargs(), rules.surprise
     if row_log is not None and not (device_tail and continuous_waves):
         raise RuntimeError("self_play_tree_gpu: a finished-row log needs device_tail and continuous_waves")
     if evaluator not in ("auto", "fused", "module"):
         raise ValueError(f"evaluator must be auto / fused / module, got {evaluator!r}")
-    if isinstance(model, FusedNet):
-        net, use_fused = model, True
-    elif isinstance(model, PriorEvaluator):
-        net, use_fused = model, False
+    if isinstance(model, (FusedNet, PriorEvaluator)):
+        use_fused = isinstance(model, FusedNet)
     else:
         from .net_hip import fused_supported
         use_fused = evaluator == "fused" or (evaluator == "auto" and fused_supported(model))
-        net = FusedNet(model, dev) if use_fused else model.eval()
+    rules.refuse(batch_k=batch_k, fused=use_fused, persistent=_persistent_default(), sample_moves=sample_moves,
+                 device_tail=bool(device_tail), prior_evaluator=isinstance(model, PriorEvaluator),
+                 policy_target_temperature=policy_target_temperature,
+                 policy_target_prior_pseudocount=policy_target_prior_pseudocount)
+    net = model if isinstance(model, (FusedNet, PriorEvaluator)) else FusedNet(model, dev) if use_fused else model.eval()
     wave = max(1, min(int(concurrent_games), int(num_games)))
     # two half-batches on two streams (see DualStreamTreeMCTS) once a wave is large enough to fill the chip twice over
     if dual_stream is None:
         dual_stream = use_fused and net.pack.channels == 64 and wave >= 1024 and int(batch_k) <= 1   # waves: large launches already
-    if cap and (not use_fused or int(batch_k) > 1):
-        raise ValueError("playout cap randomization needs the fused network search with batch_k = 1 (not the external-"
-                         "module evaluator, not legacy waves)")
-    if forced and (not use_fused or int(batch_k) > 1):
-        raise ValueError("forced playouts need the fused network search with batch_k = 1 (not the external-module "
-                         "evaluator, not legacy waves)")
-    if forced and _persistent_default():
-        raise ValueError("forced playouts are not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
-    if solver:
-        why = solver_refusal(batch_k=batch_k, fused=use_fused)
-        if why is not None:
-            raise ValueError(f"the MCTS-Solver is not supported with {why}")
-    if gumbel:
-        why = gumbel_refusal(batch_k=batch_k, fused=use_fused, forced_playouts_k=forced_playouts_k,
-                             policy_target_temperature=policy_target_temperature,
-                             policy_target_prior_pseudocount=policy_target_prior_pseudocount)
-        if why is not None:
-            raise ValueError(f"the Gumbel root search is not supported with {why}")
-    shape = puct_shape_refusal(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
-                               cpuct_base=cpuct_base, batch_k=batch_k, fused=use_fused,
-                               gumbel_considered=gumbel_considered if gumbel else 0)
-    if kld.on:
-        why = kld_stop_refusal(batch_k=batch_k, fused=use_fused, gumbel_considered=gumbel_considered if gumbel else 0)
-        if why is not None:
-            raise ValueError(f"KLD-gain early stopping is not supported with {why}")
-    if repick:
-        why = move_pick_refusal(sample_moves=sample_moves, gumbel_considered=gumbel_considered if gumbel else 0)
-        if why is not None:
-            raise ValueError(f"visit-offset / value-cutoff move selection is not supported with {why}")
-    if use_fused and persistent_search_available(net, batch_k) and eval_symmetry == "none":
-        if cap:
-            raise ValueError("playout cap randomization is not supported by the persistent search kernel (LZ_TREE_PERSISTENT)")
+    if use_fused and persistent_search_available(net, batch_k) and not rules.symmetric:
         dual_stream = False                                  # the persistent kernel overlaps the phases inside every CU
     cls = DualStreamTreeMCTS if (dual_stream and use_fused and net.pack.channels == 64 and wave >= 2) else PortableTreeMCTS
     t_setup = time.perf_counter()
@@ -2196,23 +1848,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
               sample_moves=bool(sample_moves), reuse_tree=bool(reuse_tree), reuse_factor=float(reuse_factor),
               policy_target_temperature=policy_target_temperature,
               policy_target_prior_pseudocount=float(policy_target_prior_pseudocount), batch_k=int(batch_k),
-              collect_timing=bool(collect_timing))
-    if eval_symmetry != "none":
-        kw["eval_symmetry"] = eval_symmetry
-    if cap:
-        kw.update(fast_simulations=int(playout_cap_fast_simulations), full_prob=float(playout_cap_full_prob))
-    if forced:
-        kw["forced_playouts_k"] = float(forced_playouts_k)
-    if gumbel:
-        kw.update(gumbel_considered=int(gumbel_considered), gumbel_c_visit=float(gumbel_c_visit),
-                  gumbel_c_scale=float(gumbel_c_scale))
-    if solver:
-        kw["solver"] = True
-    kw.update(shape.kwargs())
-    if kld.on:
-        kw["kld_stop"] = kld
-    if repick:
-        kw.update(move_visit_offset=float(move_visit_offset), move_value_cutoff=float(move_value_cutoff))
+              collect_timing=bool(collect_timing), rules=rules.engine())
     # Engines (arenas, descriptors) and their captured graphs are kept between calls with the same network buffers and
     # shape -- the worker calls this once per chunk and the staged loop once per iteration, and construction + capture
     # were 12.5 % of a C2 run.  `FusedNet.refresh()` writes new weights into the same buffers, so a
@@ -2223,7 +1859,8 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     key = None
     if use_fused and isinstance(model, FusedNet) and _engine_cache_limit() > 0:
         key = (cls.__name__, int(net.pack.wfrag.data_ptr()), int(net.pack.fparams.data_ptr()), int(net.desc.flags),
-               str(dev), wave, int(mcts_simulations), tuple(sorted((k, repr(v)) for k, v in kw.items())),
+               str(dev), wave, int(mcts_simulations), kw["rules"],
+               tuple(sorted((k, repr(v)) for k, v in kw.items() if k != "rules")),
                os.environ.get("LZ_TREE_GRAPH", "on"), os.environ.get("LZ_TREE_PERSISTENT", "0"))
     mcts = _ENGINE_CACHE.pop(key, None) if key is not None else None
     cache_hit = mcts is not None
@@ -2250,9 +1887,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     if device_tail:
         from .wave_tail import WaveTail
         tail = WaveTail(buffer, wave, int(max_game_plies), dev, soft_value_k=float(soft_value_k), row_log=row_log,
-                        **({"value_target_lambda": float(value_target_lambda)} if td else {}),
-                        **(resign or {}), **({"seed": int(seed)} if (resign or surprise) else {}),
-                        **({"policy_surprise_weight": float(policy_surprise_weight),
+                        **({"value_target_lambda": rules.td_lambda} if rules.td else {}),
+                        **resign, **({"seed": int(seed)} if (resign or surprise) else {}),
+                        **({"policy_surprise_weight": rules.surprise_weight,
                             "prior_fn": lambda search: root_prior(net, search, use_fused)} if surprise else {}))
         tail.collect_timing = bool(collect_timing)
         outcome, delta_hist = tail.outcome, tail.delta_hist
@@ -2261,9 +1898,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     continuous = tail is not None and bool(continuous_waves)
     # temperature half-life: the schedule as a table, indexed by the ply on the device (tail and host loop alike)
     temp_table = None
-    if halflife > 0.0:
+    if rules.halflife:
         temp_table = torch.from_numpy(temperature_table(temperature_init, temperature_final, temperature_threshold,
-                                                        halflife, int(max_game_plies))).to(dev)
+                                                        rules.temperature_halflife, int(max_game_plies))).to(dev)
     wasted_plies = 0
     started = time.perf_counter()
     for base in range(0, wave if continuous else int(num_games), wave):
@@ -2384,7 +2021,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         # (... unless that ply was launched densely: the two-plies-old live estimate had not seen the wave end yet)
         mcts_counters={"leaf_eval_count": int(mcts.leaf_evals) - (
                            wasted_plies * wave * (int(mcts_simulations) + 1)
-                           if int(batch_k) <= 1 and not (compact_lists and (cap or kld.on or getattr(mcts, "last_search_lists", False)))
+                           if int(batch_k) <= 1 and not (compact_lists and (cap or rules.kld_on or getattr(mcts, "last_search_lists", False)))
                            else 0),
                        "compact_eval_lists": int(compact_lists), "search_parts": len(engines),
                        "list_searches": int(sum(getattr(p, "list_searches", 0) for p in (getattr(mcts, "parts", None) or [mcts]))),
@@ -2400,25 +2037,10 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                           if getattr(mcts, "overlap_ratio", None) is not None else {}),
                        **({"loop_ms": int(tail.loop_ms), "host_wait_ms": int(tail.host_wait_ms),
                            "plies_launched": int(tail.plies_launched)} if tail is not None else {}),
-                       # playout cap: searches of live games by kind, and the rows the full ones recorded
-                       **(dict(zip(("full_searches", "fast_searches"), (int(x) for x in mcts.cap_counts.tolist())),
-                               recorded_positions=int(positions)) if cap else {}),
-                       # forced playouts: descents that took a due root child, visits pruned from the training targets
-                       **(dict(zip(("forced_playouts", "pruned_visits"), (int(x) for x in mcts.forced_counts.tolist())))
-                          if forced else {}),
-                       # Gumbel root search: searches of live games that ran the rule
-                       **({"gumbel_searches": int(mcts.gumbel_searches.item())} if gumbel else {}),
-                       # MCTS-Solver: edges / roots the expand steps decided, searches that ended with a decided root, picks changed
-                       **(dict(zip(("solver_proofs", "solver_roots_decided", "solver_pick_overrides"),
-                                   (int(x) for x in mcts.solver_counts.tolist()))) if solver else {}),
-                       # KLD-gain early stopping: searches it ended early, simulations they did not run
-                       **(dict(zip(("kld_stopped_searches", "kld_simulations_saved"),
-                                   (int(x) for x in mcts.kld_counts.tolist()))) if kld.on else {}),
-                       # move re-pick: games it applied to, children cut by offset / value, picks it changed
-                       **(move_pick_counters(mcts.move_pick_counts.tolist()) if repick else {}),
-                       # resignation: games that resigned, the play-through games and their false positives
+                       # the rules that are on: the engine's counter blocks (search_rules.RULE_SPECS), the rows the playout
+                       # cap's full searches recorded, and the tail's blocks of resignation and policy surprise weighting
+                       **engine_counters(rules, mcts), **({"recorded_positions": int(positions)} if cap else {}),
                        **(counters_from_block(tail.resign_counters.tolist()) if resign else {}),
-                       # policy surprise weighting: games resampled, their rows, rows replaced by a copy, mean surprise
                        **(surprise_counters_from_block(tail.surprise_counters.tolist(), float(tail.surprise_sum.item()))
                           if surprise else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))

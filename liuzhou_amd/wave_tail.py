@@ -18,8 +18,9 @@ import torch
 from . import _lib as L
 from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput
 from .trajectory_buffer import TensorTrajectoryBuffer
-from .policy_surprise import policy_surprise_on, policy_surprise_refusal
+from .policy_surprise import policy_surprise_on
 from .resign import COUNTER_KEYS, resign_kwargs
+from .search_rules import SearchRules
 from .value_target import td_lambda_on
 
 DELTA_BINS = 37
@@ -45,9 +46,7 @@ class WaveTail:
         # policy surprise weighting (policy_surprise.py; 0 = off: nothing below exists, every game keeps its own rows)
         self.surprise_alpha = float(policy_surprise_weight) if policy_surprise_on(policy_surprise_weight) else None
         if self.surprise_alpha is not None:
-            why = policy_surprise_refusal(reseat=reseat)
-            if why is not None:
-                raise ValueError(f"WaveTail: policy surprise weighting is not supported with {why}")
+            SearchRules(surprise_weight=self.surprise_alpha).refuse(reseat=reseat)
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("WaveTail needs a HIP device (no CPU path)")

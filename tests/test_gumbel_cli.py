@@ -98,15 +98,17 @@ def test_stage_and_worker_refuse(tmp_path, monkeypatch):
 
 
 def test_every_refusal_names_its_reason(monkeypatch):
-    from liuzhou_amd.tree_engine import gumbel_refusal
+    from liuzhou_amd.search_rules import SearchRules, persistent_default
+    gumbel_refusal = SearchRules.parse(32, gumbel_considered=16).refusal
     assert gumbel_refusal() is None
     for kw, word in ((dict(batch_k=2), "batch_k"), (dict(several_networks=True), "several networks"),
-                     (dict(fused=False), "external evaluator"), (dict(forced_playouts_k=2.0), "forced playouts"),
+                     (dict(fused=False), "external evaluator"),
                      (dict(policy_target_temperature=1.0), "policy_target_temperature"),
                      (dict(policy_target_prior_pseudocount=0.25), "policy_target_prior_pseudocount")):
         assert word in gumbel_refusal(**kw), kw
+    assert "forced playouts" in SearchRules.parse(32, gumbel_considered=16, forced_playouts_k=2.0).refusal()
     monkeypatch.setenv("LZ_TREE_PERSISTENT", "1")
-    assert "persistent" in gumbel_refusal()
+    assert "persistent" in gumbel_refusal(persistent=persistent_default())
 
 
 def test_engines_refuse_before_they_touch_a_device(monkeypatch):

@@ -95,16 +95,17 @@ def test_parameters_are_validated():
 
 # ---- 3. refusals that need no device ----------------------------------------------------------------------------------------------
 def test_configurations_are_refused_with_a_reason(monkeypatch):
-    from liuzhou_amd.kld_stop import kld_stop_refusal
+    from liuzhou_amd.search_rules import SearchRules, persistent_default
+    kld_stop_refusal = SearchRules.parse(800, kld_stop_threshold=1e-4).refusal
     monkeypatch.delenv("LZ_TREE_PERSISTENT", raising=False)
     assert kld_stop_refusal() is None
     assert "batch_k" in kld_stop_refusal(batch_k=2)
     assert "several networks" in kld_stop_refusal(several_networks=True)
     assert "external evaluator" in kld_stop_refusal(fused=False)
-    assert "Gumbel" in kld_stop_refusal(gumbel_considered=8)
+    assert "Gumbel" in SearchRules.parse(800, kld_stop_threshold=1e-4, gumbel_considered=8).refusal()
     assert "persistent" in kld_stop_refusal(persistent=True)
     monkeypatch.setenv("LZ_TREE_PERSISTENT", "1")
-    assert "persistent" in kld_stop_refusal()
+    assert "persistent" in kld_stop_refusal(persistent=persistent_default())
 
 
 def test_engines_runner_worker_and_stage_refuse(monkeypatch):

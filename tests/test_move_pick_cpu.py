@@ -39,14 +39,16 @@ def test_off_at_zero_and_validation():
 
 
 def test_refusals_without_a_device():
-    assert M.move_pick_refusal() is None
-    assert "Gumbel" in M.move_pick_refusal(gumbel_considered=16)
-    assert "sample_moves" in M.move_pick_refusal(sample_moves=False)
-    M.refuse_backend(False, "cuda_root")
-    M.refuse_backend(True, "tree")
-    M.refuse_backend(True, "portable")
+    from liuzhou_amd.search_rules import SearchRules
+    on = SearchRules.parse(32, move_visit_offset=1.0)
+    assert on.refusal() is None
+    assert "Gumbel" in SearchRules.parse(32, move_visit_offset=1.0, gumbel_considered=16).refusal()
+    assert "sample_moves" in on.refusal(sample_moves=False)
+    SearchRules.parse(32).refuse(search_backend="cuda_root")
+    on.refuse(search_backend="tree")
+    on.refuse(search_backend="portable")
     with pytest.raises(ValueError, match="tree backend"):
-        M.refuse_backend(True, "cuda_root")
+        on.refuse(search_backend="cuda_root")
 
 
 def test_where_the_rule_applies():

@@ -173,7 +173,8 @@ def test_weight_validation():
 
 
 def test_refusal_reasons():
-    from liuzhou_amd.policy_surprise import policy_surprise_refusal
+    from liuzhou_amd.search_rules import SearchRules
+    policy_surprise_refusal = SearchRules.parse(16, policy_surprise_weight=0.5).refusal
     assert policy_surprise_refusal() is None
     assert policy_surprise_refusal(batch_k=4) is None      # nothing in the legacy waves prevents it
     assert "device_tail" in policy_surprise_refusal(device_tail=False)
@@ -206,7 +207,9 @@ def test_tail_refuses_the_in_kernel_reseat_before_it_touches_a_device():
 
 
 def test_root_backend_is_refused():
-    from liuzhou_amd.policy_surprise import refuse_backend
+    from liuzhou_amd.search_rules import SearchRules
+    refuse_backend = lambda on, backend: SearchRules.parse(16, policy_surprise_weight=0.5 if on else 0.0).refuse(
+        search_backend=backend)
     refuse_backend(False, "cuda_root")
     refuse_backend(True, "tree")
     refuse_backend(True, "portable")

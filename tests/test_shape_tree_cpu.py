@@ -131,7 +131,7 @@ def test_cpuct_table_is_the_formula():
 
 # ---- 4. validation ----------------------------------------------------------------------------------------------------------
 def test_parameters_are_validated():
-    from liuzhou_amd.tree_engine import puct_shape_refusal
+    from liuzhou_amd.puct_shape import parse_puct_shape as puct_shape_refusal
     off = puct_shape_refusal()
     assert not off.on and off.flags == 0 and off.kwargs() == {}
     assert not puct_shape_refusal(cpuct_base=8.0).on                # a base alone switches nothing on
@@ -150,7 +150,14 @@ def test_parameters_are_validated():
 
 
 def test_configurations_are_refused_with_a_reason(monkeypatch):
-    from liuzhou_amd.tree_engine import puct_shape_refusal
+    from liuzhou_amd.search_rules import SearchRules, persistent_default
+
+    def puct_shape_refusal(gumbel_considered=0, **kw):           # the shape's own rows of the table
+        context = {k: kw.pop(k) for k in ("batch_k", "fused", "search_backend", "persistent") if k in kw}
+        context.setdefault("persistent", persistent_default())
+        why = SearchRules.parse(800, gumbel_considered=gumbel_considered, **kw).refusal(**context)
+        if why is not None and why.startswith("first-play urgency"):
+            raise ValueError(why)
     monkeypatch.delenv("LZ_TREE_PERSISTENT", raising=False)
     for shape in (dict(fpu_reduction=0.2), dict(cpuct_log=1.0)):
         with pytest.raises(ValueError, match="Gumbel"):

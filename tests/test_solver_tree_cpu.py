@@ -184,7 +184,8 @@ def test_a_pruned_subtree_keeps_its_proof():
 
 # ---- 5. validation and refusals ----------------------------------------------------------------------------------------
 def test_refusal_reasons():
-    from liuzhou_amd.tree_engine import solver_refusal
+    from liuzhou_amd.search_rules import SearchRules
+    solver_refusal = SearchRules.parse(8, mcts_solver=True).refusal
     assert solver_refusal() is None
     assert "batch_k" in solver_refusal(batch_k=2)
     assert "several networks" in solver_refusal(several_networks=True)
@@ -208,6 +209,6 @@ def test_engines_and_runner_refuse_with_a_reason():
 
 
 def test_persistent_kernel_is_refused(monkeypatch):
-    from liuzhou_amd.tree_engine import solver_refusal
+    from liuzhou_amd.search_rules import SearchRules, persistent_default
     monkeypatch.setenv("LZ_TREE_PERSISTENT", "1")
-    assert "persistent" in solver_refusal()
+    assert "persistent" in SearchRules.parse(8, mcts_solver=True).refusal(persistent=persistent_default())
