@@ -1129,7 +1129,9 @@ __device__ __forceinline__ void tree_expand(const Tree& t, int g, int lane, cons
             const bool in = j < hi;
             const uint32_t pe = !in ? 0u : (lo == 0 ? (uint32_t)path_entry : (uint32_t)path[j]);
             const uint64_t F = __ballot(in && (pe & kPathFlip) != 0u);
-            const int above = in ? __popcll(F >> (lane + 1)) : 0;   // flips at offsets > j inside the chunk
+            // flips at offsets > j inside the chunk; two shifts: lane 63 of a full chunk would shift by 64, which the
+            // hardware takes modulo 64 (the entry then counted every flip of its chunk, itself included)
+            const int above = in ? __popcll((F >> lane) >> 1) : 0;
             if (in) {
                 Edge* e = &edges[(size_t)(pe & ~kPathFlip)];
                 const double v = ((above + flips_above) & 1) ? -backup_value : backup_value;

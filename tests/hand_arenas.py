@@ -8,6 +8,9 @@ the engine's buffers by the names of `TreeEngine.buf` as numpy arrays, the launc
 uploaded, so a hand-made mistake cannot make a launch touch memory it does not own.  The device half (`ArenaEngine`)
 uploads exactly the image, launches, and reads every buffer back as one image.
 
+The second half of the file does the same for the tree step, lz_tree_select / lz_tree_expand:
+`StepGame`, `build_step_image`, `check_step_arena`, and `ArenaEngine.select` / `expand`.
+
 Record layouts: EDGE_DT / NODE_DT of tests/tree_parity.py (include/liuzhou_hip.h)."""
 import numpy as np
 
@@ -466,3 +469,380 @@ class ArenaEngine:
                                          L.stream_ptr(self.dev))
         torch.cuda.synchronize()
         return int(rc), tuple(int(v) for v in cnt.tolist())
+
+    def select(self):
+        import torch
+        self.engine.select()
+        torch.cuda.synchronize()
+
+    def expand(self, is_root, rows):
+        """rows: values float32[B], either priors220 float32[B, 220] or heads (three float32[B, 36]), noise float32[B, 72] or
+        None, epsilon."""
+        import torch
+        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.dev)
+        heads = None if rows.get("heads") is None else tuple(up(h) for h in rows["heads"])
+        self.engine.expand(is_root=is_root, values=up(rows["values"]), heads=heads, priors220=up(rows.get("priors220")),
+                           noise=up(rows.get("noise")), epsilon=float(rows.get("epsilon", 0.25)))
+        torch.cuda.synchronize()
+
+    def set_options(self, opts):
+        """The search options of a launch (tests/step_ref.py `options`) on the engine: c_puct, forced playouts, the solver,
+        the PUCT shape."""
+        eng = self.engine
+        eng.desc.exploration_weight = float(opts["c_puct"])
+        eng.set_forced_playouts(float(opts["forced_k"]))
+        eng.set_solver(bool(opts["solver"]))
+        log, base, length = opts["cpuct"] or (0.0, 1.0, 2)
+        eng.set_puct_shape(opts["fpu"], opts["fpu_root"], cpuct_log=log, cpuct_base=base, table_len=length)
+        # every side array the step can write is there to be loaded and compared
+        assert all(getattr(eng, k, None) is not None for k in ("forced_count", "share_count", "eval_count"))
+        assert not opts["solver"] or (eng.root_proven is not None and eng.solver_count is not None)
+        self.solver = bool(opts["solver"])
+
+    def load_side(self, img):
+        import torch
+        for name in SIDE:
+            t = getattr(self.engine, name, None)
+            assert t is not None or (name in SIDE_SOLVER and not self.solver), name
+            if t is not None:
+                t.copy_(torch.from_numpy(np.ascontiguousarray(img[name])).to(self.dev))
+        torch.cuda.synchronize()
+
+    def read_side(self, like):
+        """The side arrays as they stand.  Only root_proven and solver_count may be missing, and only while the solver is
+        off (the engine allocates them when it is first switched on): they then come back as they were loaded, since the
+        descriptor holds no pointer through which a kernel could write them."""
+        out = {}
+        for name in SIDE:
+            t = getattr(self.engine, name, None)
+            assert t is not None or (name in SIDE_SOLVER and not self.solver), name
+            out[name] = like[name].copy() if t is None else t.cpu().numpy().astype(np.int32)
+        return out
+
+
+# =======================================================================================================================
+# The tree STEP (lz_tree_select / lz_tree_expand, DESIGN.md section 33): real skeletons with hand statistics.
+# Node states are real positions, a node's run holds exactly the oracle's legal actions of its state in ascending order, a
+# child's state is the oracle's successor; W, P, N, the proven bits and node_value are chosen per case.  Runs that no legal
+# position can have (65 to 72 edges, or ballast of a chosen length) are SYNTHETIC: every edge of such a run is terminal or
+# leads to a node with a real state, so no descent can end on it as an expandable leaf and no action of it is ever applied.
+# =======================================================================================================================
+M64 = (1 << 64) - 1
+INFO_WHITE, INFO_PROVEN, INFO_DECIDED = 1, 16, 18
+LEAF_INACTIVE, LEAF_EXPAND, LEAF_TERMINAL, LEAF_REUSED_ROOT, LEAF_SHARED = 0, 1, 2, 3, 4
+PATH_FLIP = 0x80000000
+# the counters and side arrays the step writes that are not engine buffers: name -> attribute of TreeEngine
+SIDE = ("root_proven", "solver_count", "forced_count", "share_count", "eval_count")
+SIDE_SOLVER = ("root_proven", "solver_count")                          # exist once the solver has been switched on
+SIDE_PRESET = {"root_proven": 0, "solver_count": 1000, "forced_count": 2000, "share_count": 3000, "eval_count": 4000}
+
+
+def cs_from_packed(p):
+    """Packed record (4 words) -> oracle CState (csrc/lz_rules.h unpack)."""
+    from oracle import lz_oracle as O
+    w = [int(v) & M64 for v in p]
+    cs = O.CState()
+    for i in range(36):
+        cs.board[i] = 1 if (w[0] >> i) & 1 else (-1 if (w[1] >> i) & 1 else 0)
+        cs.mb[i], cs.mw[i] = (w[2] >> i) & 1, (w[3] >> i) & 1
+    w0 = w[0]
+    cs.move_count, cs.msc, cs.phase = (w0 >> 36) & 0xFF, (w0 >> 44) & 0x3F, (w0 >> 50) & 7
+    cs.player = -1 if (w0 >> 53) & 1 else 1
+    cs.forced, cs.pm_req, cs.pm_rem, cs.pc_req, cs.pc_rem = ((w0 >> s) & 3 for s in (54, 56, 58, 60, 62))
+    return cs
+
+
+def packed_from_cs(cs):
+    """Oracle CState -> packed record int64[4] (csrc/lz_rules.h pack)."""
+    w = [0, 0, 0, 0]
+    for i in range(36):
+        w[0] |= (1 << i) if cs.board[i] == 1 else 0
+        w[1] |= (1 << i) if cs.board[i] == -1 else 0
+        w[2] |= (1 << i) if cs.mb[i] else 0
+        w[3] |= (1 << i) if cs.mw[i] else 0
+    w[0] |= (cs.move_count & 0xFF) << 36 | (cs.msc & 0x3F) << 44 | (cs.phase & 7) << 50 | (1 << 53 if cs.player < 0 else 0)
+    w[0] |= (cs.forced & 3) << 54 | (cs.pm_req & 3) << 56 | (cs.pm_rem & 3) << 58 | (cs.pc_req & 3) << 60 | (cs.pc_rem & 3) << 62
+    return np.array(w, np.uint64).view(np.int64)
+
+
+def edge_info_for(succ):
+    """Info byte the expand step gives the edge to `succ`: the white bit, and the terminal mark with the value for succ's
+    mover when the game is over there."""
+    from oracle import lz_oracle as O
+    info = INFO_WHITE if succ.player < 0 else 0
+    st = O.game_status(succ)
+    if st != 0:
+        tv = (1 if st == succ.player else -1) if st in (1, -1) else 0
+        info |= INFO_TERMINAL | ((tv + 1) << 2)
+    return info
+
+
+def playout(seed, start=None, plies=400):
+    """A line of real positions: seeded uniform random play with the oracle from `start` (the initial position) until the
+    game is over or a position has no legal move.  Returns (states, actions); len(states) == len(actions) + 1."""
+    from oracle import lz_oracle as O
+    rng = np.random.default_rng(seed)
+    c = start if start is not None else O.state_from_batch(O.initial_states(1), 0)
+    line, acts = [c], []
+    while O.game_status(c) == 0 and len(acts) < plies:
+        la = O.legal_indices_py(c)
+        if not la:
+            break
+        a = la[int(rng.integers(len(la)))]
+        c = O.apply_index(c, a)
+        line.append(c)
+        acts.append(a)
+    return line, acts
+
+
+class StepGame:
+    """One game of a step image: nodes in expansion order, each with its run.  `real` runs come from the oracle, `synthetic`
+    ones are written by hand under the rule above."""
+
+    def __init__(self, tag, root, fresh=False, **scalars):
+        self.tag, self.nodes, self.fresh = tag, [], fresh
+        self.scalars = dict(root_visits=3, root_w=0.0, root_init_value=0.0, active=1, root_terminal=0)
+        self.scalars.update(scalars)
+        self.root = root
+        self.index_skip = set()
+        if not fresh:
+            self._add(root, -1, None)
+
+    def _add(self, cs, parent, acts, synthetic=False):
+        from oracle import lz_oracle as O
+        if acts is None:
+            acts = O.legal_indices_py(cs)
+            succ = [O.apply_index(cs, a) for a in acts]
+            info = [edge_info_for(s) for s in succ]
+        else:
+            succ, info = [None] * len(acts), [0] * len(acts)
+        n = len(acts)
+        assert n > 0, "a node in the arena has a run"
+        self.nodes.append(dict(cs=cs, parent=parent, act=np.array(acts, np.uint8), succ=succ, synthetic=synthetic,
+                               W=np.zeros(n), P=np.full(n, np.float32(1.0) / np.float32(n), np.float32),
+                               N=np.zeros(n, np.int64), info=np.array(info, np.uint8), child=np.full(n, -1, np.int64),
+                               value=np.float32(0.0)))
+        return len(self.nodes) - 1
+
+    def slot_of(self, node, action):
+        return int(np.flatnonzero(self.nodes[node]["act"] == action)[0])
+
+    def child(self, node, slot, value=0.0):
+        """Hang the real successor of (node, slot) as a new node; returns its id."""
+        nd = self.nodes[node]
+        assert not nd["synthetic"] and nd["child"][slot] < 0 and not nd["info"][slot] & INFO_TERMINAL
+        i = self._add(nd["succ"][slot], node, None)
+        nd["child"][slot] = i
+        self.nodes[i]["value"] = np.float32(value)
+        return i
+
+    def synthetic(self, node, slot, n, terminal_values, white=None):
+        """Hang a node with a synthetic run of n edges under the real edge (node, slot): its state is the real successor,
+        its edges carry distinct action bytes and are all terminal (value terminal_values[k % len]); `attach` then gives
+        chosen edges a child with a real state."""
+        nd = self.nodes[node]
+        cs = nd["succ"][slot]
+        i = self._add(cs, node, [(7 + 3 * k) % 220 for k in range(n)], synthetic=True)
+        nd["child"][slot] = i
+        me = self.nodes[i]
+        for k in range(n):
+            tv = terminal_values[k % len(terminal_values)]
+            w = (k % 2 == 0) if white is None else white
+            me["info"][k] = (INFO_WHITE if w else 0) | INFO_TERMINAL | ((tv + 1) << 2)
+        return i
+
+    def attach(self, node, slot, cs, value=0.0):
+        """Give edge (node, slot) of a synthetic run a child node with the real state `cs` (and its real run)."""
+        nd = self.nodes[node]
+        assert nd["synthetic"]
+        i = self._add(cs, node, None)
+        nd["child"][slot] = i
+        nd["info"][slot] = INFO_WHITE if cs.player < 0 else 0
+        self.nodes[i]["value"] = np.float32(value)
+        return i
+
+    def set(self, node, slot, **kw):
+        for k, v in kw.items():
+            self.nodes[node][k][slot] = v
+
+    def steer(self, node, slot, q=0.9, n=3):
+        """Statistics that make (node, slot) the clear PUCT choice: n visits with mean q for the node's mover."""
+        nd = self.nodes[node]
+        same = (-1 if nd["info"][slot] & INFO_WHITE else 1) == nd["cs"].player
+        nd["N"][slot], nd["W"][slot] = n, (q if same else -q) * n
+
+    def line(self, acts, q=0.9, n=3, values=None):
+        """Hang the chain of `acts` below the root and steer every level along it; returns [(node, slot)] per level.  The
+        last edge gets no node."""
+        node, out = 0, []
+        for j, a in enumerate(acts):
+            s = self.slot_of(node, a)
+            self.steer(node, s, q, n)
+            out.append((node, s))
+            if j + 1 < len(acts):
+                node = self.child(node, s, value=0.0 if values is None else values[j])
+        return out
+
+
+def build_step_image(games, node_cap, chunk, seed, spare_chunks=6, stale_index=True):
+    """The image of StepGames in one engine: layout, chunk lists, 0xA5 filler and stale tables as in `build_image`; the
+    position index holds every non-root node with a real state that the game does not ask to leave out (`index_skip`)."""
+    from tests.advance_ref import pos_hash
+    rng = np.random.default_rng(seed)
+    B = len(games)
+    nes = [np.array([len(n["act"]) for n in g.nodes], np.int64) if g.nodes else np.array([-1]) for g in games]
+    lay = [greedy_layout(ne, chunk) for ne in nes]
+    shape = engine_shape(B, node_cap, chunk, sum(l[1] for l in lay) + spare_chunks)
+    img = blank_image(shape)
+    img["played"], img["reset"], img["next_sims"] = np.zeros(B, np.int32), np.zeros(B, np.uint8), 0
+    img["tags"] = [g.tag for g in games]
+    perm = rng.permutation(shape["pool_chunks"]).astype(np.int32)
+    taken = 0
+    img["pos_index"][:] = -1
+    img["path_len"][:] = 0
+    img["leaf_kind"][:] = LEAF_INACTIVE
+    for gi, g in enumerate(games):
+        ne = nes[gi]
+        where, nch, off = lay[gi]
+        ids = perm[taken:taken + nch].copy()
+        taken += nch
+        img["chunk_list"][gi, :nch], img["n_chunks"][gi] = ids, nch
+        for k in ("root_visits", "root_w", "root_init_value", "active", "root_terminal"):
+            img[k][gi] = g.scalars[k]
+        img["root_state"][gi] = packed_from_cs(g.root)
+        if g.fresh:                                                   # what lz_tree_begin leaves
+            rec = np.zeros(1, NODE_DT)
+            rec["state"], rec["nedges"], rec["parent"] = img["root_state"][gi], -1, -1
+            img["nodes"][gi, :1] = rec
+            img["nodes"][gi, 0]["old_begin"] = 0x5A5A5A5A
+            img["n_nodes"][gi], img["n_edges"][gi] = 1, 0
+            dead = img["root_terminal"][gi] != 0
+            img["leaf_kind"][gi] = LEAF_INACTIVE if dead else LEAF_EXPAND
+            img["leaf_state"][gi], img["leaf_value"][gi] = img["root_state"][gi], 0.0
+            continue
+        nn = len(g.nodes)
+        begin = ids[where[:, 0]].astype(np.int64) * chunk + where[:, 1]
+        img["n_nodes"][gi], img["n_edges"][gi] = nn, int(ids[nch - 1]) * chunk + off
+        rec = np.zeros(nn, NODE_DT)
+        rec["state"] = np.stack([packed_from_cs(n["cs"]) for n in g.nodes])
+        rec["edge_begin"], rec["nedges"] = begin, ne
+        rec["parent"] = [n["parent"] for n in g.nodes]
+        rec["old_begin"] = rng.integers(0, 1 << 20, nn)
+        img["nodes"][gi, :nn] = rec
+        img["node_value"][gi, :nn] = [n["value"] for n in g.nodes]
+        for i, n in enumerate(g.nodes):
+            k = len(n["act"])
+            run = np.zeros(k, EDGE_DT)
+            run["W"], run["P"], run["act"], run["child"] = n["W"], n["P"], n["act"], n["child"]
+            run["n_info"] = n["N"].astype(np.uint32) | (n["info"].astype(np.uint32) << 24)
+            has = n["child"] >= 0
+            ch = np.maximum(n["child"], 0)
+            run["cbegin"] = np.where(has, begin[ch], 0)               # as the expand step leaves an edge without a child
+            run["cn"] = np.where(has, ne[ch], 0)
+            img["edges"][begin[i]:begin[i] + k] = run
+        tab, mask = img["pos_index"][gi], shape["pos_slots"] - 1
+        for i in range(1, nn):
+            if g.nodes[i]["synthetic"] or i in g.index_skip:
+                continue
+            h = pos_hash(rec["state"][i])
+            for p in range(WAVE):
+                if tab[(h + p) & mask] == -1:
+                    tab[(h + p) & mask] = i
+                    break
+    img["free_chunks"][:shape["pool_chunks"] - taken] = perm[taken:]
+    img["pool_top"][0] = shape["pool_chunks"] - taken
+    img["pool_stats"][:] = (0, shape["pool_chunks"], pending_count(img))
+    for name in SIDE:
+        img[name] = np.full(B, SIDE_PRESET[name], np.int32)
+    return img
+
+
+def longest_chain(img, g):
+    """Edges on the longest root-to-leaf chain of game g (a descent writes one path entry per edge)."""
+    nn = int(img["n_nodes"][g])
+    depth = np.zeros(nn, np.int64)
+    par = img["nodes"][g, :nn]["parent"]
+    for i in range(1, nn):
+        depth[i] = depth[par[i]] + 1
+    return int(depth.max()) + 1 if int(img["nodes"][g, 0]["nedges"]) > 0 else 0
+
+
+def check_step_arena(img, step="select"):
+    """Everything a correct launch of `step` ('select': lz_tree_select, 'expand' / 'root': lz_tree_expand below the root /
+    at it) relies on, asserted before any upload: everything `check_arena` asserts, plus the step's own needs (module
+    comment above)."""
+    assert step in ("select", "expand", "root")
+    is_root = step == "root"
+    from oracle import lz_oracle as O
+    from tests.advance_ref import pos_hash
+    assert check_arena(img)
+    B, cap, chunk = img["B"], img["node_cap"], img["chunk"]
+    for name in SIDE:
+        assert img[name].dtype == np.int32 and img[name].shape == (B,), name
+    takers = 0
+    for g in range(B):
+        nn = int(img["n_nodes"][g])
+        nd = img["nodes"][g, :nn]
+        kind = int(img["leaf_kind"][g])
+        assert kind in (LEAF_INACTIVE, LEAF_EXPAND, LEAF_TERMINAL, LEAF_REUSED_ROOT, LEAF_SHARED), (g, "leaf_kind")
+        if img["root_terminal"][g]:
+            continue
+        if int(nd["nedges"][0]) < 0:                                  # a fresh root: it expands from leaf_state
+            assert nn == 1 and (img["leaf_state"][g] == img["root_state"][g]).all(), (g, "fresh root")
+            assert kind == LEAF_EXPAND and step == "root", (g, "a fresh root meets another step than the root step")
+            assert packed_status(*img["leaf_state"][g][:2]) == 0
+            takers += 1
+            continue
+        assert nn + 1 <= cap, (g, "no room for the node of an expansion")
+        assert longest_chain(img, g) < img["path_cap"] - 1, (g, "a chain reaches path_cap")
+        takers += 1
+        for i in range(nn):
+            ne, e0 = int(nd["nedges"][i]), int(nd["edge_begin"][i])
+            if ne <= 0:
+                assert i == 0, (g, i, "a node below the root without a run")
+                continue
+            run = img["edges"][e0:e0 + ne]
+            cs = cs_from_packed(nd["state"][i])
+            info = (run["n_info"] >> 24).astype(np.int64)
+            legal = O.legal_indices_py(cs) if O.game_status(cs) == 0 else []
+            real = run["act"].tolist() == legal
+            assert len(set(run["act"].tolist())) == ne, (g, i, "action bytes repeat inside a run")
+            assert ((run["n_info"] & 0xFFFFFF) <= (1 << 24) - 2).all(), (g, i, "a visit count that one more visit overflows")
+            for k in range(ne):
+                ch = int(run["child"][k])
+                term = bool(info[k] & INFO_TERMINAL)
+                assert not (term and ch >= 0), (g, i, k, "a node hangs from a terminal edge")
+                if real:
+                    succ = O.apply_index(cs, int(run["act"][k]))
+                    assert bool(info[k] & INFO_WHITE) == (succ.player < 0), (g, i, k, "player bit")
+                    if O.game_status(succ) != 0:
+                        assert info[k] & 0xF == edge_info_for(succ) & 0xF, (g, i, k, "terminal bits of a finished child")
+                    if ch >= 0:
+                        assert (nd["state"][ch] == packed_from_cs(succ)).all(), (g, i, k, "child state is not the successor")
+                else:                                                  # synthetic: never an expandable leaf
+                    assert term or ch >= 0, (g, i, k, "an edge of a synthetic run could be expanded")
+                    if ch >= 0:
+                        c2 = cs_from_packed(nd["state"][ch])
+                        assert O.game_status(c2) == 0 and bool(info[k] & INFO_WHITE) == (c2.player < 0), (g, i, k, "synthetic child")
+        # the position index names nodes that hold the state of their slot's window
+        mask = img["pos_slots"] - 1
+        tab = img["pos_index"][g]
+        for s in ([] if g in img.get("hand_index", ()) else np.flatnonzero((tab >= 1) & (tab < nn))):
+            h = pos_hash(nd["state"][int(tab[s])])
+            assert ((int(s) - h) & mask) < WAVE, (g, int(s), "index entry outside the window of its state")
+        assert ((tab == -1) | ((tab >= 1) & (tab < nn))).all(), (g, "index entry outside [1, n_nodes)")
+        if kind == LEAF_SHARED:                                        # preset by hand: the source holds the leaf's state
+            src = int(img["leaf_src"][g])
+            assert 1 <= src < nn and (nd["state"][src] == img["leaf_state"][g]).all(), (g, "leaf_src")
+            assert nd["nedges"][src] == len(O.legal_indices_py(cs_from_packed(img["leaf_state"][g]))), (g, "source run")
+        if kind in (LEAF_EXPAND, LEAF_TERMINAL, LEAF_SHARED) and step == "expand":
+            plen, le = int(img["path_len"][g]), int(img["leaf_edge"][g])
+            assert 1 <= plen < img["path_cap"], (g, "path_len")
+            p = img["path"][g * img["path_cap"]:g * img["path_cap"] + plen].astype(np.int64) & 0x7FFFFFFF
+            owned = set((img["chunk_list"][g, :int(img["n_chunks"][g])]).tolist())
+            assert all(int(e) // chunk in owned for e in p) and int(p[-1]) == le, (g, "path entry outside the game's chunks")
+    # the pool: either room for every game that may take a chunk, or none for any (the order of the takes is not
+    # specified, so a launch in which some takes succeed and others are refused has no single expected image)
+    free = int(img["pool_top"][0]) - (0 if is_root else int(img["pool_stats"][2]))
+    assert step == "select" or free >= takers or free <= 0, ("pool", free, takers)
+    return True
