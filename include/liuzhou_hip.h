@@ -376,6 +376,37 @@ LZ_API int lz_wave_reseat(const LzStateSoA* states, int64_t num_slots, uint8_t* 
                           int64_t* step_counts, int64_t* budget, int64_t* next_game, int64_t* slot_game,
                           uint8_t* reseated, int logged_only, void* stream);
 
+/* The start bank: self-play games that start from positions of earlier games (game forking; off in the reference, where
+ * every game starts from the empty board).  The bank is a ring of packed states: entries uint8[capacity, 32] (the
+ * lossless 32-byte record of csrc/lz_rules.h: four little-endian 64-bit words) and cursor int64[1] = the number of
+ * positions ever appended; filled = min(*cursor, capacity), and the filled entries are the rows [0, filled).  Game id =
+ * (slot_game ? slot_game[g] : g) + game_base; the draws are Philox blocks of lz_rng.h, purpose 3, pure functions of
+ * (seed, id, ply).  The scalar rules are csrc/lz_start_bank.h (host and device).  counters int64[3] = {forked games,
+ * sum of move_count at the fork, positions captured}.  1 <= capacity <= 2^24, probabilities in [0, 1], 0 <= min_move
+ * <= max_move (LZ_ERR_ARG); entries 16-byte, cursor and counters 8-byte aligned (LZ_ERR_ALIGN).
+ *
+ * lz_start_bank_capture: once per ply, after lz_wave_record / lz_wave_note_value / lz_wave_note_surprise and before
+ * lz_wave_resign / lz_wave_step_finish (the states are the searched roots).  Slot g is a candidate when done[g] == 0,
+ * terminal_mask[g] == 0 (the search's mask), chosen_valid_mask[g] != 0, min_move <= move_count[g] <= max_move and
+ * u01(draw(seed, id, plies[g], index 1020).x) < capture_prob.  In ascending slot order the candidate of rank r is
+ * written to row (*cursor + r) % capacity; of more candidates than `capacity` only the last `capacity` write.  Then
+ * *cursor += count and counters[2] += count.  Deterministic (one workgroup, ordered scan); capture_prob == 0 writes
+ * nothing.
+ *
+ * lz_start_bank_seed: on the slots with fresh[g] != 0 (lz_wave_reseat's `reseated`, or the live slots before the first
+ * ply).  With filled > 0, r = draw(seed, id, 0, index 1021) and u01(r.x) < fork_prob the twelve state tensors of slot g
+ * become the unpacked entry (r.y * filled) >> 32 (integer arithmetic), counters[0] += 1 and counters[1] += its
+ * move_count.  Nothing else of the slot is touched; the bank is only read. */
+LZ_API int lz_start_bank_capture(const LzStateSoA* states, int64_t num_slots, const uint8_t* done,
+                                 const uint8_t* terminal_mask, const uint8_t* chosen_valid_mask, const int64_t* plies,
+                                 const int64_t* slot_game, int64_t game_base, uint64_t seed, float capture_prob,
+                                 int64_t min_move, int64_t max_move, uint8_t* entries, int64_t capacity,
+                                 int64_t* cursor, int64_t* counters, void* stream);
+LZ_API int lz_start_bank_seed(const LzStateSoA* states, int64_t num_slots, const uint8_t* fresh,
+                              const int64_t* slot_game, int64_t game_base, uint64_t seed, float fork_prob,
+                              const uint8_t* entries, int64_t capacity, const int64_t* cursor, int64_t* counters,
+                              void* stream);
+
 /* lz_wave_log_finished: finished-row log of the streaming worker.  The reference worker sees the rows of a wave only
  * after the whole wave has drained and copies them to the host with the GPU idle
  * (v1/python/self_play_worker.py:430-546: `_run_once` -> `chunk_batch.to("cpu")` -> `save_self_play_payload`); here

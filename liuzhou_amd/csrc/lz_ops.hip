@@ -15,6 +15,7 @@
 
 #include "lz_rng.h"
 #include "lz_soa.h"
+#include "lz_start_bank.h"
 #include "lz_surprise.h"
 #include "lz_wave.h"
 
@@ -1264,6 +1265,79 @@ __global__ __launch_bounds__(kRowsBlock) void wave_reseat_kernel(
     }
 }
 
+// ---- the start bank (lz_start_bank.h holds the scalar rules): positions the wave passes through are kept in a ring of
+// lz::Packed records, and a seeded share of the games that start takes one of them instead of the empty board.
+// Capture, once per ply after wave_record_kernel / the note kernels and before the resign / step kernels (the state is
+// still the searched root): the candidates are appended in ascending slot order.  One workgroup, same scan as
+// wave_reseat_kernel; of more candidates than the ring has rows only the last `capacity` write.
+__global__ __launch_bounds__(kRowsBlock) void start_bank_capture_kernel(
+    LzStateSoA s, int64_t G, const uint8_t* __restrict__ done, const uint8_t* __restrict__ terminal,
+    const uint8_t* __restrict__ cvalid, const int64_t* __restrict__ plies, const int64_t* __restrict__ slot_game,
+    int64_t game_base, uint64_t seed, float capture_prob, int64_t min_move, int64_t max_move,
+    ulonglong2* __restrict__ entries, int64_t capacity, int64_t* __restrict__ cursor,
+    unsigned long long* __restrict__ counters) {
+    __shared__ int wave_total[kRowsBlock / kWave];
+    if (!(capture_prob > 0.f)) return;                  // uniform: the rule only forks
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
+    const int64_t per = (G + kRowsBlock - 1) / kRowsBlock;
+    const int64_t lo = tid * per, hi = (lo + per < G) ? lo + per : G;
+    auto is_candidate = [&](int64_t j) {
+        return lzbank::candidate(done[j], terminal[j], cvalid[j], s.move_count[j], min_move, max_move, seed,
+                                 (slot_game ? slot_game[j] : j) + game_base, plies[j], capture_prob);
+    };
+    int cnt = 0;
+    for (int64_t j = lo; j < hi; ++j) cnt += is_candidate(j) ? 1 : 0;
+    int incl = cnt;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int v = __shfl_up(incl, d, kWave);
+        if (lane >= d) incl += v;
+    }
+    if (lane == kWave - 1) wave_total[w] = incl;
+    __syncthreads();
+    int before = 0, count = 0;
+    for (int i = 0; i < kRowsBlock / kWave; ++i) { if (i < w) before += wave_total[i]; count += wave_total[i]; }
+    const int64_t total = *cursor < 0 ? 0 : *cursor;
+    int64_t rank = before + incl - cnt;
+    __syncthreads();                                    // every thread has read the cursor
+    if (cnt > 0) {
+        for (int64_t j = lo; j < hi; ++j) {
+            if (!is_candidate(j)) continue;
+            if (lzbank::rank_writes(rank, count, capacity)) {
+                const Packed p = pack(load_state(s, j));
+                const int64_t row = lzbank::ring_row(total, rank, capacity);
+                entries[2 * row] = make_ulonglong2(p.w0, p.w1);
+                entries[2 * row + 1] = make_ulonglong2(p.w2, p.w3);
+            }
+            ++rank;
+        }
+    }
+    if (tid == 0 && count > 0) {
+        *cursor = total + count;
+        atomicAdd(&counters[lzbank::kCaptured], (unsigned long long)count);
+    }
+}
+
+// Seed, one lane per slot, on the slots `fresh` marks (lz_wave_reseat's `reseated`, or the live slots before a run's
+// first ply): the slot's state becomes the drawn entry.  plies / step_counts / slot_game / done are not touched: `plies`
+// counts the plies since the game's start, which is what the tail's other kernels index by.
+__global__ __launch_bounds__(kBlock) void start_bank_seed_kernel(
+    LzStateSoA s, int64_t G, const uint8_t* __restrict__ fresh, const int64_t* __restrict__ slot_game,
+    int64_t game_base, uint64_t seed, float fork_prob, const ulonglong2* __restrict__ entries, int64_t capacity,
+    const int64_t* __restrict__ cursor, unsigned long long* __restrict__ counters) {
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= G) return;
+    if (fresh[g] == 0) return;
+    const int64_t j = lzbank::fork_entry(seed, (slot_game ? slot_game[g] : g) + game_base, fork_prob,
+                                         lzbank::filled(*cursor, capacity));
+    if (j < 0) return;
+    const ulonglong2 a = entries[2 * j], b = entries[2 * j + 1];
+    const State st = unpack(Packed{a.x, a.y, b.x, b.y});
+    store_state(s, g, st);
+    atomicAdd(&counters[lzbank::kForkedGames], 1ull);
+    atomicAdd(&counters[lzbank::kForkMoveSum], (unsigned long long)st.move_count);
+}
+
 // one wave per slot: copy the ply's sample into arena row rows[g] (value targets start as NaN)
 __global__ __launch_bounds__(kBlock) void wave_record_kernel(
     const int64_t* __restrict__ rows, int64_t G, const float* __restrict__ model_input,
@@ -2322,6 +2396,38 @@ int lz_wave_reseat(const LzStateSoA* s, int64_t G, uint8_t* done, int64_t* plies
     if (!soa_aligned(s)) return LZ_ERR_ALIGN;
     hipLaunchKernelGGL(wave_reseat_kernel, dim3(1), dim3(kRowsBlock), 0, as_stream(stream), *s, G, done, plies,
                        step_counts, budget, next_game, slot_game, reseated, logged_only);
+    return launch_status();
+}
+
+int lz_start_bank_capture(const LzStateSoA* s, int64_t G, const uint8_t* done, const uint8_t* terminal_mask,
+                          const uint8_t* chosen_valid_mask, const int64_t* plies, const int64_t* slot_game,
+                          int64_t game_base, uint64_t seed, float capture_prob, int64_t min_move, int64_t max_move,
+                          uint8_t* entries, int64_t capacity, int64_t* cursor, int64_t* counters, void* stream) {
+    if (G < 0 || capacity < 1 || capacity > lzbank::kMaxCapacity || min_move < 0 || max_move < min_move ||
+        !(capture_prob >= 0.f && capture_prob <= 1.f))
+        return LZ_ERR_ARG;
+    if (G == 0) return LZ_OK;
+    if (!soa_ok(s) || !done || !terminal_mask || !chosen_valid_mask || !plies || !entries || !cursor || !counters)
+        return LZ_ERR_ARG;
+    if (!soa_aligned(s) || !aligned(entries, 16) || !aligned(cursor, 8) || !aligned(counters, 8)) return LZ_ERR_ALIGN;
+    hipLaunchKernelGGL(start_bank_capture_kernel, dim3(1), dim3(kRowsBlock), 0, as_stream(stream), *s, G, done,
+                       terminal_mask, chosen_valid_mask, plies, slot_game, game_base, seed, capture_prob, min_move,
+                       max_move, reinterpret_cast<ulonglong2*>(entries), capacity, cursor,
+                       reinterpret_cast<unsigned long long*>(counters));
+    return launch_status();
+}
+
+int lz_start_bank_seed(const LzStateSoA* s, int64_t G, const uint8_t* fresh, const int64_t* slot_game, int64_t game_base,
+                       uint64_t seed, float fork_prob, const uint8_t* entries, int64_t capacity, const int64_t* cursor,
+                       int64_t* counters, void* stream) {
+    if (G < 0 || capacity < 1 || capacity > lzbank::kMaxCapacity || !(fork_prob >= 0.f && fork_prob <= 1.f))
+        return LZ_ERR_ARG;
+    if (G == 0) return LZ_OK;
+    if (!soa_ok(s) || !fresh || !entries || !cursor || !counters) return LZ_ERR_ARG;
+    if (!soa_aligned(s) || !aligned(entries, 16) || !aligned(cursor, 8) || !aligned(counters, 8)) return LZ_ERR_ALIGN;
+    hipLaunchKernelGGL(start_bank_seed_kernel, dim3(grid_threads(G)), dim3(kBlock), 0, as_stream(stream), *s, G, fresh,
+                       slot_game, game_base, seed, fork_prob, reinterpret_cast<const ulonglong2*>(entries), capacity,
+                       cursor, reinterpret_cast<unsigned long long*>(counters));
     return launch_status();
 }
 

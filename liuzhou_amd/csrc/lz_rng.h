@@ -105,9 +105,13 @@ LZ_RNG_HD float gumbel_draw(uint64_t seed, int64_t game, int64_t ply, uint32_t k
 // Index layout of purpose 3 (the two purpose bits are all taken, the 10-bit index field separates the streams):
 //   index 0            the playout cap's full / fast draw of (game, ply)
 //   index 1 + k        the Gumbel variate of child rank k; k < 220 (the action dimension), so indices 1..220
+//   index 1020        the start bank's capture draw of (game, ply) (lz_start_bank.h): u01(x) < capture_prob
+//   index 1021, ply 0  the start bank's fork draw of a game (lz_start_bank.h): u01(x) < fork_prob, y picks the entry
 //   index 1022, ply 0  the policy surprise resampling offset of a game (lz_surprise.h: game_u): u = u01(x)
 //   index 1023, ply 0  the resignation play-through draw of a game (wave_resign_kernel, lz_ops.hip): u01(x) < fraction
-// 221..1021 are free.
+// 221..1019 are free.
+constexpr uint32_t kIndexStartCapture = 1020;
+constexpr uint32_t kIndexStartFork = 1021;
 constexpr uint32_t kIndexPolicySurprise = 1022;
 constexpr uint32_t kIndexResignPlaythrough = 1023;
 

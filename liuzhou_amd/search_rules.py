@@ -65,6 +65,16 @@ kernel (LZ_TREE_PERSISTENT).
     into copy counts inside the game's own row slots.  One extra network launch of the wave per ply; with the playout
     cap only recorded rows take part.  Counters: policy_surprise.COUNTER_KEYS + DERIVED_KEYS.  Needs `device_tail`,
     not with a `PriorEvaluator` or the tail's in-kernel re-seat.
+`start_fork_prob` (0 = off), `start_capture_prob` (0 = off), `start_bank_capacity` (65536), `start_min_move` (1: the
+    empty board is never stored), `start_max_move` (143) (start_bank.py): game forking.  Once per
+    ply a seeded share `start_capture_prob` of the searched, non-terminal positions whose move count lies in
+    [start_min_move, start_max_move] is appended to a device-resident ring of `start_bank_capacity` packed states, and
+    a seeded share `start_fork_prob` of the games that start takes a uniformly drawn bank position instead of the
+    empty board (none while the bank is empty).  A forked game counts its plies from the fork: the temperature
+    schedule and `opening_random_moves` restart there, the game's own limits travel in the state.  The rule is on
+    when either probability is > 0 (capture alone fills a bank for later); `self_play_tree_gpu(start_bank=...)` takes
+    a `StartBank` that survives the call.  Counters: start_captured, start_forked_games, start_fork_move_sum.  Needs
+    `device_tail`, not with the tail's in-kernel re-seat.
 
 Adding a rule: a field (with its one "off" value) and its flat names in `parse`, its group in `kwargs` and `meta`, its
 rows in `REFUSALS`, a `RuleSpec` in `RULE_SPECS`, and its paragraph above.
@@ -131,6 +141,38 @@ def forced_playouts_on(k) -> bool:
     return k > 0.0
 
 
+START_KEYS = ("start_fork_prob", "start_capture_prob", "start_bank_capacity", "start_min_move", "start_max_move")
+START_DEFAULTS = (0.0, 0.0, 65536, 1, 143)
+START_MAX_CAPACITY = 1 << 24
+START_COUNTER_KEYS = ("start_forked_games", "start_fork_move_sum", "start_captured")      # the order of the device block
+
+
+def start_bank_on(fork_prob, capture_prob, capacity, min_move, max_move) -> bool:
+    """Validate the start bank's parameters: both probabilities in [0, 1], 1 <= capacity <= 2**24 and 0 <= min_move <=
+    max_move <= 143 (integers); on when either probability is > 0."""
+    for name, p in (("start_fork_prob", fork_prob), ("start_capture_prob", capture_prob)):
+        if isinstance(p, bool) or not 0.0 <= float(p) <= 1.0:                  # a NaN compares false
+            raise ValueError(f"{name} must lie in [0, 1] (0 = off), got {p!r}")
+    for name, v in (("start_bank_capacity", capacity), ("start_min_move", min_move), ("start_max_move", max_move)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 1 <= int(capacity) <= START_MAX_CAPACITY:
+        raise ValueError(f"start_bank_capacity must lie in [1, 2**24], got {capacity!r}")
+    if not 0 <= int(min_move) <= int(max_move) <= 143:
+        raise ValueError(f"start_min_move / start_max_move must satisfy 0 <= min <= max <= 143, got {min_move!r} / "
+                         f"{max_move!r}")
+    return float(fork_prob) > 0.0 or float(capture_prob) > 0.0
+
+
+def start_meta(settings: Mapping[str, Any], counters: Mapping[str, Any]) -> Dict[str, Any]:
+    """The manifest entry of the start bank: its settings, its three counters and the mean move count at the fork."""
+    c = {k: int(counters.get(k, 0)) for k in START_COUNTER_KEYS}
+    forks = c["start_forked_games"]
+    return {**settings, "start_captured": c["start_captured"], "start_forked_games": forks,
+            "start_fork_move_sum": c["start_fork_move_sum"],
+            "fork_avg_move": (c["start_fork_move_sum"] / forks) if forks else 0.0}
+
+
 def persistent_default() -> bool:
     """Is the persistent search kernel asked for (env LZ_TREE_PERSISTENT)?  What callers hand `refuse(persistent=...)`."""
     return os.environ.get("LZ_TREE_PERSISTENT", "0").strip().lower() in ("1", "on", "true")
@@ -159,6 +201,7 @@ class SearchRules(NamedTuple):
     move_value_cutoff: float = 0.0
     temperature_halflife: float = 0.0
     surprise_weight: float = 0.0
+    start: Tuple = ()                        # the five values in START_KEYS order, () = off
 
     @classmethod
     def parse(cls, mcts_simulations, *, eval_symmetry="none", playout_cap_fast_simulations=0, playout_cap_full_prob=1.0,
@@ -167,8 +210,10 @@ class SearchRules(NamedTuple):
               cpuct_base=CPUCT_BASE_DEFAULT, resign_threshold=0.0, resign_min_moves=10, resign_consecutive=3,
               resign_playthrough_fraction=0.1, resign_streak="side", kld_stop_threshold=0.0,
               kld_stop_interval=_kld.INTERVAL_DEFAULT, kld_stop_min_simulations=None, move_visit_offset=0.0,
-              move_value_cutoff=0.0, temperature_halflife=0.0, policy_surprise_weight=0.0) -> "SearchRules":
+              move_value_cutoff=0.0, temperature_halflife=0.0, policy_surprise_weight=0.0, start_fork_prob=0.0,
+              start_capture_prob=0.0, start_bank_capacity=65536, start_min_move=1, start_max_move=143) -> "SearchRules":
         """From the public flat keyword names (an unknown one is a TypeError).  Every value is validated, on or off."""
+        start = start_bank_on(start_fork_prob, start_capture_prob, start_bank_capacity, start_min_move, start_max_move)
         surprise = _surprise.policy_surprise_on(policy_surprise_weight)
         repick = _pick.move_pick_on(move_visit_offset, move_value_cutoff)
         halflife = _pick.halflife_on(temperature_halflife)
@@ -195,7 +240,9 @@ class SearchRules(NamedTuple):
             move_visit_offset=float(move_visit_offset) if repick else 0.0,
             move_value_cutoff=float(move_value_cutoff) if repick else 0.0,
             temperature_halflife=float(temperature_halflife) if halflife else 0.0,
-            surprise_weight=float(policy_surprise_weight) if surprise else 0.0)
+            surprise_weight=float(policy_surprise_weight) if surprise else 0.0,
+            start=(float(start_fork_prob), float(start_capture_prob), int(start_bank_capacity), int(start_min_move),
+                   int(start_max_move)) if start else ())
 
     @classmethod
     def parse_engine(cls, num_simulations, *, kld_stop: Optional[KldStop] = None, **options) -> "SearchRules":
@@ -224,6 +271,9 @@ class SearchRules(NamedTuple):
     def resign_kwargs(self) -> Dict[str, Any]:
         return dict(zip(_resign.PARAM_KEYS, self.resign))
 
+    def start_kwargs(self) -> Dict[str, Any]:
+        return dict(zip(START_KEYS, self.start))
+
     def kwargs(self) -> Dict[str, Any]:
         """The flat keyword arguments of the groups that are on ({} with everything off):
         `SearchRules.parse(sims, **rules.kwargs()) == rules`."""
@@ -239,7 +289,7 @@ class SearchRules(NamedTuple):
                 **({"move_visit_offset": self.move_visit_offset, "move_value_cutoff": self.move_value_cutoff}
                    if self.repick else {}),
                 **({"temperature_halflife": self.temperature_halflife} if self.halflife else {}),
-                **({"policy_surprise_weight": self.surprise_weight} if self.surprise else {})}
+                **({"policy_surprise_weight": self.surprise_weight} if self.surprise else {}), **self.start_kwargs()}
 
     def meta(self) -> Dict[str, Any]:
         """What a worker records in its manifest's metadata: one entry (RuleSpec.key) per rule that is on."""
@@ -257,12 +307,14 @@ class SearchRules(NamedTuple):
                 **({"resign": _resign.resign_meta(self.resign_kwargs())} if self.resign else {}),
                 **({"kld_stop": self.kld.meta()} if self.kld_on else {}),
                 **({"move_pick": _pick.move_pick_meta(pick)} if self.move_options else {}),
-                **({"policy_surprise": {"weight": self.surprise_weight}} if self.surprise else {})}
+                **({"policy_surprise": {"weight": self.surprise_weight}} if self.surprise else {}),
+                **({"start_bank": dict(zip(("fork_prob", "capture_prob", "capacity", "min_move", "max_move"), self.start))}
+                   if self.start else {})}
 
     def engine(self) -> "SearchRules":
         """The rules a search engine sees: those of the per-ply tail (TD(lambda), resignation, policy surprise, the
-        temperature half-life) are off, so engines that differ only in them are one engine (the engine cache's key)."""
-        return self._replace(td_lambda=1.0, resign=(), temperature_halflife=0.0, surprise_weight=0.0)
+        temperature half-life, the start bank) are off, so engines that differ only in them are one engine (the engine cache's key)."""
+        return self._replace(td_lambda=1.0, resign=(), temperature_halflife=0.0, surprise_weight=0.0, start=())
 
     def refusal(self, **context) -> Optional[str]:
         """The message of the first row of REFUSALS whose rule is on and whose condition holds in `context`
@@ -302,6 +354,8 @@ def _with(on: str, subject: str, *causes) -> list:
 # (rule's on-property, context key or None, condition(context value, rules), message) -- walked top to bottom, the first
 # hit is raised.  First every rule against the root-PUCT backend, then rule by rule what else is in its way.
 REFUSALS = [
+    ("start", *_ROOT, "the start bank needs the tree backend, not the root-PUCT search ({v!r}): its capture and seed "
+                      "kernels run in the tree backend's per-ply device tail"),
     ("surprise", *_ROOT, "policy surprise weighting needs the tree backend, not the root-PUCT search ({v!r}): it compares "
                          "the tree search's policy target with the network prior"),
     ("move_options", *_ROOT, "move_visit_offset / move_value_cutoff / temperature_halflife need the tree backend, not the "
@@ -328,6 +382,10 @@ REFUSALS = [
                                             "kernel, before the rows of the game are weighed"),
            ("prior_evaluator", lambda v, r: bool(v), "a PriorEvaluator: it returns priors of its own making, there is no "
                                                      "plain network to evaluate the root with")),
+    *_with("start", "the start bank is",
+           (*_NO_TAIL, "the host loop (device_tail=False): the bank is filled and read by the per-ply device tail"),
+           ("reseat", lambda v, r: bool(v), "the in-kernel re-seat (reseat=True): the step kernel starts the next game "
+                                            "there, and no kernel runs between its fresh state and the search")),
     ("resign", *_NO_TAIL, "resignation needs device_tail: the rule runs in the per-ply device tail, the host loop has none"),
     ("td", *_NO_TAIL, "value_target_lambda < 1 needs device_tail: the host loop keeps the reference's finalisation (every "
                       "row gets the final result)"),
@@ -388,6 +446,8 @@ RULE_SPECS = (
     RuleSpec("move_pick", _AS_IS("visit_offset", "value_cutoff", "temperature_halflife"), _pick.COUNTER_KEYS,
              present_only=True, on="repick", source="move_pick_counts"),
     RuleSpec("policy_surprise", (("weight", 0.0),), summary=lambda s, c: _surprise.surprise_meta(s["weight"], c)),
+    RuleSpec("start_bank", (("fork_prob", 0.0), ("capture_prob", 0.0), ("capacity", 65536), ("min_move", 1),
+                            ("max_move", 143)), START_COUNTER_KEYS + ("fork_avg_move",), summary=start_meta),
 )
 SOLVER_COUNTER_KEYS = ("solver_proofs", "solver_roots_decided", "solver_pick_overrides")
 

@@ -136,8 +136,8 @@ def run_self_play_stage(*, model_state: Dict[str, torch.Tensor], num_games: int,
     `<stem>.wNN.chunkMMMMM<ext>` chunk files plus the manifest `output_path`.  Returns (merged stats, manifest).
     `worker_fn` / `in_process` exist for tests (a stub worker, no process pool).  `search_options`: the optional rules
     of the tree backend's search (symmetric evaluation, playout cap, forced playouts, Gumbel root search, TD(lambda)
-    targets, MCTS-Solver, PUCT shape, resignation, KLD-gain stop, move re-pick, temperature half-life, policy surprise),
-    under the names and defaults of `search_rules.SearchRules.parse`; described there.  They are validated and refused
+    targets, MCTS-Solver, PUCT shape, resignation, KLD-gain stop, move re-pick, temperature half-life, policy surprise, the
+    start bank), under the names and defaults of `search_rules.SearchRules.parse`; described there.  They are validated and refused
     here, and reach the workers only when they are on."""
     rules = SearchRules.parse(mcts_simulations, **search_options)
     rules.refuse(search_backend=search_backend, sample_moves=sample_moves, persistent=persistent_default(),

@@ -29,6 +29,7 @@ from .net import ChessNet
 from .self_play_storage import estimate_bytes_per_sample, plan_sample_ranges, save_self_play_payload, slice_batch_cpu
 from .policy_surprise import derive_counters as derive_surprise_counters
 from .policy_surprise import surprise_meta
+from .search_rules import start_meta
 from .resign import derive_counters
 from .self_play_types import SelfPlayV1Stats
 from .trajectory_buffer import TensorSelfPlayBatch
@@ -210,6 +211,8 @@ def write_worker_chunks(run_once, *, worker_idx: int, device: str, games: int, g
     wmeta.update(meta_common)
     if "policy_surprise" in wmeta:      # policy surprise weighting: its weight and what the resampling did in this shard
         wmeta["policy_surprise"] = surprise_meta(wmeta["policy_surprise"]["weight"], stats.mcts_counters)
+    if "start_bank" in wmeta:           # the start bank: its settings and what was captured and forked in this shard
+        wmeta["start_bank"] = start_meta(wmeta["start_bank"], stats.mcts_counters)
     manifest = {
         "payload_format": "v1_worker_chunk_manifest", "version": 1, "num_samples": int(sum(sizes)),
         "num_shards": len(files), "shard_files": list(files), "shard_sizes": list(sizes),
@@ -462,6 +465,8 @@ class StreamedShardFiles:
         wmeta.update(self.meta_common)
         if "policy_surprise" in wmeta:  # policy surprise weighting: its weight and what the resampling did in this shard
             wmeta["policy_surprise"] = surprise_meta(wmeta["policy_surprise"]["weight"], stats.mcts_counters)
+        if "start_bank" in wmeta:       # the start bank: its settings and what was captured and forked in this shard
+            wmeta["start_bank"] = start_meta(wmeta["start_bank"], stats.mcts_counters)
         manifest = {
             "payload_format": "v1_worker_chunk_manifest", "version": 1, "num_samples": int(sum(self.sizes)),
             "num_shards": len(self.files), "shard_files": list(self.files), "shard_sizes": list(self.sizes),
@@ -592,8 +597,8 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
     """`search_options`: the optional rules of the tree backend's search, under the names and defaults of
     `search_rules.SearchRules.parse` and described there (symmetric evaluation, playout cap, forced playouts, Gumbel root
     search, TD(lambda) targets, MCTS-Solver, PUCT shape, resignation, KLD-gain stop, move re-pick, temperature half-life,
-    policy surprise).  They are validated and refused before a device is touched; the rules that are on are recorded in
-    the manifests' metadata (`SearchRules.meta`)."""
+    policy surprise, the start bank -- one bank per shard, reused by every chunk).  They are validated and refused before a
+    device is touched; the rules that are on are recorded in the manifests' metadata (`SearchRules.meta`)."""
     from .search_rules import SearchRules, persistent_default
     rules = SearchRules.parse(mcts_simulations, **search_options)
     rules.refuse(search_backend=search_backend, sample_moves=sample_moves, persistent=persistent_default(),
@@ -628,6 +633,7 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                              "manifest output.")
 
         chunk_no = [0]
+        bank = []                             # the start bank of this shard, made with the first chunk that needs it
         tree = backend in ("portable", "tree")
         stream = os.environ.get("LZ_WORKER_STREAM", "1") != "0"
         if stream and not tree:
@@ -658,11 +664,14 @@ def run_self_play_worker(*, worker_idx: int, shard_device: str, shard_games: int
                           sample_moves=bool(sample_moves), concurrent_games=max(1, min(n, concurrent)), verbose=False)
             if backend in ("portable", "tree"):
                 from .tree_engine import self_play_tree_gpu
+                if rules.start and not bank:
+                    from .start_bank import StartBank
+                    bank.append(StartBank(rules.start_kwargs()["start_bank_capacity"], dev))
                 return self_play_tree_gpu(evaluator, opening_random_moves=int(opening_random_moves),
                                           policy_target_temperature=policy_target_temperature,
                                           policy_target_prior_pseudocount=float(policy_target_prior_pseudocount),
                                           seed=rng_seed, collect_timing=os.environ.get("LZ_WORKER_TIMING", "1") != "0", row_log=row_log,
-                                          **rules.kwargs(), **common)
+                                          **({"start_bank": bank[0]} if bank else {}), **rules.kwargs(), **common)
             from .self_play_gpu_runner import self_play_v1_gpu
             return self_play_v1_gpu(evaluator, opening_random_moves=int(opening_random_moves), sparse_ply=int(sparse_ply),
                                     sparse_top_k=int(sparse_top_k), row_log=row_log, **common)

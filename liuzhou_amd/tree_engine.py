@@ -36,7 +36,7 @@ from .kld_stop import KldStop, parse_kld_stop
 from .move_pick import temperature_table
 from .policy_surprise import counters_from_block as surprise_counters_from_block, root_prior
 from .resign import counters_from_block
-from .search_rules import (SearchRules, engine_counters, forced_playouts_on, parse_eval_symmetry,
+from .search_rules import (START_COUNTER_KEYS, SearchRules, engine_counters, forced_playouts_on, parse_eval_symmetry,
                            persistent_default as _persistent_default, playout_cap_on, search_simulations)
 
 MAX_CHILDREN = 72
@@ -1802,7 +1802,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        policy_target_prior_pseudocount: float = 0.0, reuse_tree: bool = True,
                        reuse_factor: float = -1.0, dual_stream: Optional[bool] = None, continuous_waves: bool = True,
                        device_tail: bool = True, batch_k: int = 1, evaluator: str = "auto", seed: int = 12345,
-                       collect_timing: bool = False, row_log=None,
+                       collect_timing: bool = False, row_log=None, start_bank=None,
                        **search_options) -> Tuple[TensorSelfPlayBatch, SelfPlayV1Stats]:
     """Tree-search twin of self_play_v1_gpu (same outputs); mirrors v1/python/portable_self_play.py:82-284,
     including the subtree reuse it performs on every move (:191, `reuse_tree`).
@@ -1815,12 +1815,15 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
     game ends and the returned batch is empty; needs `device_tail` and `continuous_waves`.
     `search_options`: the optional rules of the search and of the per-ply tail -- symmetric evaluation, playout cap,
     forced playouts, Gumbel root search, TD(lambda) value targets, MCTS-Solver, first-play urgency / visit-scaled cpuct,
-    resignation, KLD-gain early stopping, move re-pick, temperature half-life, policy surprise weighting -- under the names
+    resignation, KLD-gain early stopping, move re-pick, temperature half-life, policy surprise weighting, the start bank
+    -- under the names
     and defaults of `search_rules.SearchRules.parse`; what each does, the mcts_counters it adds and what it cannot run
-    with are described in search_rules.  A refusal is a ValueError before anything is allocated."""
+    with are described in search_rules.  A refusal is a ValueError before anything is allocated.
+    `start_bank` (start_bank.StartBank, with the start bank rule on): the bank the games fork from and the searched
+    positions go to; it is the caller's and survives the call.  Without one the call makes a private, empty bank."""
     dev = torch.device(device)
     rules = SearchRules.parse(mcts_simulations, **search_options)
-    cap, resign, surprise = rules.cap, rules.resign_kwargs(), rules.surprise
+    cap, resign, surprise, start = rules.cap, rules.resign_kwargs(), rules.surprise, rules.start_kwargs()
     if row_log is not None and not (device_tail and continuous_waves):
         raise RuntimeError("self_play_tree_gpu: a finished-row log needs device_tail and continuous_waves")
     if evaluator not in ("auto", "fused", "module"):
@@ -1834,6 +1837,16 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                  device_tail=bool(device_tail), prior_evaluator=isinstance(model, PriorEvaluator),
                  policy_target_temperature=policy_target_temperature,
                  policy_target_prior_pseudocount=policy_target_prior_pseudocount)
+    if start_bank is not None:
+        if not start:
+            raise ValueError("self_play_tree_gpu: a start bank was passed but the rule is off (start_fork_prob and "
+                             "start_capture_prob are both 0)")
+        if int(start_bank.capacity) != start["start_bank_capacity"]:
+            raise ValueError(f"self_play_tree_gpu: the start bank holds {int(start_bank.capacity)} positions, "
+                             f"start_bank_capacity is {start['start_bank_capacity']}")
+    elif start:
+        from .start_bank import StartBank
+        start_bank = StartBank(start["start_bank_capacity"], dev)
     net = model if isinstance(model, (FusedNet, PriorEvaluator)) else FusedNet(model, dev) if use_fused else model.eval()
     wave = max(1, min(int(concurrent_games), int(num_games)))
     # two half-batches on two streams (see DualStreamTreeMCTS) once a wave is large enough to fill the chip twice over
@@ -1888,7 +1901,9 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
         from .wave_tail import WaveTail
         tail = WaveTail(buffer, wave, int(max_game_plies), dev, soft_value_k=float(soft_value_k), row_log=row_log,
                         **({"value_target_lambda": rules.td_lambda} if rules.td else {}),
-                        **resign, **({"seed": int(seed)} if (resign or surprise) else {}),
+                        **resign, **({"seed": int(seed)} if (resign or surprise or start) else {}),
+                        **({"start_bank": start_bank, **{k: v for k, v in start.items() if k != "start_bank_capacity"}}
+                           if start else {}),
                         **({"policy_surprise_weight": rules.surprise_weight,
                             "prior_fn": lambda search: root_prior(net, search, use_fused)} if surprise else {}))
         tail.collect_timing = bool(collect_timing)
@@ -1922,7 +1937,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
             lists_below = wave - (samples_per_launch_pass(net) if use_fused else 0)
             if cap:
                 tail.game_plies = game_plies if continuous else game_plies[base:base + g]
-            if resign or surprise:
+            if resign or surprise or start:
                 tail.game_base = 0 if continuous else base
             tail.run(lambda st, temps, dn, reseated: mcts.search_batch(
                          st, temperatures=temps, active=~dn, reset=reseated,
@@ -2042,6 +2057,7 @@ def self_play_tree_gpu(model, num_games: int, mcts_simulations: int, temperature
                        **engine_counters(rules, mcts), **({"recorded_positions": int(positions)} if cap else {}),
                        **(counters_from_block(tail.resign_counters.tolist()) if resign else {}),
                        **(surprise_counters_from_block(tail.surprise_counters.tolist(), float(tail.surprise_sum.item()))
-                          if surprise else {})},
+                          if surprise else {}),
+                       **(dict(zip(START_COUNTER_KEYS, (int(x) for x in tail.start_counters.tolist()))) if start else {})},
         piece_delta_buckets={str(d - 18): int(v) for d, v in enumerate(hist)}, device=str(dev))
     return batch, stats

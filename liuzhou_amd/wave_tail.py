@@ -2,7 +2,8 @@
 finalisation of finished games without a host round trip (`lz_wave_record`, `lz_wave_step_finish`), and optionally the
 TD(lambda) value targets from the searches' root values (`lz_wave_note_value`, `lz_wave_td_targets`; value_target.py)
 and resignation with play-through calibration (`lz_wave_resign`, `lz_wave_resign_book`; resign.py) and policy surprise
-weighting of a finished game's rows (`lz_wave_note_surprise`, `lz_wave_surprise_resample`; policy_surprise.py).
+weighting of a finished game's rows (`lz_wave_note_surprise`, `lz_wave_surprise_resample`; policy_surprise.py) and the
+start bank that games fork from (`lz_start_bank_capture`, `lz_start_bank_seed`; start_bank.py).
 
 It replaces, for whole waves, the sequence `append_steps` -> `step_index[...] = rows` -> `self_play_step_inplace` ->
 `finalize_games_inplace` of v1/python/self_play_gpu_runner.py:205-247, whose `nonzero`-shaped outputs force one host
@@ -20,7 +21,7 @@ from .mcts_gpu import GpuStateBatch, RootSearchBatchOutput
 from .trajectory_buffer import TensorTrajectoryBuffer
 from .policy_surprise import policy_surprise_on
 from .resign import COUNTER_KEYS, resign_kwargs
-from .search_rules import SearchRules
+from .search_rules import SearchRules, start_bank_on
 from .value_target import td_lambda_on
 
 DELTA_BINS = 37
@@ -31,7 +32,8 @@ class WaveTail:
                  soft_value_k: float = 2.0, reseat: bool = False, row_log=None, value_target_lambda: float = 1.0,
                  resign_threshold: float = 0.0, resign_min_moves: int = 10, resign_consecutive: int = 3,
                  resign_playthrough_fraction: float = 0.1, resign_streak: str = "side", seed: int = 0,
-                 policy_surprise_weight: float = 0.0, prior_fn=None) -> None:
+                 policy_surprise_weight: float = 0.0, prior_fn=None, start_bank=None, start_fork_prob: float = 0.0,
+                 start_capture_prob: float = 0.0, start_min_move: int = 1, start_max_move: int = 143) -> None:
         # TD(lambda) value targets (value_target.py; 1 = off: every row gets the game's result, nothing below exists)
         self.td_lambda = float(value_target_lambda) if td_lambda_on(value_target_lambda) else None
         if self.td_lambda is not None and reseat:
@@ -47,6 +49,18 @@ class WaveTail:
         self.surprise_alpha = float(policy_surprise_weight) if policy_surprise_on(policy_surprise_weight) else None
         if self.surprise_alpha is not None:
             SearchRules(surprise_weight=self.surprise_alpha).refuse(reseat=reseat)
+        # the start bank (start_bank.py; both probabilities 0 = off: nothing below exists and every game starts from the
+        # empty board); the bank is the caller's and outlives the tail
+        capacity = start_bank.capacity if start_bank is not None else 1
+        start = None
+        if start_bank_on(start_fork_prob, start_capture_prob, capacity, start_min_move, start_max_move):
+            if start_bank is None:
+                raise ValueError("WaveTail: the start bank rule is on but no `start_bank` (start_bank.StartBank) was passed")
+            start = SearchRules(start=(float(start_fork_prob), float(start_capture_prob), capacity, int(start_min_move),
+                                       int(start_max_move)))
+            start.refuse(reseat=reseat)
+        elif start_bank is not None:
+            raise ValueError("WaveTail: a start bank was passed but start_fork_prob and start_capture_prob are both 0")
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("WaveTail needs a HIP device (no CPU path)")
@@ -109,6 +123,14 @@ class WaveTail:
             self.surprise_sum = z(1, torch.float64)
             if self.was_live is None:
                 self.was_live = z(self.G, torch.uint8)
+        # the start bank: its parameters and the int64[3] counter block (forked games, the sum of their move counts at
+        # the fork, positions captured)
+        self.bank = self.start = self.start_counters = None
+        if start is not None:
+            if start_bank.device != dev:
+                raise ValueError(f"WaveTail: the start bank lives on {start_bank.device}, the wave on {dev}")
+            self.bank, self.start = start_bank, start.start_kwargs()
+            self.start_counters = z(3, torch.int64)
         if row_log is not None:
             if reseat:
                 raise ValueError("WaveTail: the finished-row log needs run()'s re-seating (reseat=False)")
@@ -276,6 +298,36 @@ class WaveTail:
                 L.ptr(self.surprise_src), L.ptr(self.surprise_counters), L.ptr(self.surprise_sum),
                 L.stream_ptr(self.device)), "wave_surprise_resample")
 
+    def start_capture(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, search: RootSearchBatchOutput,
+                      slot_game: Optional[torch.Tensor] = None) -> None:
+        """The start bank: append a seeded share of this ply's searched positions (after `record` / `note_value` /
+        `note_surprise`, before `resign_step` / `step_finish`: the state is still the searched root)."""
+        term, cvalid = search.terminal_mask.contiguous(), search.chosen_valid_mask.contiguous()
+        if term.element_size() != 1 or int(term.numel()) != self.G or cvalid.element_size() != 1 or int(cvalid.numel()) != self.G:
+            raise RuntimeError("WaveTail.start_capture: terminal_mask and chosen_valid_mask must be one byte per slot")
+        b, p = self.bank, self.start
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_start_bank_capture(
+                C.byref(L.soa(states.tensors())), L.i64(self.G), L.ptr(done), L.ptr(term), L.ptr(cvalid), L.ptr(plies),
+                L.ptr(slot_game), L.i64(self.game_base), C.c_uint64(self.seed), C.c_float(p["start_capture_prob"]),
+                L.i64(p["start_min_move"]), L.i64(p["start_max_move"]), L.ptr(b.entries), L.i64(b.capacity),
+                L.ptr(b.cursor), L.ptr(self.start_counters), L.stream_ptr(self.device)), "start_bank_capture")
+
+    def start_seed(self, states: GpuStateBatch, fresh: torch.Tensor, slot_game: Optional[torch.Tensor] = None) -> None:
+        """The start bank: a seeded share of the slots `fresh` marks (uint8 / bool per slot: they start a game with this
+        ply's search) takes a bank position instead of the empty board."""
+        if fresh.element_size() != 1 or int(fresh.numel()) != self.G or not fresh.is_contiguous():
+            raise RuntimeError("WaveTail.start_seed: `fresh` must be one contiguous byte per slot")
+        ts = states.tensors()
+        if any(not t.is_contiguous() for t in ts):
+            raise RuntimeError("WaveTail.start_seed: state tensors must be contiguous (they are updated in place)")
+        b = self.bank
+        with torch.cuda.device(self.device):
+            L.check(L.lib().lz_start_bank_seed(
+                C.byref(L.soa(ts)), L.i64(self.G), L.ptr(fresh), L.ptr(slot_game), L.i64(self.game_base),
+                C.c_uint64(self.seed), C.c_float(self.start["start_fork_prob"]), L.ptr(b.entries), L.i64(b.capacity),
+                L.ptr(b.cursor), L.ptr(self.start_counters), L.stream_ptr(self.device)), "start_bank_seed")
+
     def start_next_games(self, states: GpuStateBatch, plies: torch.Tensor, done: torch.Tensor, step_counts: torch.Tensor,
                          budget: torch.Tensor, next_game: torch.Tensor, slot_game: torch.Tensor,
                          reseated: Optional[torch.Tensor] = None) -> None:
@@ -306,6 +358,8 @@ class WaveTail:
         note_surprise -> resign -> step_finish -> resign_book -> td_targets -> surprise_resample -> the log: a game's rows
         carry their final targets before they are resampled, and are resampled before they leave.  `prior_fn(search)` is
         called once per ply, right after the search (one extra network launch).
+        With the start bank (`start_fork_prob` / `start_capture_prob` > 0) start_seed follows the re-seat (and precedes the
+        first ply's search, for the slots that are live then), and start_capture follows note_surprise.
         `temperature_table` (float32 on the device, move_pick.temperature_table: the half-life schedule): the temperature of
         a slot is table[min(ply, len - 1)] instead of the t_init / t_final step at `t_threshold`."""
         dev, g = self.device, self.G
@@ -325,6 +379,8 @@ class WaveTail:
         slot_game = self.slot_game
         slot_game.copy_(torch.arange(g, dtype=torch.int64, device=dev))
         reseated = torch.zeros((g,), dtype=torch.uint8, device=dev)
+        forks = self.start is not None and self.start["start_fork_prob"] > 0.0
+        captures = self.start is not None and self.start["start_capture_prob"] > 0.0
         ply = 0
         t_run = time.perf_counter()
         while True:
@@ -340,6 +396,10 @@ class WaveTail:
                     log.poll(k)                                   # may switch log arenas (a segment leaves)
             if games_to_start > 0 and ply > 0:
                 self.start_next_games(states, plies, done, step_counts, budget, next_game, slot_game, reseated)
+                if forks:
+                    self.start_seed(states, reseated, slot_game=slot_game)
+            if forks and ply == 0:                      # a bank filled by an earlier call seeds the first wave too
+                self.start_seed(states, ~done if done.dtype == torch.bool else (done == 0), slot_game=slot_game)
             if temperature_table is not None:
                 temps = temperature_table.index_select(0, plies.clamp(0, int(temperature_table.numel()) - 1))
             else:
@@ -352,6 +412,8 @@ class WaveTail:
                     self.note_value(states, plies, done, step_counts, search)
                 if self.surprise_alpha is not None:
                     self.note_surprise(done, step_counts, search, self.prior_fn(search))
+                if captures:
+                    self.start_capture(states, plies, done, search, slot_game=slot_game)
             with self._bracket("self_play_step_ms"):
                 if self.resign is not None:
                     self.resign_step(states, plies, done, search, slot_game=slot_game)

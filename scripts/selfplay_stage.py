@@ -101,6 +101,15 @@ def parse(argv=None):
     ap.add_argument("--policy_surprise_weight", type=float, default=0.0,
                     help="policy surprise weighting (tree backend): share of a game's total row weight handed out in "
                          "proportion to KL(policy target || network prior); in [0, 1], 0 = off (KataGo uses 0.5)")
+    ap.add_argument("--start_fork_prob", type=float, default=0.0,
+                    help="start bank (tree backend): share of the games that start from a position of an earlier game "
+                         "instead of the empty board (liuzhou_amd/start_bank.py); in [0, 1], 0 = off")
+    ap.add_argument("--start_capture_prob", type=float, default=0.0,
+                    help="start bank: share of the searched positions that is kept in the shard's bank; in [0, 1], 0 = off")
+    ap.add_argument("--start_bank_capacity", type=int, default=65536, help="start bank: positions the ring holds")
+    ap.add_argument("--start_min_move", type=int, default=1,
+                    help="start bank: smallest move count that is kept (1: never the empty board)")
+    ap.add_argument("--start_max_move", type=int, default=143, help="start bank: largest move count that is kept")
     ap.add_argument("--self_play_target_samples_per_shard", type=int, default=0)
     ap.add_argument("--self_play_chunk_target_bytes", type=int, default=0)
     ap.add_argument("--self_play_shard_dir", default=None)
@@ -176,7 +185,11 @@ def main(argv=None) -> int:
         **({"move_visit_offset": args.move_visit_offset, "move_value_cutoff": args.move_value_cutoff}
            if (args.move_visit_offset != 0.0 or args.move_value_cutoff != 0.0) else {}),
         **({"temperature_halflife": args.temperature_halflife} if args.temperature_halflife != 0.0 else {}),
-        **({"policy_surprise_weight": args.policy_surprise_weight} if args.policy_surprise_weight != 0.0 else {}))
+        **({"policy_surprise_weight": args.policy_surprise_weight} if args.policy_surprise_weight != 0.0 else {}),
+        **({"start_fork_prob": args.start_fork_prob, "start_capture_prob": args.start_capture_prob,
+            "start_bank_capacity": args.start_bank_capacity, "start_min_move": args.start_min_move,
+            "start_max_move": args.start_max_move}
+           if (args.start_fork_prob != 0.0 or args.start_capture_prob != 0.0) else {}))
     print(f"[selfplay] games={stats.num_games} positions={stats.num_positions} "
           f"positions/s={stats.positions_per_sec:.1f} W/L/D={stats.black_wins}/{stats.white_wins}/{stats.draws} "
           f"shards={manifest['num_shards']} -> {output}", flush=True)

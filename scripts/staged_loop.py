@@ -114,7 +114,24 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--validate-evaluator", default=None, choices=("module", "fused"),
                     help="forward pass of --validate 1: the PyTorch module under autocast (default) or the fp16 kernels "
                          "self-play runs")
+    ap.add_argument("--start-fork-prob", type=float, default=0.0,
+                    help="start bank (tree search): share of the games that start from a position of an earlier game "
+                         "instead of the empty board (liuzhou_amd/start_bank.py); every playing rank keeps one bank "
+                         "across the iterations; 0 = off")
+    ap.add_argument("--start-capture-prob", type=float, default=0.0,
+                    help="start bank: share of the searched positions that is kept in the bank; 0 = off")
+    ap.add_argument("--start-bank-capacity", type=int, default=65536, help="start bank: positions the ring holds")
+    ap.add_argument("--start-min-move", type=int, default=1, help="start bank: smallest move count that is kept")
+    ap.add_argument("--start-max-move", type=int, default=143, help="start bank: largest move count that is kept")
     return ap
+
+
+def start_options(args) -> dict:
+    """The start bank's flat options, {} when the rule is off."""
+    from liuzhou_amd.search_rules import SearchRules
+    return SearchRules.parse(args.sims, start_fork_prob=args.start_fork_prob, start_capture_prob=args.start_capture_prob,
+                             start_bank_capacity=args.start_bank_capacity, start_min_move=args.start_min_move,
+                             start_max_move=args.start_max_move).start_kwargs()
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -140,6 +157,11 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error("--replay-merge-value-target distribution needs --replay-merge-positions exact or symmetric")
     if not args.validate and args.validate_evaluator is not None:
         ap.error("--validate-evaluator needs --validate 1")
+    try:
+        if start_options(args) and args.search != "tree":
+            ap.error("--start-fork-prob / --start-capture-prob need --search tree")
+    except ValueError as exc:
+        ap.error(str(exc))
     return args
 
 
@@ -275,6 +297,10 @@ def main(argv=None) -> int:
     log = []
     fused = FusedNet(model, dev) if plays else None
     pending = None                                                     # overlap: the generation gathered last iteration
+    start = start_options(args) if plays else {}
+    if start:                                                          # this rank's start bank, kept across the iterations
+        from liuzhou_amd.start_bank import StartBank
+        start["start_bank"] = StartBank(start["start_bank_capacity"], dev)
     digests_seen = []
     for it in range(1, args.iterations + 1):
         if world > 1:
@@ -289,7 +315,7 @@ def main(argv=None) -> int:
             batch, _stats = play(fused, num_games=args.games_per_gpu, mcts_simulations=args.sims,
                                  temperature_init=1.0, temperature_final=0.1, temperature_threshold=10,
                                  exploration_weight=1.0, device=str(dev), max_game_plies=args.max_game_plies,
-                                 concurrent_games=args.games_per_gpu)
+                                 concurrent_games=args.games_per_gpu, **start)
             torch.cuda.synchronize(dev)
             t_play = time.perf_counter() - t0
         else:
