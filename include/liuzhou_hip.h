@@ -407,6 +407,30 @@ LZ_API int lz_start_bank_seed(const LzStateSoA* states, int64_t num_slots, const
                               const uint8_t* entries, int64_t capacity, const int64_t* cursor, int64_t* counters,
                               void* stream);
 
+/* The opening book: positions of a start bank as arena openings (csrc/lz_opening_book.h holds the scalar rules, host and
+ * device).  Records are the 32-byte packed states of the bank, uint8[m, 32].
+ *
+ * lz_opening_book_keys: for record i in [0, m), one lane each, valid[i] = 1 iff the record is canonical (packing its
+ * unpacked state gives the same 32 bytes), its phase is in 1..7, no cell is both black and white, the game is running
+ * (game_status 0), the position has a legal action (the tree search's enumeration) and min_move <= move_count <=
+ * max_move; else 0.  A valid record's keys[i] = {img0 | meta << 36, img1, img2, img3}: the four boards under the
+ * symmetry sym[i] in 0..7 that makes (img0..img3) smallest (the lowest such index; lz_dedup_position_keys' choice), meta =
+ * bits 50..63 of word 0 (phase, player, forced, pending marks / captures).  move_count and moves_since_capture are not
+ * in the key.  An invalid record's keys[i] = {INT64_MIN | i, 0, 0, 0}, sym[i] = 0.  Every byte of valid[0..m),
+ * keys[0..4m) and sym[0..m) is written, nothing else; total on any 32 bytes.  m == 0: LZ_OK without a launch.  m < 0,
+ * min_move < 0 or max_move < min_move, a NULL pointer: LZ_ERR_ARG.  records, keys 16-byte aligned (LZ_ERR_ALIGN).
+ *
+ * lz_states_from_packed: the inverse of lz_pack_states, with a gather.  For row g in [0, n), one lane each, with j =
+ * index[g] in [0, capacity) the twelve state tensors of row g become the unpacked records[j]; a row whose index is outside
+ * [0, capacity) is left untouched.  Nothing else is written; records and index are only read.  For canonical records
+ * lz_pack_states of the rows returns the gathered bytes.  n == 0: LZ_OK without a launch.  n < 0, capacity < 0, a NULL
+ * pointer (records may be NULL when capacity == 0): LZ_ERR_ARG.  records 16-byte, index 8-byte, the three cell planes
+ * 4-byte aligned (LZ_ERR_ALIGN). */
+LZ_API int lz_opening_book_keys(const uint8_t* records, int64_t m, int64_t min_move, int64_t max_move, uint8_t* valid,
+                                int64_t* keys, int8_t* sym, void* stream);
+LZ_API int lz_states_from_packed(const uint8_t* records, int64_t capacity, const int64_t* index, int64_t n,
+                                 const LzStateSoA* states, void* stream);
+
 /* lz_wave_log_finished: finished-row log of the streaming worker.  The reference worker sees the rows of a wave only
  * after the whole wave has drained and copies them to the host with the GPU idle
  * (v1/python/self_play_worker.py:430-546: `_run_once` -> `chunk_batch.to("cpu")` -> `save_self_play_payload`); here

@@ -109,7 +109,7 @@ HOST_SYMBOLS = ("lz_version", "lz_status_string", "lz_encode_actions_fast", "lz_
                 "lz_symmetry_tables", "lz_symmetry_gather_samples", "lz_symmetry_transform_states",
                 "lz_symmetry_transform_packed", "lz_dedup_position_keys", "lz_dedup_merge_groups", "lz_valid_reduce",
                 "lz_valid_classify", "lz_replay_position_keys", "lz_replay_merge_records", "lz_merge_value_distributions",
-                "lz_start_bank_capture", "lz_start_bank_seed")
+                "lz_start_bank_capture", "lz_start_bank_seed", "lz_opening_book_keys", "lz_states_from_packed")
 _STATUS = {0: "ok", -1: "invalid argument", -2: "unsupported dimensions", -3: "kernel launch failed",
            -4: "misaligned pointer", -5: "illegal action for the state"}
 

@@ -9,8 +9,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libliuzhou_hip.so")
 SOURCES = ("lz_ops.hip", "lz_engine.hip", "lz_net.hip", "lz_net_f32.hip", "lz_train.hip", "lz_search.hip", "lz_symmetry.hip",
-           "lz_dedup.hip", "lz_replay_merge.hip", "lz_valid.hip", "lz_value_dist.hip")
-HEADERS = ("lz_rules.h", "lz_soa.h", "lz_symmetry.h", "lz_wave.h", "lz_rng.h", "lz_net_dev.h", "lz_live_index.h", "lz_surprise.h", "lz_tree_dev.h", "lz_dedup.h", "lz_replay_merge.h", "lz_valid.h", "lz_value_dist.h", "lz_start_bank.h", os.path.join("..", "..", "include", "liuzhou_hip.h"))
+           "lz_dedup.hip", "lz_replay_merge.hip", "lz_valid.hip", "lz_value_dist.hip", "lz_opening_book.hip")
+HEADERS = ("lz_rules.h", "lz_soa.h", "lz_symmetry.h", "lz_wave.h", "lz_rng.h", "lz_net_dev.h", "lz_live_index.h", "lz_surprise.h", "lz_tree_dev.h", "lz_dedup.h", "lz_replay_merge.h", "lz_valid.h", "lz_value_dist.h", "lz_start_bank.h", "lz_state_rows.h", "lz_state_rows_host.h", "lz_opening_book.h", os.path.join("..", "..", "include", "liuzhou_hip.h"))
 
 
 def hipcc_path() -> str:
@@ -27,7 +27,8 @@ HOST_SOURCES = (HOST_SOURCE, os.path.join(CSRC, "lz_scalar.cpp"),      # the ope
                 os.path.join(CSRC, "lz_dedup_host.cpp"),                # + the position dedup, rows and records
                 os.path.join(CSRC, "lz_valid_host.cpp"),                # + the validation sums and classification
                 os.path.join(CSRC, "lz_value_dist_host.cpp"),           # + the value distributions of merged groups
-                os.path.join(CSRC, "lz_start_bank_host.cpp"))           # + the start bank's capture and seed
+                os.path.join(CSRC, "lz_start_bank_host.cpp"),           # + the start bank's capture and seed
+                os.path.join(CSRC, "lz_opening_book_host.cpp"))         # + the opening book's keys and seating
 
 
 def build_host(force: bool = False, verbose: bool = False) -> str:

@@ -37,6 +37,8 @@ class EvaluationStats:
     total_games: int
     color_breakdown: Dict[str, Dict[str, int]] = field(default_factory=dict)
     move_log: Optional[torch.Tensor] = None      # int32[games, plies] 220-d action indices (-1 pad), if recorded
+    openings: Optional[torch.Tensor] = None      # int64[games] opening-book entry of every game (CPU), with a book
+    paired: Optional[Dict[str, Any]] = None      # opening_book.paired_statistics + book_size / openings_used / opening_move_mean
 
     def _rate(self, v: int) -> float:
         return 0.0 if self.total_games == 0 else v / self.total_games
@@ -54,10 +56,13 @@ class EvaluationStats:
         return self._rate(self.draws)
 
     def to_payload(self, name: str) -> Dict[str, Any]:
-        return {"name": str(name), "wins": int(self.wins), "losses": int(self.losses), "draws": int(self.draws),
-                "total_games": int(self.total_games), "win_rate": float(self.win_rate),
-                "loss_rate": float(self.loss_rate), "draw_rate": float(self.draw_rate),
-                "color_breakdown": {k: dict(v) for k, v in self.color_breakdown.items()}}
+        out = {"name": str(name), "wins": int(self.wins), "losses": int(self.losses), "draws": int(self.draws),
+               "total_games": int(self.total_games), "win_rate": float(self.win_rate),
+               "loss_rate": float(self.loss_rate), "draw_rate": float(self.draw_rate),
+               "color_breakdown": {k: dict(v) for k, v in self.color_breakdown.items()}}
+        if self.paired is not None:                          # only when an opening book was used
+            out["paired"] = dict(self.paired)
+        return out
 
 
 def _uniform_legal_codes(state: GpuStateBatch):
@@ -183,15 +188,60 @@ def _joinable(agents: Sequence[TreeSearchAgent]) -> bool:
                                          for x in agents)
 
 
+def _check_book(opening_book, games: int, opening_random_moves: int, what: str) -> None:
+    """The refusals of a match of `games` games from a book: what a book cannot be combined with is a ValueError."""
+    from .opening_book import OpeningBook
+    if not isinstance(opening_book, OpeningBook) or len(opening_book) < 1:
+        raise ValueError("opening_book must be an OpeningBook with at least one position")
+    if int(opening_random_moves) > 0:
+        raise ValueError("an opening book cannot be combined with opening_random_moves > 0: the book's positions are the "
+                         "openings")
+    if int(games) < 2 or int(games) % 2 != 0:
+        raise ValueError(f"with an opening book {what} must be even (every opening is played twice, colours swapped), "
+                         f"got {games}")
+
+
+def _book_openings(opening_book, opening_seed: int, games: int, opening_random_moves: int, what: str) -> torch.Tensor:
+    """int64[games] (CPU): the book entry of every game of a match of `games` games -- game p and game p + games/2 share
+    the opening of pair p (opening_book.assign_openings)."""
+    from .opening_book import assign_openings
+    _check_book(opening_book, games, opening_random_moves, what)
+    return assign_openings(len(opening_book), int(games) // 2, int(opening_seed)).repeat(2)
+
+
+def _seat_openings(states: GpuStateBatch, opening_book, openings: torch.Tensor) -> None:
+    """One lz_states_from_packed launch: game g starts from book entry openings[g]."""
+    from .opening_book import states_from_packed
+    book = opening_book if opening_book.device == states.device else opening_book.to(states.device)
+    states_from_packed(book.positions, openings.to(states.device).contiguous(), states.tensors())
+
+
+def _paired(res: torch.Tensor, opening_book, openings: torch.Tensor) -> Dict[str, Any]:
+    """The pair statistics of one match: `res` the challenger's results (+1 / 0 / -1) of its games, first half then
+    second half, `openings` their book entries."""
+    from .opening_book import paired_statistics
+    points = ((res.to(torch.float64) + 1.0) / 2.0).cpu()
+    half = int(points.numel()) // 2
+    out = paired_statistics(points[:half], points[half:])
+    used = openings[:half]
+    out["book_size"] = len(opening_book)
+    out["openings_used"] = int(torch.unique(used).numel())
+    out["opening_move_mean"] = float(opening_book.move_counts.cpu().index_select(0, used).to(torch.float64).mean())
+    return out
+
+
 def _play_games(agents: Sequence[Any], player_a: torch.Tensor, player_b: torch.Tensor, a_black: torch.Tensor, device, *,
                 joint: bool = True, opening_random_moves: int = 0, max_game_plies: int = 512,
-                record_moves: bool = False):
-    """Tree-backend game loop: game g between agents player_a[g] (black iff a_black[g]) and player_b[g].  Returns
-    (result from black's side float32[n], move log int32[n, plies] or None)."""
+                record_moves: bool = False, opening_book=None, openings: Optional[torch.Tensor] = None):
+    """Tree-backend game loop: game g between agents player_a[g] (black iff a_black[g]) and player_b[g], from the empty
+    board or, with a book, from its entry openings[g].  Returns (result from black's side float32[n], move log
+    int32[n, plies] or None)."""
     dev = torch.device(device)
     n = int(player_a.numel())
     G = _pad16(n)
     states = GpuStateBatch.initial(dev, n)
+    if opening_book is not None:
+        _seat_openings(states, opening_book, openings)
     plies = torch.zeros((n,), dtype=torch.int64, device=dev)
     done = torch.zeros((n,), dtype=torch.bool, device=dev)
     result_black = torch.zeros((n,), dtype=torch.float32, device=dev)
@@ -262,7 +312,8 @@ def _play_games(agents: Sequence[Any], player_a: torch.Tensor, player_b: torch.T
     return result_black, (torch.stack(log, dim=1) if (record_moves and log) else None)
 
 
-def _stats(result_black: torch.Tensor, challenger_black: torch.Tensor, move_log) -> EvaluationStats:
+def _stats(result_black: torch.Tensor, challenger_black: torch.Tensor, move_log, opening_book=None,
+           openings: Optional[torch.Tensor] = None) -> EvaluationStats:
     n = int(result_black.numel())
     res = torch.where(challenger_black, result_black, -result_black)
     win, loss, draw = res > 0, res < 0, res == 0
@@ -270,16 +321,25 @@ def _stats(result_black: torch.Tensor, challenger_black: torch.Tensor, move_log)
     for name, sel in (("black", challenger_black), ("white", ~challenger_black)):
         cb[name] = {"wins": int((win & sel).sum()), "losses": int((loss & sel).sum()), "draws": int((draw & sel).sum()),
                     "games": int(sel.sum())}
-    return EvaluationStats(wins=int(win.sum()), losses=int(loss.sum()), draws=int(draw.sum()), total_games=n,
-                           color_breakdown=cb, move_log=move_log)
+    stats = EvaluationStats(wins=int(win.sum()), losses=int(loss.sum()), draws=int(draw.sum()), total_games=n,
+                            color_breakdown=cb, move_log=move_log)
+    if opening_book is not None:
+        stats.openings, stats.paired = openings, _paired(res, opening_book, openings)
+    return stats
 
 
 def play_matches(challenger, opponent, num_games: int, device, *, opening_random_moves: int = 0,
                  max_game_plies: int = 512, seed: Optional[int] = None, record_moves: bool = False,
-                 joint: bool = True) -> EvaluationStats:
+                 joint: bool = True, opening_book=None, opening_seed: int = 0) -> EvaluationStats:
     """All `num_games` games at once on `device`; returns the challenger's W/L/D (`record_moves`: plus every game's
     sequence of 220-d action indices in `move_log`).  With a `TreeSearchAgent` on either side the tree backend's loop
-    runs; `joint` (two tree agents): one search per ply over both sides' games, else one per agent."""
+    runs; `joint` (two tree agents): one search per ply over both sides' games, else one per agent.
+    `opening_book` (an `OpeningBook`; `num_games` even): game p and game p + num_games/2 start from the book entry of pair
+    p (`assign_openings(len(book), num_games/2, opening_seed)`), the challenger black in the first and white in the second;
+    the stats gain `openings` and `paired`.  The states' own move_count / moves_since_capture carry the game limits."""
+    openings = None
+    if opening_book is not None:
+        openings = _book_openings(opening_book, opening_seed, num_games, opening_random_moves, "num_games")
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("eval arena needs a HIP device (no CPU path)")
@@ -292,9 +352,11 @@ def play_matches(challenger, opponent, num_games: int, device, *, opening_random
         res, log = _play_games([challenger, opponent], torch.zeros((n,), dtype=torch.int64, device=dev),
                                torch.ones((n,), dtype=torch.int64, device=dev), challenger_black, dev, joint=joint,
                                opening_random_moves=opening_random_moves, max_game_plies=max_game_plies,
-                               record_moves=record_moves)
-        return _stats(res, challenger_black, log)
+                               record_moves=record_moves, opening_book=opening_book, openings=openings)
+        return _stats(res, challenger_black, log, opening_book, openings)
     states = GpuStateBatch.initial(dev, n)
+    if opening_book is not None:
+        _seat_openings(states, opening_book, openings)
     plies = torch.zeros((n,), dtype=torch.int64, device=dev)
     done = torch.zeros((n,), dtype=torch.bool, device=dev)
     challenger_black = torch.arange(n, device=dev) < (n / 2)          # eval_checkpoint.py:487-495
@@ -340,8 +402,11 @@ def play_matches(challenger, opponent, num_games: int, device, *, opening_random
     for name, sel in (("black", challenger_black), ("white", ~challenger_black)):
         cb[name] = {"wins": int((win & sel).sum()), "losses": int((loss & sel).sum()), "draws": int((draw & sel).sum()),
                     "games": int(sel.sum())}
-    return EvaluationStats(wins=int(win.sum()), losses=int(loss.sum()), draws=int(draw.sum()), total_games=n,
-                           color_breakdown=cb, move_log=torch.stack(log, dim=1) if (record_moves and log) else None)
+    stats = EvaluationStats(wins=int(win.sum()), losses=int(loss.sum()), draws=int(draw.sum()), total_games=n,
+                            color_breakdown=cb, move_log=torch.stack(log, dim=1) if (record_moves and log) else None)
+    if opening_book is not None:
+        stats.openings, stats.paired = openings, _paired(res, opening_book, openings)
+    return stats
 
 
 def load_checkpoint_model(path: str):
@@ -379,10 +444,13 @@ def evaluate_checkpoint(challenger_checkpoint: str, opponent_checkpoint: Optiona
                         sample_moves: bool = False, opening_random_moves: int = 0, max_game_plies: int = 512,
                         seed: int = 0, search_backend: str = "v1", fpu_reduction: Optional[float] = None,
                         fpu_root_reduction: Optional[float] = None, cpuct_log: float = 0.0,
-                        cpuct_base: float = 19652.0) -> Dict[str, Any]:
+                        cpuct_base: float = 19652.0, opening_book=None, opening_seed: int = 0) -> Dict[str, Any]:
     """vs-previous (two checkpoints) or vs-random (opponent None) probe; payload as eval_checkpoint.py:139-154.
-    `search_backend`: "v1" (root PUCT) or "portable" (the tree search, both sides in one engine)."""
+    `search_backend`: "v1" (root PUCT) or "portable" (the tree search, both sides in one engine).  `opening_book`: the
+    games are colour-swapped pairs from the book (play_matches) and the payload gains the key "paired"."""
     games = int(num_games) if int(num_games) % 2 == 0 else max(2, (int(num_games) // 2) * 2)   # even (:48-54)
+    if opening_book is not None:                              # refusals before a checkpoint is read
+        _check_book(opening_book, games, opening_random_moves, "num_games")
     if search_backend not in SEARCH_BACKENDS:
         raise ValueError(f"search_backend must be one of {SEARCH_BACKENDS}, got {search_backend!r}")
     shape = dict(fpu_reduction=fpu_reduction, fpu_root_reduction=fpu_root_reduction, cpuct_log=cpuct_log,
@@ -392,8 +460,9 @@ def evaluate_checkpoint(challenger_checkpoint: str, opponent_checkpoint: Optiona
     opp = RandomAgent() if not opponent_checkpoint else make_agent(
         load_checkpoint_model(opponent_checkpoint), search_backend, device, mcts_simulations, temperature, sample_moves,
         seed, **shape)
+    book = {} if opening_book is None else dict(opening_book=opening_book, opening_seed=opening_seed)
     stats = play_matches(chall, opp, games, device, opening_random_moves=opening_random_moves,
-                         max_game_plies=max_game_plies, seed=seed)
+                         max_game_plies=max_game_plies, seed=seed, **book)
     payload = stats.to_payload("vs_previous" if opponent_checkpoint else "vs_random")
     payload["seed"] = int(seed)
     return payload
@@ -417,10 +486,14 @@ class RoundRobinResult:
 
 def play_round_robin(models: Sequence[Any], games_per_pair: int, device, *, joint: bool = True,
                      opening_random_moves: int = 0, max_game_plies: int = 512, seed: Optional[int] = None,
-                     record_moves: bool = False) -> RoundRobinResult:
+                     record_moves: bool = False, opening_book=None, opening_seed: int = 0) -> RoundRobinResult:
     """Every pair (i < j) of up to 8 agents (TreeSearchAgents in one engine, one segment each, when `joint`) plays
     `games_per_pair` games, i black in the first half of them; all games at once.  Pair (i, j)'s games are what
-    play_matches(models[i], models[j], games_per_pair) plays when no random moves are drawn."""
+    play_matches(models[i], models[j], games_per_pair) plays when no random moves are drawn.  `opening_book`
+    (`games_per_pair` even): every model pair plays the same assignment of openings, the one play_matches makes."""
+    openings = None
+    if opening_book is not None:
+        openings = _book_openings(opening_book, opening_seed, games_per_pair, opening_random_moves, "games_per_pair")
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("eval arena needs a HIP device (no CPU path)")
@@ -436,13 +509,14 @@ def play_round_robin(models: Sequence[Any], games_per_pair: int, device, *, join
     pb = torch.cat([torch.full((m,), j, dtype=torch.int64, device=dev) for _, j in pairs])
     a_black = first.repeat(len(pairs))
     res, log = _play_games(list(models), pa, pb, a_black, dev, joint=joint, opening_random_moves=opening_random_moves,
-                           max_game_plies=max_game_plies, record_moves=record_moves)
+                           max_game_plies=max_game_plies, record_moves=record_moves, opening_book=opening_book,
+                           openings=None if openings is None else openings.repeat(len(pairs)))
     wdl = torch.zeros((K, K, 3), dtype=torch.int64)
     points = [0] * K
     pair_stats = {}
     for p, (i, j) in enumerate(pairs):
         sl = slice(p * m, (p + 1) * m)
-        st = _stats(res[sl], first, None if log is None else log[sl])
+        st = _stats(res[sl], first, None if log is None else log[sl], opening_book, openings)
         pair_stats[(i, j)] = st
         wdl[i, j] = torch.tensor([st.wins, st.draws, st.losses])
         wdl[j, i] = torch.tensor([st.losses, st.draws, st.wins])

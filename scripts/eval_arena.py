@@ -37,6 +37,8 @@ def parse(argv=None):
     ap.add_argument("--fpu_root_reduction", type=float, default=None)    # ... at the root (default: --fpu_reduction)
     ap.add_argument("--cpuct_log", type=float, default=0.0)              # tree backend: visit-scaled cpuct (0 = off)
     ap.add_argument("--cpuct_base", type=float, default=19652.0)
+    ap.add_argument("--opening_book", default=None)                      # an OpeningBook file (scripts/build_opening_book.py):
+    ap.add_argument("--opening_seed", type=int, default=0)               # colour-swapped pairs from it, assigned by this seed
     args, ignored = ap.parse_known_args(argv)
     args.ignored = ignored
     return args
@@ -47,8 +49,21 @@ def backend_of(args) -> str:
     return "portable" if str(args.backend).strip().lower() == "portable" else "v1"
 
 
+def opening_book_of(args):
+    """The book of --opening_book on the evaluation device, None without the flag.  Refused together with random
+    opening moves, before the file or the device is touched."""
+    if not args.opening_book:
+        return None
+    if int(args.v1_opening_random_moves) > 0:
+        raise ValueError("--opening_book cannot be combined with --v1_opening_random_moves > 0: the book's positions are "
+                         "the openings")
+    from liuzhou_amd.opening_book import OpeningBook
+    return OpeningBook.load(args.opening_book, args.device)
+
+
 def main(argv=None) -> int:
     args = parse(argv)
+    book = opening_book_of(args)
     from liuzhou_amd.eval_arena import evaluate_checkpoint
     seed = 0 if args.seed is None else int(args.seed)
     backend = backend_of(args)
@@ -60,6 +75,8 @@ def main(argv=None) -> int:
         common.update(fpu_reduction=args.fpu_reduction, fpu_root_reduction=args.fpu_root_reduction)
     if args.cpuct_log != 0.0:
         common.update(cpuct_log=args.cpuct_log, cpuct_base=args.cpuct_base)
+    if book is not None:
+        common.update(opening_book=book, opening_seed=int(args.opening_seed))
     out = {"challenger_checkpoint": args.challenger_checkpoint, "previous_checkpoint": args.previous_checkpoint,
            "backend": backend, "mcts_simulations": int(args.mcts_simulations), "seed": seed}
     if args.eval_games_vs_random > 0:
@@ -72,6 +89,11 @@ def main(argv=None) -> int:
             p = out[key]
             print(f"[eval] {args.match_name or key}: W-L-D={p['wins']}-{p['losses']}-{p['draws']} ({p['total_games']} games), "
                   f"win={p['win_rate'] * 100:.2f}% loss={p['loss_rate'] * 100:.2f}% draw={p['draw_rate'] * 100:.2f}%", flush=True)
+            if "paired" in p:
+                q = p["paired"]
+                print(f"[eval] {args.match_name or key}: {q['pairs']} pairs from {q['openings_used']} of {q['book_size']} openings, "
+                      f"pentanomial={q['pentanomial']} score={q['score']:.4f} +- {q['score_stderr']:.4f} "
+                      f"(as independent games: +- {q['trinomial_stderr']:.4f}) los={q['los']:.3f}", flush=True)
     if args.output_json:
         os.makedirs(os.path.dirname(args.output_json) or ".", exist_ok=True)
         with open(args.output_json, "w") as f:
